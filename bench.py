@@ -10,12 +10,17 @@ on rank 0.  condition_on_previous_text = False, temperature 0.
 
 Default (weak scaling, BASELINE config 3 at N = 1): the file holds ``--seconds``
 (600) of audio per rank.  ``--sharded-file 1`` (config 4): one file of ``--seconds``
-(e.g. 3600) in total, whatever the rank count (strong scaling).  With more than one
-rank, rank 0 re-transcribes the whole file unsharded after the timed region and
-reports whether the merged segments equal it (``verify``).
+(e.g. 3600) in total, whatever the rank count (strong scaling).
 
 value = (audio seconds of the whole file x steps) / (max over ranks of the timed
 wall time) = whole-job xRT.  rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times ``--steps`` steps, writes the last step's segment
+records under ``--dump-outputs DIR`` if given, and prints the line from the timed region
+alone.  ``--full`` adds what takes runs of its own after it: the roofline figures of
+the dominant kernels and of the step graph (``time_stage``), the single-window latency,
+the CPU baseline (one rank) and, with more than one rank, rank 0 re-transcribing the
+whole file unsharded and reporting whether the merged segments equal it (``verify``).
 
 Launch: under torch.distributed.run (WORLD_SIZE set) every process is one rank.
 Without it, ``--gpus N`` > 1 starts the N ranks itself (``launch_ranks``): N child
@@ -52,14 +57,23 @@ def parse():
                    help="audio seconds per GPU (weak scaling); with --sharded-file, of the whole file")
     p.add_argument("--sharded-file", type=int, default=0,
                    help="config 4: one file of --seconds sharded over the ranks (strong scaling)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything that is not the headline figure: the per-kernel "
+                        "and step-graph rooflines (time_stage runs), single-window latency (--latency), the unsharded "
+                        "comparison (--verify) and the CPU baseline (--cpu-baseline); without it none of them runs")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 writes what the last timed step returned (the merged segment records) as "
+                        "DIR/<name>.npy, float64, one row per segment")
     p.add_argument("--verify", type=int, default=-1,
-                   help="rank 0 compares the merged segments with an unsharded run (default: when > 1 rank)")
+                   help="with --full: rank 0 compares the merged segments with an unsharded run (default: when > 1 "
+                        "rank)")
     p.add_argument("--latency", type=int, default=1,
-                   help="also time single-window decoding (1 window x beam: the per-token p50 of §8(d))")
+                   help="with --full: also time single-window decoding (1 window x beam: the per-token p50 of §8(d))")
     p.add_argument("--beam", type=int, default=5)
     p.add_argument("--dtype", default="fp16")
     p.add_argument("--max-windows", type=int, default=20)
-    p.add_argument("--cpu-baseline", type=int, default=1)
+    p.add_argument("--cpu-baseline", type=int, default=1,
+                   help="with --full: the CPU oracle decoding one window on this host (1 GPU only)")
     p.add_argument("--cpu-steps", type=int, default=48,
                    help="CPU baseline: beam decoder steps of its window, the step part scaled to the window's 224 "
                         "(a bounded sample: ~20-25 s of CPU work on 16 cores; 0 = the whole 224-step window, ~90 s)")
@@ -77,7 +91,10 @@ def parse():
     p.add_argument("--balance", default="clips", choices=("clips", "tokens"),
                    help="clips per rank: contiguous blocks (clips: equal clip counts, fixed work) or every N-th clip "
                         "(tokens: natural decoding, where EOTs and speech density make windows unequal)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1 (the result line is about the timed steps)")
+    return args
 
 
 def _free_port():
@@ -260,6 +277,39 @@ def load_traffic(kernel):
     return None
 
 
+def seeded_state_dict(dims, seed):
+    """whisper.synthetic.synthetic_state_dict(dims, seed), its tensors drawn on a few
+    threads.  Every tensor has a generator stream of its own, seeded by (seed, name), so
+    the values are those of the serial call; numpy's generators release the GIL, and the
+    1.5 G values of large-v3 take seconds instead of most of a plain run's set-up."""
+    from concurrent.futures import ThreadPoolExecutor
+    from whisper import synthetic as S
+    shapes = S.state_dict_shapes(dims)
+    with ThreadPoolExecutor(max_workers=min(8, len(os.sched_getaffinity(0)))) as pool:
+        tensors = pool.map(lambda kv: S._tensor(kv[0], kv[1], seed), shapes.items())
+        return dict(zip(shapes, tensors))
+
+
+SEGMENT_SCALARS = ("seek", "start", "end", "temperature", "avg_logprob", "compression_ratio", "no_speech_prob")
+
+
+def dump_outputs(out_dir, segments):
+    """--dump-outputs: the segment records a caller of the timed path receives (the last
+    timed step's merged segments, in file order), one float64 array per field with one
+    row per segment: the scalar fields, ``n_tokens`` and ``tokens`` ([segments, longest],
+    rows padded with -1).  ``text`` is the decoding of ``tokens`` and is not written.  A
+    few KB per window: far below any size that would need sampling."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.array([s[k] for s in segments], dtype=np.float64) for k in SEGMENT_SCALARS}
+    arrays["n_tokens"] = np.array([len(s["tokens"]) for s in segments], dtype=np.float64)
+    tokens = np.full((len(segments), max((len(s["tokens"]) for s in segments), default=0)), -1.0, dtype=np.float64)
+    for i, s in enumerate(segments):
+        tokens[i, :len(s["tokens"])] = s["tokens"]
+    arrays["tokens"] = tokens
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def encoder_flops(dims):
     n, L, T = dims["n_audio_state"], dims["n_audio_layer"], 1500
     conv = 2 * 3000 * dims["n_mels"] * 3 * n + 2 * 1500 * n * 3 * n
@@ -348,6 +398,92 @@ def cpu_baseline(model_name, sd, audio, beams, n_steps):
                        f"beam search, torch CPU fp32, {threads} threads of {cpu_model})")
 
 
+def full_measurements(args, model, dims, n_win, mean_ctx):
+    """--full: the measurements that take GPU runs of their own after the timed steps (the
+    rooflines of the dominant kernel, the cross-attention and the step graph; the
+    single-window latency).  Returns their entries of the result line."""
+    import whisper
+    # roofline of the dominant kernel (k_proj: the split-K projections of the decoder
+    # step), timed live with HIP events on the context's stream over launches at the
+    # bench batch (all layers, so weights stream from HBM)
+    model.ctx.encode([3000 * i for i in range(n_win)], [3000] * n_win)
+    from whisper.decoding import DecodingTask
+    task = DecodingTask(model, whisper.DecodingOptions(language="en", beam_size=args.beam))
+    model.ctx.decode_begin(task.wh_opts(), [task.initial_tokens] * n_win, [task.sot_index] * n_win)
+    rows = n_win * args.beam
+    # in-step: every k_proj of 6 eager steps bracketed by HIP events on the context
+    # stream, each behind its real producer kernel (what rocprof sees in the step);
+    # back-to-back: the same launches queued without their producers (time_stage 2)
+    model.ctx.time_stage(7, 2)  # warm-up (without it the same tree read 7.0-8.1 us run to run)
+    gemv_ms = model.ctx.time_stage(7, 6)
+    gemv_b2b_ms = model.ctx.time_stage(2, 3)
+    kern = model.ctx.step_kernels(n_win, args.beam)  # what the library runs for this batch
+    p1 = kern["proj"] == "k_proj1"
+    fused_q = "<qproj" in kern["xattn"]  # the cross-q projected inside the cross-attention (round 6)
+    gemv_bytes = projection_bytes_per_launch(dims, rows, p1, fused_q=fused_q)
+    xattn_ms = model.ctx.time_stage(3, 3)
+    xattn_bytes = cross_attn_bytes_per_launch(dims, n_win, rows, fused_q=fused_q)
+    step_ms = model.ctx.time_stage(0, 20)
+    step_bytes = decoder_step_bytes(dims, n_win, args.beam, mean_ctx)
+
+    # single-window decoding (§8(d)'s p50: one _main_loop iteration at B = beam): one
+    # window, the whole 224-step fixed-work decode through decode_steps, per-token wall
+    # time of each 8-step chunk (graph launches + the host's done poll)
+    latency = None
+    if args.latency:
+        model.ctx.encode([0], [3000])
+        t1 = DecodingTask(model, whisper.DecodingOptions(language="en", beam_size=args.beam,
+                                                         suppress_tokens=f"-1,{task.tokenizer.eot}"))
+        model.ctx.decode_begin(t1.wh_opts(), [t1.initial_tokens], [t1.sot_index])
+        model.ctx.token_ms(reset=True)
+        model.ctx.decode_steps(t1.sample_len)
+        tk1 = model.ctx.token_ms(reset=True)
+        # the step graph alone, on a live window (after decode_steps the window is done and
+        # the selection / merge would return early): begin the batch again, then 20 replays
+        model.ctx.decode_begin(t1.wh_opts(), [t1.initial_tokens], [t1.sot_index])
+        step1 = model.ctx.time_stage(0, 20)
+        latency = {"p50_token_ms_1window": round(float(np.median(tk1)), 4), "step_graph_ms_1window": round(step1, 4),
+                   "step_bytes_1window": decoder_step_bytes(dims, 1, args.beam, mean_ctx),
+                   "roofline_frac_1window": round(decoder_step_bytes(dims, 1, args.beam, mean_ctx) /
+                                                  (step1 * 1e-3) / (HBM_PEAK_GBS * 1e9), 4)}
+
+    def gbs(b, ms):
+        return b / (ms * 1e-3) / 1e9
+
+    # the committed PMC pass (profiles/pmc_traffic.py) ran large-v3 at 20 windows (k_proj,
+    # k_xattn_seg) and at one window (k_proj1): other shapes report no traffic
+    lv3 = args.model == "large-v3"
+    traffic = load_traffic(kern["proj"]) if lv3 and (p1 or n_win == 20) else None
+    xattn_traffic = load_traffic(kern["xattn"].split("<")[0]) if lv3 and n_win == 20 else None
+    out = {
+        "roofline": {"bound": "hbm", "kernel": (f"k_proj1 whole-K projection, fused LayerNorm / epilogue ({rows} rows"
+                                                if p1 else f"k_proj split-K projection ({rows} rows")
+                                               + f", avg of the {'five' if fused_q else 'six'} per decoder layer)",
+                     "achieved": round(gbs(gemv_bytes, gemv_ms), 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(gbs(gemv_bytes, gemv_ms) / HBM_PEAK_GBS, 4),
+                     "traffic": traffic, "bytes_per_launch": gemv_bytes, "ms_per_launch": round(gemv_ms, 5),
+                     "timing": "HIP events around each launch inside eager decoder steps",
+                     "launches_per_layer": 5 if fused_q else 6,
+                     "ms_per_launch_back_to_back": round(gemv_b2b_ms, 5),
+                     "back_to_back_note": "time_stage 2: the layer's projections queued without their "
+                                          "producers; on the k_proj1 path the non-deferred fc2 and the plain QKV "
+                                          "LayerNorm prologue (the step itself defers fc2's residual)"},
+        "roofline_cross_attn": {"bound": "hbm", "kernel": f"{kern['xattn']} ({n_win} windows x {args.beam} beams)",
+                                "achieved": round(gbs(xattn_bytes, xattn_ms), 1), "peak": HBM_PEAK_GBS,
+                                "frac": round(gbs(xattn_bytes, xattn_ms) / HBM_PEAK_GBS, 4),
+                                "traffic": xattn_traffic,
+                                "bytes_per_launch": xattn_bytes, "ms_per_launch": round(xattn_ms, 5)},
+        "roofline_step": {"bound": "hbm", "kernel": f"decoder step hipGraph ({n_win} windows x {args.beam} beams)",
+                          "achieved": round(gbs(step_bytes, step_ms), 1), "peak": HBM_PEAK_GBS,
+                          "frac": round(gbs(step_bytes, step_ms) / HBM_PEAK_GBS, 4),
+                          "bytes_per_launch": step_bytes, "ms_per_launch": round(step_ms, 4)},
+    }
+    if latency:
+        out["latency_1window"] = latency
+        out["p50_token_ms"] = latency["p50_token_ms_1window"]
+    return out
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -366,13 +502,13 @@ def main():
         print(f"bench.py: --max-windows {args.max_windows} exceeds what one context holds at beam {args.beam} in "
               f"{args.dtype} (self-KV cache per layer < 2 GiB): using {lim}", file=sys.stderr, flush=True)
         args.max_windows = lim
-    sd = S.synthetic_state_dict(dims, 0)
+    sd = seeded_state_dict(dims, 0)
     model = whisper.Whisper(whisper.ModelDimensions(**dims), args.model, device=local, dtype=args.dtype,
                             max_windows=args.max_windows, max_group=args.beam)
     model.load_state_dict(sd)
     if args.model in whisper._ALIGNMENT_HEADS:  # as load_model does (reference __init__.py:176-177)
         model.set_alignment_heads(whisper._ALIGNMENT_HEADS[args.model])
-    if not (rank == 0 and world == 1 and args.cpu_baseline):
+    if not (args.full and rank == 0 and world == 1 and args.cpu_baseline):
         del sd
         sd = None
     if args.word_timestamps and world > 1:
@@ -432,8 +568,11 @@ def main():
         with open(args.dump, "w") as f:
             json.dump([{k: s[k] for k in ("seek", "tokens", "avg_logprob", "no_speech_prob")} for s in merged], f)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, merged)
+
     verify = None
-    if (args.verify if args.verify >= 0 else world > 1) and rank == 0:
+    if args.full and (args.verify if args.verify >= 0 else world > 1) and rank == 0:
         # the whole file on this GPU alone, same options, unsharded: the merged records must equal it
         clip_ts = ",".join(f"{30 * i},{30 * (i + 1)}" for i in range(n_clips))
         ref = whisper.transcribe(model, audio, condition_on_previous_text=False, clip_timestamps=clip_ts,
@@ -465,58 +604,6 @@ def main():
                "model": "encoder flops / 2.5 PFLOP/s + decoder step bytes (weights + cross-KV + self-KV at "
                         "mean context 115) / 8 TB/s, rank-local"}
 
-    # roofline of the dominant kernel (k_proj: the split-K projections of the decoder
-    # step), timed live with HIP events on the context's stream over launches at the
-    # bench batch (all layers, so weights stream from HBM)
-    model.ctx.encode([3000 * i for i in range(n_win)], [3000] * n_win)
-    from whisper.decoding import DecodingTask
-    task = DecodingTask(model, whisper.DecodingOptions(language="en", beam_size=args.beam))
-    model.ctx.decode_begin(task.wh_opts(), [task.initial_tokens] * n_win, [task.sot_index] * n_win)
-    rows = n_win * args.beam
-    # in-step: every k_proj of 6 eager steps bracketed by HIP events on the context
-    # stream, each behind its real producer kernel (what rocprof sees in the step);
-    # back-to-back: the same launches queued without their producers (time_stage 2)
-    model.ctx.time_stage(7, 2)  # warm-up (without it the same tree read 7.0-8.1 us run to run)
-    gemv_ms = model.ctx.time_stage(7, 6)
-    gemv_b2b_ms = model.ctx.time_stage(2, 3)
-    kern = model.ctx.step_kernels(n_win, args.beam)  # what the library runs for this batch
-    p1 = kern["proj"] == "k_proj1"
-    fused_q = "<qproj" in kern["xattn"]  # the cross-q projected inside the cross-attention (round 6)
-    gemv_bytes = projection_bytes_per_launch(dims, rows, p1, fused_q=fused_q)
-    xattn_ms = model.ctx.time_stage(3, 3)
-    xattn_bytes = cross_attn_bytes_per_launch(dims, n_win, rows, fused_q=fused_q)
-    step_ms = model.ctx.time_stage(0, 20)
-    step_bytes = decoder_step_bytes(dims, n_win, args.beam, mean_ctx)
-
-    # single-window decoding (§8(d)'s p50: one _main_loop iteration at B = beam): one
-    # window, the whole 224-step fixed-work decode through decode_steps, per-token wall
-    # time of each 8-step chunk (graph launches + the host's done poll)
-    latency = None
-    if args.latency:
-        model.ctx.encode([0], [3000])
-        t1 = DecodingTask(model, whisper.DecodingOptions(language="en", beam_size=args.beam,
-                                                         suppress_tokens=f"-1,{task.tokenizer.eot}"))
-        model.ctx.decode_begin(t1.wh_opts(), [t1.initial_tokens], [t1.sot_index])
-        model.ctx.token_ms(reset=True)
-        model.ctx.decode_steps(t1.sample_len)
-        tk1 = model.ctx.token_ms(reset=True)
-        # the step graph alone, on a live window (after decode_steps the window is done and
-        # the selection / merge would return early): begin the batch again, then 20 replays
-        model.ctx.decode_begin(t1.wh_opts(), [t1.initial_tokens], [t1.sot_index])
-        step1 = model.ctx.time_stage(0, 20)
-        latency = {"p50_token_ms_1window": round(float(np.median(tk1)), 4), "step_graph_ms_1window": round(step1, 4),
-                   "step_bytes_1window": decoder_step_bytes(dims, 1, args.beam, mean_ctx),
-                   "roofline_frac_1window": round(decoder_step_bytes(dims, 1, args.beam, mean_ctx) /
-                                                  (step1 * 1e-3) / (HBM_PEAK_GBS * 1e9), 4)}
-
-    def gbs(b, ms):
-        return b / (ms * 1e-3) / 1e9
-
-    # the committed PMC pass (profiles/pmc_traffic.py) ran large-v3 at 20 windows (k_proj,
-    # k_xattn_seg) and at one window (k_proj1): other shapes report no traffic
-    lv3 = args.model == "large-v3"
-    traffic = load_traffic(kern["proj"]) if lv3 and (p1 or n_win == 20) else None
-    xattn_traffic = load_traffic(kern["xattn"].split("<")[0]) if lv3 and n_win == 20 else None
     parallel = parallelism_label(world, file_seconds, args.balance)
     out = {
         "metric": "xRT (audio-s/s) large-v3 beam=5 @1/2/4/8 GPU; p50 per-token decode ms",
@@ -535,39 +622,19 @@ def main():
                                f"30 s clip grid, condition_on_previous_text=False, temperature=0"
                                + (", word_timestamps=True" if args.word_timestamps else ""),
                    "model": args.model, "global_batch": n_clips, "seq_len": 448, "parallelism": parallel},
-        # §8(d): one _main_loop iteration at B = beam for a single window; the batch
-        # figures are the same per-token wall time with every window of the rank decoding
-        "p50_token_ms": latency["p50_token_ms_1window"] if latency else round(p50_token_ms, 4),
+        # §8(d): one _main_loop iteration at B = beam for a single window (--full with
+        # --latency replaces the entry with it); the batch figures are the same per-token
+        # wall time with every window of the rank decoding
+        "p50_token_ms": round(p50_token_ms, 4),
         "p50_token_ms_batch": round(p50_token_ms, 4),
         "mean_token_ms_batch": round(ms_per_token, 4),
         "tokens_per_window": round(seg_tokens / max(1, n_clips), 1) if rank == 0 else None,
         "encoder_ms_per_window": round(enc_ms / max(enc_windows, 1), 3),
         "encoder_tflops": round(encoder_flops(dims) * enc_windows / (enc_ms * 1e-3) / 1e12, 1) if enc_ms else None,
-        "roofline": {"bound": "hbm", "kernel": (f"k_proj1 whole-K projection, fused LayerNorm / epilogue ({rows} rows"
-                                                if p1 else f"k_proj split-K projection ({rows} rows")
-                                               + f", avg of the {'five' if fused_q else 'six'} per decoder layer)",
-                     "achieved": round(gbs(gemv_bytes, gemv_ms), 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(gbs(gemv_bytes, gemv_ms) / HBM_PEAK_GBS, 4),
-                     "traffic": traffic, "bytes_per_launch": gemv_bytes, "ms_per_launch": round(gemv_ms, 5),
-                     "timing": "HIP events around each launch inside eager decoder steps",
-                     "launches_per_layer": 5 if fused_q else 6,
-                     "ms_per_launch_back_to_back": round(gemv_b2b_ms, 5),
-                     "back_to_back_note": "time_stage 2: the layer's projections queued without their "
-                                          "producers; on the k_proj1 path the non-deferred fc2 and the plain QKV "
-                                          "LayerNorm prologue (the step itself defers fc2's residual)"},
         "roofline_overall": overall,
-        "roofline_cross_attn": {"bound": "hbm", "kernel": f"{kern['xattn']} ({n_win} windows x {args.beam} beams)",
-                                "achieved": round(gbs(xattn_bytes, xattn_ms), 1), "peak": HBM_PEAK_GBS,
-                                "frac": round(gbs(xattn_bytes, xattn_ms) / HBM_PEAK_GBS, 4),
-                                "traffic": xattn_traffic,
-                                "bytes_per_launch": xattn_bytes, "ms_per_launch": round(xattn_ms, 5)},
-        "roofline_step": {"bound": "hbm", "kernel": f"decoder step hipGraph ({n_win} windows x {args.beam} beams)",
-                          "achieved": round(gbs(step_bytes, step_ms), 1), "peak": HBM_PEAK_GBS,
-                          "frac": round(gbs(step_bytes, step_ms) / HBM_PEAK_GBS, 4),
-                          "bytes_per_launch": step_bytes, "ms_per_launch": round(step_ms, 4)},
     }
-    if latency:
-        out["latency_1window"] = latency
+    if args.full:
+        out.update(full_measurements(args, model, dims, n_win, mean_ctx))
     if world > 1:
         # per rank over the timed steps: wall time, windows and segment tokens decoded, and
         # the seconds spent in the two collectives (all-reduce MAX, segment gather)

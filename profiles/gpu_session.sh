@@ -4,8 +4,8 @@
 # steps (each under its own time limit; the first failure ends the session):
 #   tests      python -m pytest tests -m gpu (thread timeouts, one process)
 #   smoke      __graft_entry__.smoke()
-#   cfg3       bench.py default (config 3, with the CPU baseline)
-#   cfg3q      bench.py default without the CPU baseline
+#   cfg3       bench.py --full (config 3, with the CPU baseline)
+#   cfg3q      bench.py --full without the CPU baseline
 #   cfg2       turbo, one 30 s window
 #   cfg5       word timestamps
 #   cfg4       one 3600 s file through the sharded path, --verify 1 (N = 1)
@@ -33,20 +33,20 @@ for step in "$@"; do
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_${tag}.txt 2>&1 || exit 3
       cat $O/smoke_${tag}.txt ;;
     cfg3)
-      timeout -k 10 500 python3 bench.py > $O/cfg3_${tag}.json 2> $O/cfg3_${tag}.err || exit 4
+      timeout -k 10 500 python3 bench.py --full > $O/cfg3_${tag}.json 2> $O/cfg3_${tag}.err || exit 4
       cat $O/cfg3_${tag}.json ;;
     cfg3q)
-      timeout -k 10 300 python3 bench.py --cpu-baseline 0 > $O/cfg3q_${tag}.json 2> $O/cfg3q_${tag}.err || exit 4
+      timeout -k 10 300 python3 bench.py --full --cpu-baseline 0 > $O/cfg3q_${tag}.json 2> $O/cfg3q_${tag}.err || exit 4
       cat $O/cfg3q_${tag}.json ;;
     cfg2)
-      timeout -k 10 300 python3 bench.py --model turbo --seconds 30 --max-windows 1 --cpu-baseline 0 \
+      timeout -k 10 300 python3 bench.py --full --model turbo --seconds 30 --max-windows 1 --cpu-baseline 0 \
         > $O/cfg2_${tag}.json 2> $O/cfg2_${tag}.err || exit 5
       cat $O/cfg2_${tag}.json ;;
     cfg5)
-      timeout -k 10 400 python3 bench.py --word-timestamps 1 --cpu-baseline 0 > $O/cfg5_${tag}.json 2> $O/cfg5_${tag}.err || exit 6
+      timeout -k 10 400 python3 bench.py --full --word-timestamps 1 --cpu-baseline 0 > $O/cfg5_${tag}.json 2> $O/cfg5_${tag}.err || exit 6
       cat $O/cfg5_${tag}.json ;;
     cfg4)
-      timeout -k 10 500 python3 bench.py --sharded-file 1 --seconds 3600 --verify 1 --cpu-baseline 0 --steps 1 \
+      timeout -k 10 500 python3 bench.py --full --sharded-file 1 --seconds 3600 --verify 1 --cpu-baseline 0 --steps 1 \
         > $O/cfg4_${tag}.json 2> $O/cfg4_${tag}.err || exit 7
       cat $O/cfg4_${tag}.json ;;
     profeager)
