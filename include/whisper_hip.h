@@ -100,6 +100,20 @@ int wh_log_mel_frames(wh_ctx* ctx, const float* audio, int64_t n_samples, int64_
 int wh_audio_upload(wh_ctx* ctx, const float* audio, int64_t n_samples);
 int wh_mel_max(wh_ctx* ctx, float* gmax);              /* raw log10 max of the last wh_log_mel */
 int wh_mel_normalize(wh_ctx* ctx, float gmax);         /* floor at gmax-8, (x+4)/4 */
+/* log-mel of n_files waveforms, concatenated in `audio` (file i has n_samples[i] floats),
+   each padded, reflect-framed, floored at ITS OWN max-8 and scaled exactly as wh_log_mel
+   does for that file alone.  The files' frames lie back to back in the context mel:
+   file i owns absolute frames [frame_base[i], frame_base[i+1]), frame_base[0] = 0,
+   frame_base[i+1]-frame_base[i] = (n_samples[i]+padding)/160.  wh_encode / wh_mel_read
+   then take absolute frames as before.  One upload, one descriptor copy, a constant
+   number of launches and one synchronisation, whatever n_files is.  The call takes over
+   the resident-audio buffer: a later wh_log_mel(ctx, NULL, n, ...) fails until
+   wh_audio_upload is called again.  n_files < 1, a file with n_samples < 1 or
+   n_samples + padding <= 200, and unset filters are refused before anything is launched;
+   wh_last_error names the file's index. */
+int wh_log_mel_batch(wh_ctx* ctx, const float* audio, int n_files, const int64_t* n_samples, int64_t padding,
+                     int n_mels, int64_t* frame_base /* [n_files+1] */);
+int wh_mel_max_batch(wh_ctx* ctx, float* gmax, int n_files); /* raw log10 max per file of the last wh_log_mel_batch */
 int wh_mel_read(wh_ctx* ctx, float* out, int64_t frame0, int64_t n_frames); /* [n_mels][n_frames], absolute frames */
 int wh_mel_write(wh_ctx* ctx, const float* mel, int64_t n_frames);          /* host mel -> context */
 

@@ -119,6 +119,15 @@ void launch_mel(const float* audio, int64_t n_real, int64_t n_padded, int64_t fr
                 const float* filters, int n_mels, float* mel, int64_t ld, unsigned* gmax, hipStream_t st);
 void launch_mel_norm(float* mel, int64_t count, int64_t ld, int n_mels, const unsigned* gmax, const float* ovr,
                      hipStream_t st);
+// one file of a wh_log_mel_batch call: its samples start at audio_off of the concatenated
+// audio, its frames at column frame_base of the mel, its frame blocks at block_base
+struct MelFile {
+  int64_t audio_off, n_real, n_padded, nframes, frame_base, block_base;
+};
+int mel_blocks(int64_t nframes);  // frame blocks one file takes (whole blocks)
+// segmented log-mel of every file, raw values then each file's own max-8 floor and scaling
+void launch_mel_seg(const float* audio, const MelFile* files, int n_files, int64_t n_blocks, const float* filters,
+                    int n_mels, float* mel, int64_t ld, unsigned* gmax, hipStream_t st);
 
 // ------------------------------------------------------------ decode state (device)
 // Per window slot w (capacity nw) with G rows (beams / samples) each.

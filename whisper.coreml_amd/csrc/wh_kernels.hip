@@ -2724,14 +2724,16 @@ void launch_zero_rows(T* buf, int64_t ws, int n, int ra, int rb, int nwin, hipSt
 // is accumulated with an ordered-uint atomicMax; k_mel_norm applies max(x, gmax-8)
 // and (x+4)/4.  16 frames per block.
 constexpr int MEL_FB = 16;
-__global__ __launch_bounds__(256) void k_mel_frames(const float* __restrict__ audio, int64_t n_real, int64_t n_audio, int64_t nframes,
-                                                    int64_t frame0, const float* __restrict__ filters, int n_mels,
-                                                    float* __restrict__ mel, int64_t ld_mel, unsigned* gmax) {
+// MEL_FB frames [f0, f0 + MEL_FB) of one file (frames >= nframes are skipped); frame f is
+// stored at column f + col_off of mel; the block's max goes into *gmax.  Shared by the
+// single-file kernel and the segmented one, so both do the same fp32 arithmetic per frame.
+__device__ __forceinline__ void mel_frame_block(const float* __restrict__ audio, int64_t n_real, int64_t n_audio, int64_t nframes,
+                                                int64_t f0, const float* __restrict__ filters, int n_mels,
+                                                float* __restrict__ mel, int64_t ld_mel, int64_t col_off, unsigned* gmax) {
   __shared__ float xs[MEL_FB][400];
   __shared__ float cs[400], sn[400];
   __shared__ float pw[MEL_FB][201];
   const int tid = threadIdx.x;
-  const int64_t f0 = frame0 + (int64_t)blockIdx.x * MEL_FB;
   for (int i = tid; i < 400; i += 256) {
     float s, c;
     sincospif((float)i / 200.0f, &s, &c);  // angle 2*pi*i/400
@@ -2780,11 +2782,58 @@ __global__ __launch_bounds__(256) void k_mel_frames(const float* __restrict__ au
     float s = 0.f;
     for (int k = 0; k < 201; ++k) s += fr[k] * pw[fi][k];
     const float lv = log10f(fmaxf(s, 1e-10f));
-    mel[(int64_t)m * ld_mel + (f - frame0)] = lv;
+    mel[(int64_t)m * ld_mel + (f + col_off)] = lv;
     lmax = fmaxf(lmax, lv);
   }
   lmax = wave_max(lmax);
   if ((tid & 63) == 0) atomicMax(gmax, f2ord(lmax));
+}
+
+__global__ __launch_bounds__(256) void k_mel_frames(const float* __restrict__ audio, int64_t n_real, int64_t n_audio, int64_t nframes,
+                                                    int64_t frame0, const float* __restrict__ filters, int n_mels,
+                                                    float* __restrict__ mel, int64_t ld_mel, unsigned* gmax) {
+  mel_frame_block(audio, n_real, n_audio, nframes, frame0 + (int64_t)blockIdx.x * MEL_FB, filters, n_mels, mel, ld_mel,
+                  -frame0, gmax);
+}
+
+// Segmented form (wh_log_mel_batch): one launch over the frame blocks of every file.  A
+// block belongs to one file (each file's frames round up to whole blocks); it finds the
+// file by bisecting the per-file block prefixes, reflects inside that file's samples only
+// and feeds that file's slot of gmax.
+__device__ __forceinline__ int mel_file_of_block(const MelFile* __restrict__ files, int n_files, int64_t b) {
+  int lo = 0, hi = n_files - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (files[mid].block_base <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void k_mel_frames_seg(const float* __restrict__ audio, const MelFile* __restrict__ files,
+                                                        int n_files, const float* __restrict__ filters, int n_mels,
+                                                        float* __restrict__ mel, int64_t ld_mel, unsigned* gmax) {
+  const int fidx = mel_file_of_block(files, n_files, blockIdx.x);
+  const MelFile F = files[fidx];
+  mel_frame_block(audio + F.audio_off, F.n_real, F.n_padded, F.nframes, ((int64_t)blockIdx.x - F.block_base) * MEL_FB,
+                  filters, n_mels, mel, ld_mel, F.frame_base, gmax + fidx);
+}
+
+// every element is floored against its own file's max; same arithmetic as k_mel_norm
+__global__ __launch_bounds__(256) void k_mel_norm_seg(float* mel, int64_t ld_mel, int n_mels, const MelFile* __restrict__ files,
+                                                      int n_files, const unsigned* __restrict__ gmax) {
+  const int fidx = mel_file_of_block(files, n_files, blockIdx.x);
+  const MelFile F = files[fidx];
+  const float mx = ord2f(gmax[fidx]);
+  const float floor_v = mx - 8.0f;
+  const int64_t f0 = ((int64_t)blockIdx.x - F.block_base) * MEL_FB;
+  for (int i = threadIdx.x; i < MEL_FB * n_mels; i += 256) {
+    const int m = i / MEL_FB, fi = i - m * MEL_FB;
+    const int64_t f = f0 + fi;
+    if (f >= F.nframes) continue;
+    float* p = mel + (int64_t)m * ld_mel + F.frame_base + f;
+    *p = (fmaxf(*p, floor_v) + 4.0f) * 0.25f;
+  }
 }
 
 __global__ void k_mel_norm(float* mel, int64_t count_per_row, int64_t ld, int n_mels, const unsigned* gmax,
@@ -2809,6 +2858,13 @@ void launch_mel(const float* audio, int64_t n_real, int64_t n_padded, int64_t fr
 void launch_mel_norm(float* mel, int64_t count, int64_t ld, int n_mels, const unsigned* gmax, const float* ovr,
                      hipStream_t st) {
   k_mel_norm<<<1024, 256, 0, st>>>(mel, count, ld, n_mels, gmax, ovr), wh_launched("k_mel_norm");
+}
+int mel_blocks(int64_t nframes) { return (int)((nframes + MEL_FB - 1) / MEL_FB); }
+void launch_mel_seg(const float* audio, const MelFile* files, int n_files, int64_t n_blocks, const float* filters,
+                    int n_mels, float* mel, int64_t ld, unsigned* gmax, hipStream_t st) {
+  if (n_blocks <= 0) return;
+  k_mel_frames_seg<<<(unsigned)n_blocks, 256, 0, st>>>(audio, files, n_files, filters, n_mels, mel, ld, gmax), wh_launched("k_mel_frames_seg");
+  k_mel_norm_seg<<<(unsigned)n_blocks, 256, 0, st>>>(mel, ld, n_mels, files, n_files, gmax), wh_launched("k_mel_norm_seg");
 }
 
 // explicit instantiations

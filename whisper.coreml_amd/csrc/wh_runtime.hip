@@ -127,6 +127,9 @@ struct wh_ctx {
                              int normalize, int64_t* total_frames) = 0;
   virtual int audio_upload(const float* audio, int64_t n) = 0;
   virtual int mel_max(float* g) = 0;
+  virtual int log_mel_batch(const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
+                            int64_t* frame_base) = 0;
+  virtual int mel_max_batch(float* g, int n_files) = 0;
   virtual int mel_normalize(float g) = 0;
   virtual int mel_read(float* out, int64_t f0, int64_t nf) = 0;
   virtual int mel_write(const float* mel, int64_t nf) = 0;
@@ -197,6 +200,11 @@ struct Ctx : public wh_ctx {
   int mel_nm = 0;
   unsigned* d_gmax = nullptr;
   float* d_gmax_f = nullptr;
+  // wh_log_mel_batch: per-file descriptors and per-file ordered-uint maxima
+  MelFile* d_mel_files = nullptr;
+  unsigned* d_gmax_files = nullptr;
+  size_t mel_files_cap = 0;
+  int mel_batch_files = 0;  // files of the last wh_log_mel_batch (0: the mel is not from one)
   std::map<int, float*> d_filters;
 
   // encoder buffers
@@ -294,6 +302,8 @@ struct Ctx : public wh_ctx {
     if (d_mel) rel(hipFree(d_mel), "hipFree(mel)");
     for (auto& kv : d_filters) rel(hipFree(kv.second), "hipFree(mel filters)");
     if (d_gmax) rel(hipFree(d_gmax), "hipFree(mel max)");
+    if (d_mel_files) rel(hipFree(d_mel_files), "hipFree(mel files)");
+    if (d_gmax_files) rel(hipFree(d_gmax_files), "hipFree(mel file max)");
     if (scratch) rel(hipFree(scratch), "hipFree(scratch)");
     if (h_done) rel(hipHostFree(h_done), "hipHostFree(done flags)");
     for (auto& e : poll_ev)
@@ -671,7 +681,90 @@ struct Ctx : public wh_ctx {
     mel_frames = count;
     mel_f0 = frame0;
     mel_nm = n_mels;
+    mel_batch_files = 0;
     *total_frames = total;
+    return 0;
+  }
+  // log-mel of n_files waveforms (concatenated in `audio`) in one pass: one upload, one
+  // descriptor copy, the segmented frames + normalisation launches, one synchronisation.
+  // The files' frames lie back to back in d_mel (row stride = all frames of the call).
+  int log_mel_batch(const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
+                    int64_t* frame_base) override {
+    if (n_files < 1) return fail(-7, "log_mel_batch: n_files = " + std::to_string(n_files) + ", need at least one file");
+    if (!audio || !n_samples || !frame_base) return fail(-1, "null argument");
+    if (pad < 0) return fail(-7, "log_mel_batch: negative padding");
+    if (!h_filters.count(n_mels)) return fail(-7, "mel filters for n_mels=" + std::to_string(n_mels) + " not set");
+    std::vector<MelFile> files(n_files);
+    int64_t samples = 0, frames = 0, blocks = 0;
+    for (int i = 0; i < n_files; ++i) {
+      const int64_t n = n_samples[i];
+      if (n < 1) return fail(-7, "log_mel_batch: file " + std::to_string(i) + " has no samples");
+      if (n + pad <= 200) return fail(-7, "log_mel_batch: file " + std::to_string(i) + " too short for reflect padding");
+      MelFile& f = files[i];
+      f.audio_off = samples;
+      f.n_real = n;
+      f.n_padded = n + pad;
+      f.nframes = (n + pad) / 160;
+      f.frame_base = frames;
+      f.block_base = blocks;
+      samples += n;
+      frames += f.nframes;
+      blocks += mel_blocks(f.nframes);
+    }
+    if (blocks > 0x7fffffff) return fail(-7, "log_mel_batch: too many frames for one call");
+    if ((size_t)samples > audio_cap) {
+      if (d_audio) HIPCHK(hipFree(d_audio));
+      d_audio = nullptr;
+      audio_cap = std::max<size_t>(samples, 16000);
+      HIPCHK(hipMalloc(&d_audio, audio_cap * 4));
+    }
+    audio_n = -1;  // the buffer now holds several files: no resident audio of any length
+    const size_t need = (size_t)n_mels * frames;
+    if (need > mel_cap) {
+      if (d_mel) HIPCHK(hipFree(d_mel));
+      d_mel = nullptr;
+      mel_cap = need;
+      HIPCHK(hipMalloc(&d_mel, mel_cap * 4));
+    }
+    if ((size_t)n_files > mel_files_cap) {
+      if (d_mel_files) HIPCHK(hipFree(d_mel_files));
+      if (d_gmax_files) HIPCHK(hipFree(d_gmax_files));
+      d_mel_files = nullptr;
+      d_gmax_files = nullptr;
+      mel_files_cap = std::max<size_t>(n_files, 64);
+      HIPCHK(hipMalloc(&d_mel_files, mel_files_cap * sizeof(MelFile)));
+      HIPCHK(hipMalloc(&d_gmax_files, mel_files_cap * 4));
+    }
+    mel_batch_files = 0;
+    HIPCHK(hipEventRecord(tm.a, st));
+    HIPCHK(hipMemcpyAsync(d_audio, audio, (size_t)samples * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_mel_files, files.data(), n_files * sizeof(MelFile), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_gmax_files, 0, (size_t)n_files * 4, st));
+    launch_mel_seg(d_audio, d_mel_files, n_files, blocks, d_filters[n_mels], n_mels, d_mel, frames, d_gmax_files, st);
+    HIPCHK(hipEventRecord(tm.b, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, tm.a, tm.b));
+    stats[0] += ms;
+    mel_frames = frames;
+    mel_f0 = 0;
+    mel_nm = n_mels;
+    mel_batch_files = n_files;
+    for (int i = 0; i < n_files; ++i) frame_base[i] = files[i].frame_base;
+    frame_base[n_files] = frames;
+    return 0;
+  }
+  int mel_max_batch(float* g, int n_files) override {
+    if (!g) return fail(-1, "null argument");
+    if (n_files < 1 || n_files != mel_batch_files)
+      return fail(-7, "mel_max_batch: the context mel is of " + std::to_string(mel_batch_files) + " batch files, not " +
+                          std::to_string(n_files));
+    std::vector<unsigned> u(n_files);
+    HIPCHK(hipMemcpy(u.data(), d_gmax_files, (size_t)n_files * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n_files; ++i) {
+      const unsigned v = (u[i] & 0x80000000u) ? (u[i] & 0x7fffffffu) : ~u[i];
+      memcpy(g + i, &v, 4);
+    }
     return 0;
   }
   std::map<int, std::vector<float>> h_filters;
@@ -683,6 +776,7 @@ struct Ctx : public wh_ctx {
     return 0;
   }
   int mel_normalize(float g) override {
+    if (mel_batch_files) return fail(-7, "mel_normalize: the context mel is of a wh_log_mel_batch call, each file already normalised");
     HIPCHK(hipMemcpyAsync(d_gmax_f, &g, 4, hipMemcpyHostToDevice, st));
     launch_mel_norm(d_mel, mel_frames, mel_frames, mel_nm, d_gmax, d_gmax_f, st);
     HIPCHK(hipStreamSynchronize(st));
@@ -706,6 +800,7 @@ struct Ctx : public wh_ctx {
     mel_frames = nf;
     mel_f0 = 0;
     mel_nm = nm;
+    mel_batch_files = 0;
     return 0;
   }
 
@@ -2162,6 +2257,11 @@ int wh_audio_upload(wh_ctx* ctx, const float* audio, int64_t n) {
   CTXCALL(ctx->audio_upload(audio, n));
 }
 int wh_mel_max(wh_ctx* ctx, float* g) { CTXCALL(ctx->mel_max(g)); }
+int wh_log_mel_batch(wh_ctx* ctx, const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
+                     int64_t* frame_base) {
+  CTXCALL(ctx->log_mel_batch(audio, n_files, n_samples, pad, n_mels, frame_base));
+}
+int wh_mel_max_batch(wh_ctx* ctx, float* g, int n_files) { CTXCALL(ctx->mel_max_batch(g, n_files)); }
 int wh_mel_normalize(wh_ctx* ctx, float g) { CTXCALL(ctx->mel_normalize(g)); }
 int wh_mel_read(wh_ctx* ctx, float* out, int64_t f0, int64_t nf) { CTXCALL(ctx->mel_read(out, f0, nf)); }
 int wh_mel_write(wh_ctx* ctx, const float* mel, int64_t nf) { CTXCALL(ctx->mel_write(mel, nf)); }

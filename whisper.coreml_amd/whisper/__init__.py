@@ -25,6 +25,7 @@ from .decoding import DecodingOptions, DecodingResult, decode, detect_language
 from .model import ModelDimensions, Whisper
 from .synthetic import MODEL_DIMS, synthetic_state_dict
 from .transcribe import transcribe
+from .multifile import transcribe_batch
 
 __version__ = "20240930+hip1"
 
@@ -111,6 +112,6 @@ def load_model(name: str, device: Optional[Union[str, int]] = None, download_roo
     return model
 
 
-__all__ = ["available_models", "load_model", "transcribe", "decode", "detect_language", "DecodingOptions",
+__all__ = ["available_models", "load_model", "transcribe", "transcribe_batch", "decode", "detect_language", "DecodingOptions",
            "DecodingResult", "log_mel_spectrogram", "pad_or_trim", "load_audio", "ModelDimensions", "Whisper",
            "HipBackendError"]

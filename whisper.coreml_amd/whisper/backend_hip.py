@@ -56,6 +56,8 @@ _EXPORTS = {
     "wh_audio_upload": (c_int, [c_void_p, c_void_p, c_int64]),
     "wh_mel_max": (c_int, [c_void_p, POINTER(c_float)]),
     "wh_mel_normalize": (c_int, [c_void_p, c_float]),
+    "wh_log_mel_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "wh_mel_max_batch": (c_int, [c_void_p, c_void_p, c_int]),
     "wh_mel_read": (c_int, [c_void_p, c_void_p, c_int64, c_int64]),
     "wh_mel_write": (c_int, [c_void_p, c_void_p, c_int64]),
     "wh_encode": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
@@ -249,6 +251,25 @@ class HipContext:
         g = c_float()
         self._check(self.lib.wh_mel_max(self.h, ctypes.byref(g)), "wh_mel_max")
         return g.value
+
+    def log_mel_batch(self, audios: Sequence[np.ndarray], n_mels: int, padding: int = 0) -> np.ndarray:
+        """Log-mel of several files in one device pass, each normalised with its own max
+        exactly as ``log_mel`` does for it alone.  Returns the frame bases (int64,
+        ``len(audios) + 1``): file i owns absolute frames [base[i], base[i+1]) of the
+        context mel, which ``encode`` / ``mel_read`` address as before."""
+        arrs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in audios]
+        n = np.asarray([a.shape[0] for a in arrs], dtype=np.int64)
+        cat = np.concatenate(arrs) if arrs and n.sum() > 0 else np.zeros(1, dtype=np.float32)
+        base = np.zeros(len(arrs) + 1, dtype=np.int64)
+        self._check(self.lib.wh_log_mel_batch(self.h, _ptr(cat), len(arrs), _ptr(n) if len(arrs) else None,
+                                              int(padding), n_mels, _ptr(base)), "wh_log_mel_batch")
+        return base
+
+    def mel_max_batch(self, n_files: int) -> np.ndarray:
+        """Raw log10 max of each file of the last ``log_mel_batch``."""
+        g = np.empty(max(int(n_files), 1), dtype=np.float32)
+        self._check(self.lib.wh_mel_max_batch(self.h, _ptr(g), int(n_files)), "wh_mel_max_batch")
+        return g[:n_files]
 
     def mel_normalize(self, gmax: float):
         self._check(self.lib.wh_mel_normalize(self.h, float(gmax)), "wh_mel_normalize")

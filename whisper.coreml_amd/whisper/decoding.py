@@ -29,6 +29,11 @@ if TYPE_CHECKING:
 _seed_counter = itertools.count(1)
 
 
+def next_seed() -> int:
+    """The process counter's next sampling seed (what a T > 0 decode draws by default)."""
+    return next(_seed_counter) * 0x9E3779B97F4A7C15 % (1 << 64)
+
+
 def compression_ratio(text: str) -> float:
     """utils.py:45-47."""
     b = text.encode("utf-8")
@@ -132,7 +137,7 @@ class DecodingTask:
         s += [t.transcribe, t.translate, t.sot, t.sot_prev, t.sot_lm, t.no_speech]
         return sorted(set(s))
 
-    def wh_opts(self) -> WhDecodeOpts:
+    def wh_opts(self, seed: Optional[int] = None) -> WhDecodeOpts:
         o, t = self.options, self.tokenizer
         w = WhDecodeOpts()
         w.group = self.n_group
@@ -160,7 +165,10 @@ class DecodingTask:
         w.suppress = self._sup.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
         w.n_suppress = len(sup)
         # the seed is part of the captured step graph: keep it constant for T = 0
-        w.seed = (next(_seed_counter) * 0x9E3779B97F4A7C15 % (1 << 64)) if w.temperature > 0 else 0
+        if w.temperature > 0:
+            w.seed = next_seed() if seed is None else seed % (1 << 64)
+        else:
+            w.seed = 0
         return w
 
     def finalize(self, raw: dict) -> Tuple[List[int], float, float]:
@@ -190,20 +198,30 @@ class DecodingTask:
 
 
 def run_windows(model: "Whisper", options: DecodingOptions, prompts: Sequence[Optional[List[int]]],
-                audio_features: bool = False, slots: Optional[Sequence[int]] = None) -> List[DecodingResult]:
+                audio_features: bool = False, slots: Optional[Sequence[int]] = None,
+                languages: Optional[Sequence[Optional[str]]] = None, seed: Optional[int] = None
+                ) -> List[DecodingResult]:
     """Decode windows already encoded into the model's context: window i uses encoder
-    slot ``slots[i]`` (default i), all with ``options`` except the per-window prompt."""
-    tasks = [DecodingTask(model, replace(options, prompt=p)) for p in prompts]
+    slot ``slots[i]`` (default i), all with ``options`` except the per-window prompt
+    and, with ``languages``, the per-window language (windows of different files; the
+    device options do not depend on the language, only the initial tokens do).
+    ``seed``: the sampling seed of this call (T > 0); default the process counter's next."""
+    if languages is None:
+        tasks = [DecodingTask(model, replace(options, prompt=p)) for p in prompts]
+    else:
+        if len(languages) != len(prompts):
+            raise ValueError("run_windows: one language per window")
+        tasks = [DecodingTask(model, replace(options, prompt=p, language=lg)) for p, lg in zip(prompts, languages)]
     t0 = tasks[0]
-    opts = t0.wh_opts()
+    opts = t0.wh_opts(seed)
     ctx = model.ctx
     ctx.decode_begin(opts, [t.initial_tokens for t in tasks], [t.sot_index for t in tasks], slots=slots)
     # every window stops on the device (completion, n_ctx or sample_len updates);
     # decode_steps returns once all of them are done
     ctx.decode_steps(t0.sample_len)
     out = []
-    lang = t0.tokenizer.language or "en"
     for i, t in enumerate(tasks):
+        lang = t.tokenizer.language or "en"
         raw = ctx.decode_read(i, t.n_group)
         toks, _, avg = t.finalize(raw)
         text = t.tokenizer.decode(toks).strip()
@@ -242,6 +260,18 @@ def decode(model: "Whisper", mel, options: DecodingOptions = DecodingOptions(), 
     return res[0] if single else res
 
 
+def language_probs(model: "Whisper", slot: int, tokenizer: Tokenizer):
+    """(language token, {code: probability}) of the window encoded in ``slot``: one
+    decoder pass over <|startoftranscript|>, softmax over the language tokens."""
+    lang_tokens = np.asarray(tokenizer.all_language_tokens)
+    logits, _ = model.ctx.prefill_logits(slot, [tokenizer.sot])
+    row = logits[0].astype(np.float64)
+    sel = row[lang_tokens]
+    p = np.exp(sel - sel.max())
+    p /= p.sum()
+    return int(lang_tokens[int(np.argmax(sel))]), {c: float(pp) for c, pp in zip(tokenizer.all_language_codes, p)}
+
+
 def detect_language(model: "Whisper", mel, tokenizer: Optional[Tokenizer] = None):
     """Language id as upstream whisper does it (the fork's version is broken,
     decoding.py:58 calls the removed Whisper.logits): one decoder pass over
@@ -254,19 +284,13 @@ def detect_language(model: "Whisper", mel, tokenizer: Optional[Tokenizer] = None
         tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages)
     if tokenizer.language is None or tokenizer.language_token not in tokenizer.sot_sequence:
         raise ValueError("This model doesn't have language tokens so it can't perform lang id")
-    lang_tokens = np.asarray(tokenizer.all_language_tokens)
-    codes = tokenizer.all_language_codes
     out_tokens, out_probs = [], []
     for m in mel:
         model.ctx.mel_write(m)
         model.ctx.encode([0], [N_FRAMES])
-        logits, _ = model.ctx.prefill_logits(0, [tokenizer.sot])
-        row = logits[0].astype(np.float64)
-        sel = row[lang_tokens]
-        p = np.exp(sel - sel.max())
-        p /= p.sum()
-        out_tokens.append(int(lang_tokens[int(np.argmax(sel))]))
-        out_probs.append({c: float(pp) for c, pp in zip(codes, p)})
+        tok, probs = language_probs(model, 0, tokenizer)
+        out_tokens.append(tok)
+        out_probs.append(probs)
     if single:
         return out_tokens[0], out_probs[0]
     return out_tokens, out_probs

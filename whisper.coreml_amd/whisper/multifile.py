@@ -1,0 +1,256 @@
+"""transcribe_batch: many files decoded together, one lane per file.
+
+Inside a file every window depends on the previous one (seek, prompt carry-over, the
+running last-speech time), so ``transcribe()`` with the default options walks it one
+window at a time.  Different files are independent whatever the options are: here
+each file is a lane (``transcribe._Lane``, the reference loop's state for one file)
+and every round encodes and decodes the next window of all live lanes together —
+the batched encoder, the batched step graph and ``find_alignment_batch``.
+
+Files are taken in groups whose log-mel fits ``mel_budget_frames``; one
+``log_mel_batch`` call computes a group's mel (each file normalised with its own
+max), the files' frames lying back to back in the context mel.  At most
+``ctx.max_windows`` lanes are live; a lane that ends hands its slot to the next
+pending file of the group.  ``run_files`` is the scheduler alone, with the GPU work
+behind callables, so it can be driven without a device.
+"""
+
+from typing import TYPE_CHECKING, Callable, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from .audio import HOP_LENGTH, N_FRAMES, N_SAMPLES, load_audio
+from .backend_hip import DeviceAudio
+from .decoding import DecodingResult, language_probs, next_seed
+from .timing import find_alignment_batch
+from .tokenizer import LANGUAGES, get_tokenizer
+from .transcribe import _Lane, _check_fp16, _decode_with_fallback, _plan_file
+
+if TYPE_CHECKING:
+    from .model import Whisper
+
+# frames of log-mel one group may hold.  A frame is n_mels floats: at 128 mels this is
+# 2 GiB of mel (plus 2.4 GiB of concatenated audio), about 11 hours of audio per group.
+DEFAULT_MEL_BUDGET_FRAMES = 4_000_000
+
+Window = Tuple["_Lane", int, int, Optional[List[int]]]  # (lane, absolute frame, segment size, prompt)
+
+
+def file_frames(n_samples: int) -> int:
+    """Frames of one file's log-mel with the 30 s padding transcribe() uses."""
+    return (int(n_samples) + N_SAMPLES) // HOP_LENGTH
+
+
+def split_groups(frames: Sequence[int], mel_budget_frames: int) -> List[List[int]]:
+    """Consecutive files whose frames fit the budget; a file larger than the budget is a
+    group of its own (it needs that much mel under transcribe() as well)."""
+    groups: List[List[int]] = []
+    used = 0
+    for i, f in enumerate(frames):
+        if not groups or used + f > mel_budget_frames:
+            groups.append([])
+            used = 0
+        groups[-1].append(i)
+        used += f
+    return groups
+
+
+def run_lanes(lanes: Sequence["_Lane"], max_windows: int, decode_round: Callable[[List[Window]], List[DecodingResult]],
+              align_round: Optional[Callable[[List[Tuple[int, "_Lane", int]]], List[list]]] = None) -> None:
+    """Rounds over ``lanes`` (taken in the given order): every live lane offers its next
+    window, ``decode_round`` decodes them together (window i in slot i), each lane applies
+    its result; with ``align_round`` the windows that were not skipped are aligned together
+    ((slot, lane, segment size) each) before the lanes finish them.  At most ``max_windows``
+    lanes are live; a lane that ends frees its place for the next pending one."""
+    if max_windows < 1:
+        raise ValueError("max_windows must be at least 1")
+    pending = list(lanes)
+    live: List["_Lane"] = []
+    while True:
+        windows: List[Window] = []
+        still: List["_Lane"] = []
+        for lane in live:
+            w = lane.next_window()
+            if w is not None:
+                still.append(lane)
+                windows.append((lane, *w))
+        while len(still) < max_windows and pending:
+            lane = pending.pop(0)
+            w = lane.next_window()
+            if w is not None:  # None: nothing to decode (shorter than 1 s)
+                still.append(lane)
+                windows.append((lane, *w))
+        live = still
+        if not windows:
+            return
+        results = decode_round(windows)
+        if len(results) != len(windows):
+            raise RuntimeError("decode_round returned %d results for %d windows" % (len(results), len(windows)))
+        kept = [(slot, w[0], w[2]) for slot, (w, r) in enumerate(zip(windows, results)) if w[0].apply(r)]
+        aligns = align_round(kept) if align_round is not None else [None] * len(kept)
+        for (_, lane, _), alignment in zip(kept, aligns):
+            lane.finish(alignment)
+
+
+def run_files(n_samples: Sequence[int], *, max_windows: int, mel_budget_frames: int,
+              prepare_group: Callable[[List[int]], Sequence[int]],
+              make_lanes: Callable[[List[int], Sequence[int]], List["_Lane"]],
+              decode_round, align_round=None) -> List["_Lane"]:
+    """The scheduler: checks the lengths, splits the files into mel groups, and runs each
+    group's lanes longest-first.  ``prepare_group(indices)`` computes the group's mel and
+    returns the files' frame bases; ``make_lanes(indices, bases)`` builds their lanes
+    (language detection sits there).  Returns the finished lanes in input order."""
+    for i, n in enumerate(n_samples):
+        if int(n) < 1:
+            raise ValueError(f"audio {i} is empty")
+    if mel_budget_frames < 1:
+        raise ValueError("mel_budget_frames must be positive")
+    frames = [file_frames(n) for n in n_samples]
+    out: List[Optional["_Lane"]] = [None] * len(frames)
+    for group in split_groups(frames, mel_budget_frames):
+        bases = prepare_group(group)
+        lanes = make_lanes(group, bases)
+        for i, lane in zip(group, lanes):
+            out[i] = lane
+        order = sorted(range(len(group)), key=lambda k: -frames[group[k]])  # stable: ties keep input order
+        run_lanes([lanes[k] for k in order], max_windows, decode_round, align_round)
+    return out
+
+
+def _per_file(value, n: int, name: str, is_single) -> list:
+    """One value for all files, or a list with one per file."""
+    if is_single(value):
+        return [value] * n
+    value = list(value)
+    if len(value) != n:
+        raise ValueError(f"{name}: {len(value)} values for {n} files")
+    return value
+
+
+def _is_number(x) -> bool:
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+
+def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]], *,
+                     language: Union[None, str, Sequence[Optional[str]]] = None,
+                     mel_budget_frames: int = DEFAULT_MEL_BUDGET_FRAMES, verbose: Optional[bool] = None,
+                     temperature: Union[float, Tuple[float, ...]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
+                     compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+                     no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = True,
+                     initial_prompt=None, carry_initial_prompt: bool = False, word_timestamps: bool = False,
+                     prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
+                     clip_timestamps="0", hallucination_silence_threshold: Optional[float] = None,
+                     **decode_options) -> List[dict]:
+    """``[transcribe(model, a, **kwargs) for a in audios]`` with the files decoded
+    together: ``result[i]`` is what ``transcribe(model, audios[i], ...)`` returns.
+
+    ``audios``: paths and/or 1-D arrays.  ``language``: None (detected per file on a
+    multilingual model), one code, or one per file.  ``initial_prompt`` and
+    ``clip_timestamps``: one value for all files, or a list with one per file (a list of
+    ints is one token prompt, a list of numbers one clip list).  ``mel_budget_frames``
+    bounds the log-mel frames held on the device at a time.  The other keywords are
+    transcribe()'s."""
+    for k in ("schedule", "mel_max_reduce", "_mel_prepared"):
+        if k in decode_options:
+            raise TypeError(f"transcribe_batch() does not take {k!r}")
+    _check_fp16(model, decode_options.pop("fp16", True))
+    ctx = model.ctx
+    n_mels = model.dims.n_mels
+    if isinstance(audios, (str, np.ndarray, DeviceAudio)):
+        raise TypeError("audios must be a sequence of paths and/or 1-D arrays")
+    waves: List[np.ndarray] = []
+    for i, a in enumerate(audios):
+        if isinstance(a, DeviceAudio):
+            raise TypeError(f"audio {i}: DeviceAudio is one file resident in the context; pass paths or arrays")
+        if isinstance(a, str):
+            a = load_audio(a)
+        a = np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32)
+        if a.ndim != 1:
+            raise ValueError(f"audio {i} is not 1-D (shape {a.shape})")
+        waves.append(a)
+    n = len(waves)
+    languages = _per_file(language, n, "language", lambda v: v is None or isinstance(v, str))
+    prompts = _per_file(initial_prompt, n, "initial_prompt",
+                        lambda v: v is None or isinstance(v, str) or all(_is_number(x) for x in v))
+    clips = _per_file(clip_timestamps, n, "clip_timestamps",
+                      lambda v: isinstance(v, str) or all(_is_number(x) for x in v))
+    thresholds = (compression_ratio_threshold, logprob_threshold, no_speech_threshold)
+    probe = get_tokenizer(model.is_multilingual, num_languages=model.num_languages) if model.is_multilingual else None
+
+    def prepare_group(group: List[int]):
+        return ctx.log_mel_batch([waves[i] for i in group], n_mels, padding=N_SAMPLES)
+
+    def detect(group: List[int], bases) -> None:
+        """Language of every file of the group that has none: the first window of up to
+        max_windows files per encode, one <|startoftranscript|> pass per slot."""
+        todo = [k for k, i in enumerate(group) if languages[i] is None]
+        for c0 in range(0, len(todo), ctx.max_windows):
+            chunk = todo[c0:c0 + ctx.max_windows]
+            seeks = [int(bases[k]) for k in chunk]
+            sizes = [min(N_FRAMES, int(bases[k + 1] - bases[k])) for k in chunk]
+            ctx.encode(seeks, sizes)
+            model._last_windows = (seeks, sizes)
+            for slot, k in enumerate(chunk):
+                _, probs = language_probs(model, slot, probe)
+                languages[group[k]] = max(probs, key=probs.get)
+                if verbose is not None:
+                    print(f"[{group[k]}] Detected language: {LANGUAGES[languages[group[k]]].title()}")
+
+    plans = {}
+    # one sampling seed per file, drawn in input order as a loop of transcribe() calls draws them
+    file_seeds = [next_seed() for _ in range(n)]
+
+    def make_lanes(group: List[int], bases) -> List[_Lane]:
+        if not model.is_multilingual:
+            for i in group:
+                languages[i] = languages[i] or "en"
+        else:
+            detect(group, bases)
+        lanes = []
+        for k, i in enumerate(group):
+            content_frames = int(bases[k + 1] - bases[k]) - N_FRAMES
+            opts = dict(decode_options, language=languages[i])
+            plan = _plan_file(model, content_frames, languages[i], opts, temperature=temperature,
+                              thresholds=thresholds, initial_prompt=prompts[i], word_timestamps=word_timestamps,
+                              prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
+                              clip_timestamps=clips[i],
+                              hallucination_silence_threshold=hallucination_silence_threshold)
+            plans[i] = plan
+            tokenizer, seek_clips, prompt_tokens, st = plan
+            lanes.append(_Lane(model.dims.n_text_ctx, seek_clips, prompt_tokens, condition_on_previous_text,
+                               carry_initial_prompt, st, base=int(bases[k]), file_seed=file_seeds[i]))
+        return lanes
+
+    def decode_round(windows: List[Window]) -> List[DecodingResult]:
+        seeks = [w[1] for w in windows]
+        sizes = [w[2] for w in windows]
+        ctx.encode(seeks, sizes)
+        model._last_windows = (seeks, sizes)
+        st = windows[0][0].st  # the decoding options and thresholds are the same for every file
+        return _decode_with_fallback(model, st["base"], st["temperatures"], [w[3] for w in windows], st["thresholds"],
+                                     languages=[w[0].language for w in windows],
+                                     seed_keys=[(w[0].file_seed, w[0].window[0]) for w in windows])
+
+    def align_round(kept):
+        if not kept:
+            return []
+        toks = [lane.st["tokenizer"] for _, lane, _ in kept]
+        return find_alignment_batch(model, toks[0], [lane.text_tokens() for _, lane, _ in kept],
+                                    [size for _, _, size in kept], [slot for slot, _, _ in kept], tokenizers=toks)
+
+    lanes = run_files([w.shape[0] for w in waves], max_windows=ctx.max_windows, mel_budget_frames=mel_budget_frames,
+                      prepare_group=prepare_group, make_lanes=make_lanes, decode_round=decode_round,
+                      align_round=align_round if word_timestamps else None)
+    results = []
+    for i, lane in enumerate(lanes):
+        tokenizer, _, prompt_tokens, _ = plans[i]
+        all_tokens = list(prompt_tokens)
+        segments = []
+        for s in lane.segments:
+            segments.append({"id": len(segments), **s})
+            all_tokens.extend(s["tokens"])
+            if verbose:
+                print(f"[{i}] [{s['start']:.2f} --> {s['end']:.2f}] {s['text']}")
+        results.append(dict(text=tokenizer.decode(all_tokens[len(prompt_tokens):]), segments=segments,
+                            language=languages[i]))
+    return results

@@ -11,7 +11,7 @@ own outputs by tests/golden/micro_words.json.
 
 import itertools
 from dataclasses import dataclass
-from typing import TYPE_CHECKING, List
+from typing import TYPE_CHECKING, List, Optional
 
 import numpy as np
 
@@ -53,20 +53,26 @@ def find_alignment(model: "Whisper", tokenizer: Tokenizer, text_tokens: List[int
 
 def find_alignment_batch(model: "Whisper", tokenizer: Tokenizer, text_tokens: List[List[int]],
                          num_frames: List[int], slots: List[int], *, medfilt_width: int = 7,
-                         qk_scale: float = 1.0) -> List[List[WordTiming]]:
+                         qk_scale: float = 1.0, tokenizers: Optional[List[Tokenizer]] = None
+                         ) -> List[List[WordTiming]]:
     """find_alignment of several windows (slots) with one wh_align_batch call: their
-    first passes batched on the GPU, one DTW workgroup per window."""
+    first passes batched on the GPU, one DTW workgroup per window.  ``tokenizers``
+    (one per window, default ``tokenizer`` for all) serves windows of different
+    languages; their sot sequences have the same length."""
     if qk_scale != 1.0:
         raise NotImplementedError("qk_scale != 1.0 (the reference always passes 1.0)")
     out: List[List[WordTiming]] = [[] for _ in text_tokens]
     todo = [i for i, t in enumerate(text_tokens) if len(t) > 0]
     if not todo:
         return out
-    seqs = [[*tokenizer.sot_sequence, tokenizer.no_timestamps, *text_tokens[i], tokenizer.eot] for i in todo]
+    toks = list(tokenizers) if tokenizers is not None else [tokenizer] * len(text_tokens)
+    if any(len(t.sot_sequence) != len(tokenizer.sot_sequence) for t in toks):
+        raise ValueError("find_alignment_batch: tokenizers with sot sequences of different lengths")
+    seqs = [[*toks[i].sot_sequence, toks[i].no_timestamps, *text_tokens[i], toks[i].eot] for i in todo]
     res = model.ctx.align_batch([slots[i] for i in todo], seqs, len(tokenizer.sot_sequence),
                                 [num_frames[i] for i in todo], _alignment_head_ids(model), medfilt_width)
     for i, (probs, text_indices, time_indices) in zip(todo, res):
-        out[i] = _words_from_path(tokenizer, text_tokens[i], probs, text_indices, time_indices)
+        out[i] = _words_from_path(toks[i], text_tokens[i], probs, text_indices, time_indices)
     return out
 
 

@@ -18,6 +18,10 @@ empty-segment clearing).  Two schedules:
   ``last_speech_timestamp``; if that would move any window's seek (it can only
   through a one-word last segment) the file is re-run sequentially.
 
+The sequential loop's per-file state and body live in ``_Lane``; the sequential
+schedule drives one lane alone, ``multifile.transcribe_batch`` one lane per file with
+the next window of every unfinished file decoded together.
+
 The log-mel of the whole file is computed on the GPU and stays there; windows
 are cut from it on the device.
 """
@@ -31,7 +35,7 @@ import numpy as np
 
 from .audio import FRAMES_PER_SECOND, HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, load_audio
 from .backend_hip import DeviceAudio
-from .decoding import DecodingOptions, DecodingResult, detect_language, run_windows
+from .decoding import DecodingOptions, DecodingResult, detect_language, next_seed, run_windows
 from .timing import WordTiming, apply_alignment, find_alignment, find_alignment_batch
 from .tokenizer import LANGUAGES, get_tokenizer
 
@@ -39,16 +43,33 @@ if TYPE_CHECKING:
     from .model import Whisper
 
 
-def _decode_with_fallback(model, base_opts: DecodingOptions, temperatures, prompts: List, thresholds
-                          ) -> List[DecodingResult]:
+def _window_seed(file_seed: int, seek: int, temperature_index: int) -> int:
+    """Sampling seed of one window's decode at one fallback temperature: a function of
+    the file's seed and the window, not of the order in which windows are decoded, so a
+    file samples the same tokens whether its windows run alone or next to other files'."""
+    x = (file_seed ^ (seek * 0xBF58476D1CE4E5B9) ^ ((temperature_index + 1) * 0x94D049BB133111EB)) % (1 << 64)
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) % (1 << 64)
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) % (1 << 64)
+    return x ^ (x >> 31)
+
+
+def _decode_with_fallback(model, base_opts: DecodingOptions, temperatures, prompts: List, thresholds,
+                          languages: Optional[List[Optional[str]]] = None,
+                          seed_keys: Optional[List[Tuple[int, int]]] = None) -> List[DecodingResult]:
     """transcribe.py:188-228 for a batch of windows (slots 0..n-1 already encoded).
     A retry at the next temperature decodes only the windows that still need work,
-    from the encoder slots that already hold their audio features (no re-encode)."""
+    from the encoder slots that already hold their audio features (no re-encode).
+    ``languages``: one per window (windows of different files), default the options'.
+    ``seed_keys``: (file seed, seek) per window.  With them a retry at T > 0 decodes each
+    pending window in a call of its own, seeded by ``_window_seed``: the device sampler
+    keys its draws by the call's seed and the row in the call, so this is what makes a
+    window's samples independent of its neighbours in the round.  Without them the
+    pending windows share one call and the process counter's next seed."""
     cr_thr, lp_thr, ns_thr = thresholds
     n = len(prompts)
     results: List[Optional[DecodingResult]] = [None] * n
     pending = list(range(n))
-    for t in temperatures:
+    for ti, t in enumerate(temperatures):
         kw = {}
         if t > 0:
             kw = dict(beam_size=None, patience=None)
@@ -57,8 +78,18 @@ def _decode_with_fallback(model, base_opts: DecodingOptions, temperatures, promp
         opts = replace(base_opts, temperature=t, **kw)
         if t > 0 and opts.best_of is None:
             opts = replace(opts, best_of=None)
-        res = run_windows(model, opts, [prompts[i] for i in pending],
-                          slots=None if pending == list(range(n)) else pending)
+        calls = [pending]
+        if t > 0 and seed_keys is not None:
+            calls = [[i] for i in pending]
+        res = []
+        for call in calls:
+            extra = {}
+            if languages is not None:
+                extra["languages"] = [languages[i] for i in call]
+            if t > 0 and seed_keys is not None:
+                extra["seed"] = _window_seed(seed_keys[call[0]][0], seed_keys[call[0]][1], ti)
+            res += run_windows(model, opts, [prompts[i] for i in call],
+                               slots=None if call == list(range(n)) else call, **extra)
         nxt = []
         for i, r in zip(pending, res):
             results[i] = r
@@ -140,6 +171,44 @@ def _clear_empty(tokenizer, segs: List[dict]):
             s["words"] = []
 
 
+def _plan_file(model: "Whisper", content_frames: int, language: str, decode_options: dict, *, temperature,
+               thresholds, initial_prompt, word_timestamps, prepend_punctuations, append_punctuations,
+               clip_timestamps, hallucination_silence_threshold):
+    """What one file's loop needs besides its mel (transcribe.py:141-183, 230-254):
+    (tokenizer, clips, initial prompt tokens, state of the window loop)."""
+    task = decode_options.get("task", "transcribe")
+    tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=language,
+                              task=task)
+    content_duration = float(content_frames * HOP_LENGTH / SAMPLE_RATE)
+
+    if isinstance(clip_timestamps, str):
+        clip_timestamps = [float(ts) for ts in (clip_timestamps.split(",") if clip_timestamps else [])]
+    seek_points = [round(ts * FRAMES_PER_SECOND) for ts in clip_timestamps]
+    if len(seek_points) == 0:
+        seek_points.append(0)
+    if len(seek_points) % 2 == 1:
+        seek_points.append(content_frames)
+    seek_clips = list(zip(seek_points[::2], seek_points[1::2]))
+
+    temperatures = [temperature] if isinstance(temperature, (int, float)) else list(temperature)
+    base = DecodingOptions(**{k: v for k, v in decode_options.items() if k in DecodingOptions.__dataclass_fields__})
+    input_stride = N_FRAMES // model.dims.n_audio_ctx
+    time_precision = input_stride * HOP_LENGTH / SAMPLE_RATE
+
+    if isinstance(initial_prompt, str):  # transcribe.py:243-244
+        initial_prompt_tokens = tokenizer.encode(" " + initial_prompt.strip())
+    else:
+        initial_prompt_tokens = list(initial_prompt) if initial_prompt else []
+
+    if word_timestamps and task == "translate":
+        warnings.warn("Word-level timestamps on translations may not be reliable.")
+    state = dict(content_frames=content_frames, content_duration=content_duration, tokenizer=tokenizer,
+                 temperatures=temperatures, thresholds=thresholds, base=base, input_stride=input_stride,
+                 time_precision=time_precision, word_timestamps=word_timestamps, prepend=prepend_punctuations,
+                 append=append_punctuations, hallucination=hallucination_silence_threshold)
+    return tokenizer, seek_clips, initial_prompt_tokens, state
+
+
 def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Optional[bool] = None,
                temperature: Union[float, Tuple[float, ...]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
@@ -190,7 +259,6 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
 
     frames = prepare_mel()
     content_frames = frames - N_FRAMES
-    content_duration = float(content_frames * HOP_LENGTH / SAMPLE_RATE)
 
     if decode_options.get("language") is None:
         if not model.is_multilingual:
@@ -206,41 +274,18 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
             if verbose is not None:
                 print(f"Detected language: {LANGUAGES[decode_options['language']].title()}")
     language = decode_options["language"]
-    task = decode_options.get("task", "transcribe")
-    tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=language,
-                              task=task)
-
-    if isinstance(clip_timestamps, str):
-        clip_timestamps = [float(ts) for ts in (clip_timestamps.split(",") if clip_timestamps else [])]
-    seek_points = [round(ts * FRAMES_PER_SECOND) for ts in clip_timestamps]
-    if len(seek_points) == 0:
-        seek_points.append(0)
-    if len(seek_points) % 2 == 1:
-        seek_points.append(content_frames)
-    seek_clips = list(zip(seek_points[::2], seek_points[1::2]))
-
-    temperatures = [temperature] if isinstance(temperature, (int, float)) else list(temperature)
-    thresholds = (compression_ratio_threshold, logprob_threshold, no_speech_threshold)
-    base = DecodingOptions(**{k: v for k, v in decode_options.items() if k in DecodingOptions.__dataclass_fields__})
-    input_stride = N_FRAMES // model.dims.n_audio_ctx
-    time_precision = input_stride * HOP_LENGTH / SAMPLE_RATE
-
-    if isinstance(initial_prompt, str):  # transcribe.py:243-244
-        initial_prompt_tokens = tokenizer.encode(" " + initial_prompt.strip())
-    else:
-        initial_prompt_tokens = list(initial_prompt) if initial_prompt else []
-
-    if word_timestamps and task == "translate":
-        warnings.warn("Word-level timestamps on translations may not be reliable.")
+    plan = _plan_file(model, content_frames, language, decode_options, temperature=temperature,
+                      thresholds=(compression_ratio_threshold, logprob_threshold, no_speech_threshold),
+                      initial_prompt=initial_prompt, word_timestamps=word_timestamps,
+                      prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
+                      clip_timestamps=clip_timestamps,
+                      hallucination_silence_threshold=hallucination_silence_threshold)
+    tokenizer, seek_clips, initial_prompt_tokens, state = plan
     batched = schedule == "batched" or (
         schedule == "auto" and not condition_on_previous_text and not carry_initial_prompt
         and not initial_prompt_tokens and len(seek_clips) > 1)
     if hallucination_silence_threshold is not None and word_timestamps:
         batched = False  # its seek rules read the running last_speech_timestamp
-    state = dict(content_frames=content_frames, content_duration=content_duration, tokenizer=tokenizer,
-                 temperatures=temperatures, thresholds=thresholds, base=base, input_stride=input_stride,
-                 time_precision=time_precision, word_timestamps=word_timestamps, prepend=prepend_punctuations,
-                 append=append_punctuations, hallucination=hallucination_silence_threshold)
     segments = None
     if batched:
         segments = _run_batched(model, seek_clips, initial_prompt_tokens, state)
@@ -338,44 +383,85 @@ def _words_and_seek(st, segs, alignment, seek, previous_seek, segment_size, sing
     return seek
 
 
-def _run_sequential(model, clips, initial_prompt_tokens, condition_on_previous_text, carry_initial_prompt, st):
-    ctx = model.ctx
-    content_frames = st["content_frames"]
-    all_tokens = list(initial_prompt_tokens)
-    segments = []
-    prompt_reset_since = 0
-    remaining_prompt_length = model.dims.n_text_ctx // 2 - 1 - len(initial_prompt_tokens)
-    last_speech_timestamp = 0.0
-    clip_idx, seek = 0, clips[0][0]
-    while clip_idx < len(clips):
-        cs, ce = clips[clip_idx]
-        if seek < cs:
-            seek = cs
-        if seek >= ce:
-            clip_idx += 1
-            if clip_idx < len(clips):
-                seek = clips[clip_idx][0]
-            continue
-        segment_size, segment_duration = _window_at(seek, clips[clip_idx], content_frames)
-        if segment_duration < 1.0:  # fork: drop < 1 s tails (transcribe.py:292-297)
-            clip_idx += 1
-            continue
-        if carry_initial_prompt:
-            nignored = max(len(initial_prompt_tokens), prompt_reset_since)
-            prompt = initial_prompt_tokens + all_tokens[nignored:][-remaining_prompt_length:]
-        else:
-            prompt = all_tokens[prompt_reset_since:]
-        ctx.encode([seek], [segment_size])
-        model._last_windows = ([seek], [segment_size])
-        result = _decode_with_fallback(model, st["base"], st["temperatures"], [prompt or None], st["thresholds"])[0]
-        previous_seek = seek
-        segs, seek, skipped, single_end = _apply_result(model, result, seek, segment_size, st)
-        if skipped:
-            continue
+class _Lane:
+    """One file's running state of the reference loop (transcribe.py:256-515): clip
+    index, seek, the tokens so far with the prompt-reset mark, the last speech time.
+    The loop is cut where the GPU work sits: ``next_window`` offers the next window
+    and its prompt, ``apply`` takes the decoded result (no-speech skip, segment
+    split), ``finish`` takes the window's word alignment (word timings with the seek
+    refinement, hallucination-silence rules, empty-segment clearing, prompt reset).
+    ``_run_sequential`` drives one lane alone; ``transcribe_batch`` drives one lane
+    per file, many at a time.  Seeks are the file's own frames; ``base`` is where the
+    file's frames start in the context mel."""
+
+    def __init__(self, n_text_ctx: int, clips, initial_prompt_tokens, condition_on_previous_text: bool,
+                 carry_initial_prompt: bool, st: dict, base: int = 0, file_seed: int = 0):
+        self.st = st
+        self.base = base
+        self.file_seed = file_seed  # with the seek: the sampling seed of a window's T > 0 retries
+        self.clips = clips
+        self.initial_prompt_tokens = list(initial_prompt_tokens)
+        self.condition_on_previous_text = condition_on_previous_text
+        self.carry_initial_prompt = carry_initial_prompt
+        self.all_tokens = list(initial_prompt_tokens)
+        self.segments: List[dict] = []
+        self.prompt_reset_since = 0
+        self.remaining_prompt_length = n_text_ctx // 2 - 1 - len(self.initial_prompt_tokens)
+        self.last_speech_timestamp = 0.0
+        self.clip_idx, self.seek = 0, clips[0][0]
+        self.window: Optional[Tuple[int, int]] = None  # (seek, segment size) being decoded
+        self.language = st["tokenizer"].language
+
+    def next_window(self) -> Optional[Tuple[int, int, Optional[List[int]]]]:
+        """(absolute first frame, segment size, prompt) of the next window; None: done."""
+        clips = self.clips
+        while self.clip_idx < len(clips):
+            cs, ce = clips[self.clip_idx]
+            if self.seek < cs:
+                self.seek = cs
+            if self.seek >= ce:
+                self.clip_idx += 1
+                if self.clip_idx < len(clips):
+                    self.seek = clips[self.clip_idx][0]
+                continue
+            segment_size, segment_duration = _window_at(self.seek, clips[self.clip_idx], self.st["content_frames"])
+            if segment_duration < 1.0:  # fork: drop < 1 s tails (transcribe.py:292-297)
+                self.clip_idx += 1
+                continue
+            if self.carry_initial_prompt:
+                nignored = max(len(self.initial_prompt_tokens), self.prompt_reset_since)
+                prompt = self.initial_prompt_tokens + self.all_tokens[nignored:][-self.remaining_prompt_length:]
+            else:
+                prompt = self.all_tokens[self.prompt_reset_since:]
+            self.window = (self.seek, segment_size)
+            return self.base + self.seek, segment_size, prompt or None
+        self.window = None
+        return None
+
+    def apply(self, result: DecodingResult) -> bool:
+        """The decoded window: no-speech skip, segments, provisional seek.  False: the
+        window was skipped (nothing to align, ``finish`` is not called)."""
+        seek, segment_size = self.window
+        self.result = result
+        self.previous_seek = seek
+        self.segs, self.seek, skipped, self.single_end = _apply_result(None, result, seek, segment_size, self.st)
+        return not skipped
+
+    def text_tokens(self) -> List[int]:
+        """Text tokens of the applied window, the input of its word alignment."""
+        eot = self.st["tokenizer"].eot
+        return [t for s in self.segs for t in s["tokens"] if t < eot]
+
+    def finish(self, alignment=None):
+        """Second half of the loop body; ``alignment`` is the window's find_alignment
+        result (word timestamps only)."""
+        st, segs, result = self.st, self.segs, self.result
+        previous_seek, segment_size = self.window
+        seek, single_end = self.seek, self.single_end
+        content_frames = st["content_frames"]
         if st["word_timestamps"]:
-            alignment = _window_alignment(model, st, segs, segment_size, 0) if segs else []
             seek = _words_and_seek(st, segs, alignment, seek, previous_seek, segment_size, single_end,
-                                   last_speech_timestamp)
+                                   self.last_speech_timestamp)
             time_offset = float(previous_seek * HOP_LENGTH / SAMPLE_RATE)
             window_end_time = float((previous_seek + N_FRAMES) * HOP_LENGTH / SAMPLE_RATE)
             segment_duration = segment_size * HOP_LENGTH / SAMPLE_RATE
@@ -393,9 +479,9 @@ def _run_sequential(model, clips, initial_prompt_tokens, condition_on_previous_t
                 if first_segment is not None and _is_segment_anomaly(first_segment):
                     gap = first_segment["start"] - time_offset
                     if gap > threshold:
-                        seek = previous_seek + round(gap * FRAMES_PER_SECOND)
-                        continue
-                hal_last_end = last_speech_timestamp
+                        self.seek = previous_seek + round(gap * FRAMES_PER_SECOND)
+                        return
+                hal_last_end = self.last_speech_timestamp
                 for si in range(len(segs)):
                     segment = segs[si]
                     if not segment["words"]:
@@ -419,13 +505,36 @@ def _run_sequential(model, clips, initial_prompt_tokens, condition_on_previous_t
                     hal_last_end = segment["end"]
             last_word_end = get_end(segs)
             if last_word_end is not None:
-                last_speech_timestamp = last_word_end
+                self.last_speech_timestamp = last_word_end
+        self.seek = seek
         _clear_empty(st["tokenizer"], segs)
-        segments.extend(segs)
-        all_tokens.extend(t for s in segs for t in s["tokens"])
-        if not condition_on_previous_text or result.temperature > 0.5:
-            prompt_reset_since = len(all_tokens)
-    return segments
+        self.segments.extend(segs)
+        self.all_tokens.extend(t for s in segs for t in s["tokens"])
+        if not self.condition_on_previous_text or result.temperature > 0.5:
+            self.prompt_reset_since = len(self.all_tokens)
+
+
+def _run_sequential(model, clips, initial_prompt_tokens, condition_on_previous_text, carry_initial_prompt, st):
+    """The reference's order: one lane, one window at a time."""
+    ctx = model.ctx
+    lane = _Lane(model.dims.n_text_ctx, clips, initial_prompt_tokens, condition_on_previous_text,
+                 carry_initial_prompt, st, file_seed=next_seed())
+    while True:
+        window = lane.next_window()
+        if window is None:
+            break
+        seek, segment_size, prompt = window
+        ctx.encode([seek], [segment_size])
+        model._last_windows = ([seek], [segment_size])
+        result = _decode_with_fallback(model, st["base"], st["temperatures"], [prompt], st["thresholds"],
+                                       seed_keys=[(lane.file_seed, lane.window[0])])[0]
+        if not lane.apply(result):
+            continue
+        alignment = None
+        if st["word_timestamps"]:
+            alignment = _window_alignment(model, st, lane.segs, segment_size, 0) if lane.segs else []
+        lane.finish(alignment)
+    return lane.segments
 
 
 def _run_batched(model, clips, initial_prompt_tokens, st):
