@@ -3,9 +3,8 @@ decode loop on the same logits.
 
 The graph path (`whisper.decode` -> decode_steps, one window) runs k_vocab1 (the final
 LayerNorm + vocabulary projection: a workgroup's columns reduced over its 8 K-eighths in
-wave order), then k_logit_part with the window's candidate merge folded in (round 4);
-the tuning build's WHISPER_HIP_VOCAB_SEL=1 runs all three as one launch (k_vocab_sel),
-with the same vocabulary arithmetic.  The per-step ABI (wh_prefill / wh_step /
+wave order), then k_logit_part with the window's candidate merge folded in (round 4).
+The per-step ABI (wh_prefill / wh_step /
 wh_reorder_kv through HipInference) runs the same decoder layers and k_vocab1, so both
 paths see bit-identical logits every step; `oracle.ref_whisper.decode` applies the
 reference's filters, log-softmax and GreedyDecoder / BeamSearchDecoder updates to them

@@ -28,10 +28,14 @@ typedef float float8_t __attribute__((ext_vector_type(8)));
 #define WH_DEV __device__ __forceinline__
 #define WH_DEV_HOST __host__ __device__ __forceinline__
 
-// Tuning switches (WHISPER_HIP_* environment variables that select measured-but-not-
-// adopted kernel variants for A/B runs) are read only by the tuning build
-// (`make tune` -> lib/libwhisper_hip_tune.so, loaded with WHISPER_HIP_LIB).  The shipped
-// library ignores the environment: every variant it can run is the tested default.
+// Tuning switches (WHISPER_HIP_* environment variables) are read only by the tuning build
+// (`make tune` -> lib/libwhisper_hip_tune.so, loaded with WHISPER_HIP_LIB); the shipped
+// library ignores the environment.  A switch costs no kernel: it sets a numeric parameter
+// of a live kernel (GEMV_WGS, POLL_CHUNK, ENC_CHUNK, XS_K, SA_KCO_MIN, PROJ_FORCE), runs the
+// step without its graph (EAGER), or sends a shape down the path the shipped library takes
+// for another shape or dtype (SLAB16, SLAB16_QKV, P1, PROJ, VOCAB1, VOCAB_SMALL, ENC_KZ, XQ,
+// XQP, LOGIT_SPLIT).  Variants that lost their A/B are deleted, not switched off: DESIGN.md
+// "Removed variants" names the commit where each can be read.
 #ifndef WH_TUNING
 #define WH_TUNING 0
 #endif

@@ -6,14 +6,15 @@
 //   GreedyDecoder.update                                  (decoding.py:304-320)
 //   BeamSearchDecoder.update incl. finished bookkeeping   (decoding.py:350-409)
 //   PyTorchInference.rearrange_kv_cache                   (decoding.py:189-204) -> index indirection
-// k_logit_part + k_logit_combine (default): 8 or 32 vocabulary slices per row, one workgroup
-//               each, then one wave per row merging the kept slices.
+// k_logit_part (default): 8, 16 or 32 vocabulary slices per row, one workgroup each; the
+//               row's last slice to finish merges the kept slices, and the window's last
+//               row runs the candidate merge.
 // k_logit_rows: the single-workgroup form (one 1024-thread workgroup per decoder row;
 //               WHISPER_HIP_LOGIT_SPLIT=0).
-// k_merge     : one workgroup per window (candidate merge, history/ancestry update).
+// k_merge     : one workgroup per window (candidate merge, history/ancestry update) where
+//               the selection launch did not run it.
 #include <cstdlib>
 
-#include "wh_gemm.h"
 #include "wh_kernels.h"
 
 namespace wh {
@@ -316,9 +317,6 @@ struct MergeLds {
   int etok[MG_MAXG];  // each row's input token for the next step
   float csc[MG_MAXG * KC];
   int csrc[MG_MAXG * KC], ctok[MG_MAXG * KC], rk[MG_MAXG * KC];
-  // k_logit_part<..., WIN>: the window's row combines leave their candidates here ([G][KC])
-  float wcv[MG_MAXG * KC];
-  int wci[MG_MAXG * KC];
 };
 // the next step's input rows of window w (k_embed's arithmetic: x = E[tok] + P[pos] in
 // fp32, pos = min(length - 1, pmax)); newtok[b]: row b's token at pos (passed from
@@ -356,9 +354,7 @@ __device__ void merge_embed(const MergeEmbed& em, int w, int G, int pos, const i
   else merge_embed_rows<float, NT>(em, w, G, pos, newtok, tid);
 }
 
-// LDSC: the candidates are in L.wcv / L.wci (the window's row combines ran in this
-// workgroup, k_logit_part<..., WIN>): no global round trip for them
-template <int NT, bool SC1, bool LDSC = false>
+template <int NT, bool SC1>
 __device__ __forceinline__ void merge_window(const DecState& s, const DecOpts& o, const MergeEmbed& em, int w, int tid, MergeLds& L) {
   static_assert(NT >= MG_MAXG * KC, "one lane per candidate");
   CT_MARK(CT_MERGE, 0);
@@ -380,13 +376,11 @@ __device__ __forceinline__ void merge_window(const DecState& s, const DecOpts& o
   const auto rsv = wt_rsrc(s.cand_val), rsi = wt_rsrc(s.cand_idx);
   // candidate k of row b of the window
   auto cval = [&](int b, int k) -> float {
-    if constexpr (LDSC) return L.wcv[b * KC + k];
     const int i = (w * G + b) * KC + k;
     if constexpr (SC1) return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsv, i * 4, 0, 16));
     else return s.cand_val[i];
   };
   auto cidx = [&](int b, int k) -> int {
-    if constexpr (LDSC) return L.wci[b * KC + k];
     const int i = (w * G + b) * KC + k;
     if constexpr (SC1) return (int)__builtin_amdgcn_raw_buffer_load_b32(rsi, i * 4, 0, 16);
     else return s.cand_idx[i];
@@ -569,8 +563,8 @@ __device__ __forceinline__ void merge_window(const DecState& s, const DecOpts& o
 // ApplyTimestampRules tail (decoding.py:522-531: logsumexp over timestamps vs the text
 // maximum) and the masking of text it may decide are both per-slice facts the combine
 // selects between.  k_logit_part applies the filters in place and writes, per slice:
-// max, sum of exp(x - max), argbest, Gumbel best, top-(G+1); k_logit_combine (one wave
-// per row) merges the kept slices.  Same choices as k_logit_rows; the normaliser is
+// max, sum of exp(x - max), argbest, Gumbel best, top-(G+1); the row's last slice to finish
+// (one wave) merges the kept slices.  Same choices as k_logit_rows; the normaliser is
 // summed per slice (float rounding of the log-probabilities differs in the last bits).
 constexpr int LP_THREADS = 512;
 // WH_LP_OCC=1: cap k_logit_part at 80 VGPRs (6 waves per SIMD: 3 workgroups per CU);
@@ -635,8 +629,7 @@ __device__ __forceinline__ void wave_argbest(float& v, int& idx) {
 }
 
 template <int NS, bool WT>
-__device__ __forceinline__ void lp_combine(const LPRec* rec, int r, const DecState& s, const DecOpts& o, int lane,
-                                           float* cv_out = nullptr, int* ci_out = nullptr);
+__device__ __forceinline__ void lp_combine(const LPRec* rec, int r, const DecState& s, const DecOpts& o, int lane);
 
 // Two barriers per workgroup: (1) after the history scan (last sampled timestamp), (2)
 // after every wave has reduced its own max, rescaled sum of exp and top-(G+1) list (or
@@ -644,26 +637,16 @@ __device__ __forceinline__ void lp_combine(const LPRec* rec, int r, const DecSta
 // The slice's logits and suppress words are loaded first, before the history, so their
 // round trip overlaps it.
 //
-// MERGE (with FUSED): the candidates of the row combine are stored write-through and counted
+// MERGE: the candidates of the row combine are stored write-through and counted
 // on the window's counter (s.lpw_cnt); the combine completing the window tells its
 // workgroup, whose 8 waves then run the window's candidate merge (k_merge folded in:
 // merge_window<512, sc1 candidate loads>).  A finished window's rows are re-embedded by
 // its first row's first slice.
 //
-// WIN (with MERGE, round 6): the slices count on their WINDOW's counter (G x NS arrivals)
-// instead of their row's; the slice completing the window runs every row's combine in its
-// workgroup (wave b: row b's NS records, sc1 loads, then lp_combine into LDS) and the merge
-// reads those candidates from LDS — the row-level arrival, the candidates' write-through
-// stores, their drain and their sc1 reload leave the chain.  Same records, same combine
-// arithmetic, same merge: bit-identical selections.
-template <int NS, int LP_EPT, bool FUSED, bool MERGE = false, bool WIN = false>
+template <int NS, int LP_EPT, bool MERGE = false>
 __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __restrict__ logits, int ldl, DecState s,
                                                            DecOpts o, MergeEmbed em) {
   CT_MARK(CT_LOGIT, 0);
-  static_assert(FUSED || !MERGE, "the merge rides on the fused combine");
-  static_assert(!WIN || MERGE, "window arrival: the merge runs in this launch");
-  // (WIN: the launcher checks that G x NS records fit the merge's history / ancestry
-  // staging, which they alias: lp_win_fits)
   constexpr int NWV = LP_THREADS / 64;
   __shared__ __attribute__((aligned(16))) char mlds_raw[MERGE ? sizeof(MergeLds) : 4];
   MergeLds& mlds = *reinterpret_cast<MergeLds*>(mlds_raw);
@@ -770,11 +753,10 @@ __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __r
   const auto rrs = wt_rsrc(s.lpart + (int64_t)r * LP_SLICES * LP_REC);
   const int rec_off = j * LP_REC * 4;
   auto wt_rec = [&](int off, float v) { wt_store1(rrs, off, v); };
-  // FUSED: the row's last slice to finish merges all NS records (the k_logit_combine
-  // launch folded in; cdna_hip_programming.md §6 Guideline 16 R1, as k_xattn_seg): the
+  // the row's last slice to finish merges all NS records (no combine launch; cdna_hip_programming.md §6 Guideline 16 R1, as k_xattn_seg): the
   // record's sc1 stores drained (vmcnt(0)), a relaxed agent add on the row's counter; the
   // wave drawing NS - 1 re-arms it and reads the NS records with sc1 loads into LDS
-  __shared__ __attribute__((aligned(16))) float recs[FUSED ? NS * LP_REC : 4];
+  __shared__ __attribute__((aligned(16))) float recs[NS * LP_REC];
   // (wave 0) returns true when this combine completed the window (MERGE)
   auto arrive_and_combine = [&]() -> bool {
     CT_MARK(CT_LOGIT_SLICE, 2);
@@ -808,53 +790,14 @@ __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __r
     if (lane == 0) __hip_atomic_store(s.lpw_cnt + w, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return true;
   };
-  // WIN: the window's arrival (every slice of every row of window w); true for the last
-  auto arrive_window = [&]() -> bool {
-    CT_MARK(CT_LOGIT_SLICE, 2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int ticket = 0;
-    if (lane == 0) ticket = __hip_atomic_fetch_add(s.lpw_cnt + w, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ticket = __shfl(ticket, 0, 64);
-    CT_MARK(CT_LOGIT_SLICE, 3);
-    if (ticket != s.G * NS - 1) return false;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the loads below the add
-    if (lane == 0) __hip_atomic_store(s.lpw_cnt + w, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-  };
   // MERGE: wave 0 tells the workgroup whether it merges the window
   auto finish = [&](bool go) {
     if constexpr (MERGE) {
       if (wv == 0 && lane == 0) s_go = go;
       wh_lds_barrier();
       if (s_go) {
-        if constexpr (WIN) {
-          CT_MARK(CT_LOGIT, 1);  // this workgroup combines the window's rows
-          // the rows' records alias the merge's history / ancestry staging (written after
-          // the barrier below); wave b combines row b (G <= MG_MAXG <= 8 waves)
-          float* wrec = reinterpret_cast<float*>(&mlds.oh[0][0]);
-          if (wv < s.G) {
-            const int rr = w * s.G + wv;
-            const auto rs = wt_rsrc(s.lpart + (int64_t)rr * LP_SLICES * LP_REC);
-            constexpr int N4 = NS * LP_REC / 4, PER = (N4 + 63) / 64;
-            float4_t v[PER];
-#pragma unroll
-            for (int k = 0; k < PER; ++k)
-              v[k] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, min(lane + 64 * k, N4 - 1) * 16, 0, 16));
-            float* mine = wrec + wv * NS * LP_REC;
-#pragma unroll
-            for (int k = 0; k < PER; ++k)
-              if (lane + 64 * k < N4) reinterpret_cast<float4_t*>(mine)[lane + 64 * k] = v[k];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // one wave: its own LDS writes
-            lp_combine<NS, false>(reinterpret_cast<const LPRec*>(mine), rr, s, o, lane, mlds.wcv + wv * KC,
-                                  mlds.wci + wv * KC);
-          }
-          wh_lds_barrier();
-          CT_MARK(CT_LOGIT, 2);  // this workgroup merges its window
-          merge_window<LP_THREADS, false, true>(s, o, em, w, tid, mlds);
-        } else {
-          CT_MARK(CT_LOGIT, 2);  // this workgroup merges its window
-          merge_window<LP_THREADS, true>(s, o, em, w, tid, mlds);
-        }
+        CT_MARK(CT_LOGIT, 2);  // this workgroup merges its window
+        merge_window<LP_THREADS, true>(s, o, em, w, tid, mlds);
       }
     }
   };
@@ -933,8 +876,7 @@ __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __r
         wt_rec(rec_off + offsetof(LPRec, gv), gv); wt_rec(rec_off + offsetof(LPRec, gi), __builtin_bit_cast(float, gi));
         wt_rec(rec_off + offsetof(LPRec, gx), gi != 0x7fffffff ? gx : -INFINITY);
       }
-      if constexpr (WIN) go = arrive_window();
-      else if constexpr (FUSED) go = arrive_and_combine();
+      go = arrive_and_combine();
     } else {
       // beam: each lane holds up to two wave candidates (NWV * need <= 72), sorted within
       // the lane; `need` wave-level rounds take the best remaining head
@@ -958,8 +900,7 @@ __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __r
         }
       }
       if (lane == 0) { wt_rec(rec_off + offsetof(LPRec, mx), MX); wt_rec(rec_off + offsetof(LPRec, se), SE); }
-      if constexpr (WIN) go = arrive_window();
-      else if constexpr (FUSED) go = arrive_and_combine();
+      go = arrive_and_combine();
     }
   }  // wave 0
   finish(go);
@@ -970,10 +911,8 @@ __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __r
 // selection between text and timestamps, the normaliser, then argbest / top-(G+1) with one
 // slice per lane (decoding.py:522-531 and the candidate lists of 707-733)
 // WT: the candidates are stored write-through (sc1), for the merge in the same launch
-// cv_out / ci_out (WT false): where the row's candidates go instead of s.cand_val / cand_idx
 template <int NS, bool WT>
-__device__ __forceinline__ void lp_combine(const LPRec* rec, int r, const DecState& s, const DecOpts& o, int lane,
-                                           float* cv_out, int* ci_out) {
+__device__ __forceinline__ void lp_combine(const LPRec* rec, int r, const DecState& s, const DecOpts& o, int lane) {
   constexpr int TS = NS - 1;
   float m = -INFINITY;
   for (int j = 0; j < NS; ++j) m = fmaxf(m, rec[j].mx);
@@ -996,8 +935,8 @@ __device__ __forceinline__ void lp_combine(const LPRec* rec, int r, const DecSta
   for (int j = j0; j < NS; ++j)
     if (rec[j].mx > -INFINITY) se += rec[j].se * __expf(rec[j].mx - m);
   const float logS = logf(se);
-  float* cv = cv_out ? cv_out : s.cand_val + (int64_t)r * KC;
-  int* ci = ci_out ? ci_out : s.cand_idx + (int64_t)r * KC;
+  float* cv = s.cand_val + (int64_t)r * KC;
+  int* ci = s.cand_idx + (int64_t)r * KC;
   // lane j holds slice j (NS <= 64): wave-level argbest rounds, the order of better()
   // (value desc, index asc) as in the slices themselves
   static_assert(NS <= 64 && NS <= LP_SLICES, "one lane per slice");
@@ -1048,104 +987,43 @@ __device__ __forceinline__ void lp_combine(const LPRec* rec, int r, const DecSta
   }
 }
 
-template <int NS>
-__global__ __launch_bounds__(64) void k_logit_combine(DecState s, DecOpts o) {
-  const int r = blockIdx.x, w = r / s.G, lane = threadIdx.x;
-  // the row's slice records -> LDS in one round trip, issued with the done flag's load
-  // (the merge reads them serially; from global memory every read would be a dependent load)
-  __shared__ __attribute__((aligned(16))) float recs[NS * LP_REC];
-  {
-    constexpr int N4 = NS * LP_REC / 4, PER = (N4 + 63) / 64;
-    const float4_t* src = reinterpret_cast<const float4_t*>(s.lpart + (int64_t)r * LP_SLICES * LP_REC);
-    float4_t* dst = reinterpret_cast<float4_t*>(recs);
-    float4_t v[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) v[k] = src[min(lane + 64 * k, N4 - 1)];
-    if (s.done[w]) return;
-#pragma unroll
-    for (int k = 0; k < PER; ++k)
-      if (lane + 64 * k < N4) dst[lane + 64 * k] = v[k];
-  }
-  __syncthreads();
-  lp_combine<NS, false>(reinterpret_cast<const LPRec*>(recs), r, s, o, lane);
-}
-
 // the selection of one update; with `em` (launch_select_merge) the fused k_logit_part also
 // runs each window's merge and this returns true
 static bool select_rows(float* logits, int ldl, const DecState& s, const DecOpts& o, int nwin, hipStream_t st,
                         const MergeEmbed* em) {
-  // the sliced selection (k_logit_part + k_logit_combine) unless WHISPER_HIP_LOGIT_SPLIT=0
+  // the sliced selection (k_logit_part) unless WHISPER_HIP_LOGIT_SPLIT=0
   // (config 2, turbo one window: 0.380 -> 0.346 ms per token; config 3 unchanged)
   static const bool split = [] {
     const char* e = tune_env("WHISPER_HIP_LOGIT_SPLIT");
     return !(e && e[0] == '0');
   }();
-  // the window's merge in the selection launch unless WHISPER_HIP_LP_MERGE=0 (tuning: k_merge
-  // as its own launch)
-  static const bool fold_merge = [] {
-    const char* e = tune_env("WHISPER_HIP_LP_MERGE");
-    return !(e && e[0] == '0');
-  }();
   const int rows = nwin * s.G;
-  const bool merge = em && fold_merge && s.lpw_cnt && s.G <= MG_MAXG;
-  // the window-level arrival (k_logit_part<..., WIN>): tuning build only, WHISPER_HIP_LP_WIN=1.
-  // Measured not faster (profiles/r06/ab_selection_window_arrival.txt: 100 rows 51.5 vs
-  // 51.2 us, one turbo window 27.2 vs 28.5-28.9 us: the last slice's workgroup combining
-  // every row after the last arrival costs what the row-then-window hand-off saved)
-  static const bool win_on = [] {
-    const char* e = tune_env("WHISPER_HIP_LP_WIN");
-    return e && e[0] == '1';
-  }();
-  auto lp_win_fits = [&](int ns) {
-    return win_on && (size_t)s.G * ns * LP_REC * 4 <= sizeof(MergeLds::oh) + sizeof(MergeLds::oa);
-  };
+  const bool merge = em && s.lpw_cnt && s.G <= MG_MAXG;  // the window's merge in the selection launch
   const bool sp = split && s.hctx <= LP_THREADS;  // k_logit_part: one history position per thread
   const MergeEmbed none;
   const MergeEmbed& e = em ? *em : none;
-  // the records merged by the row's last slice (fused) unless WHISPER_HIP_LP_FUSED=0 (tuning:
-  // k_logit_combine as its own launch)
-  const char* fe = tune_env("WHISPER_HIP_LP_FUSED");
-  const bool fused = !(fe && fe[0] == '0');
+#define LP(NS_, EPT_)                                                                                                  \
+  do {                                                                                                                 \
+    if (merge) k_logit_part<NS_, EPT_, true><<<dim3(rows, NS_), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part"); \
+    else k_logit_part<NS_, EPT_><<<dim3(rows, NS_), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part"); \
+    return merge;                                                                                                      \
+  } while (0)
   // Every batch of >= 2 windows selects with 16 slices (15 text + timestamps, 8 elements
   // per lane): the per-slice normaliser sums, hence a row's log-probabilities to the last
   // bit, then do not depend on the batch size (batch invariance); at 100
   // rows 8 slices measured 3.5 us and 32 slices 10 us slower per step
   // (profiles/r03/step_tail_ab.txt).  One window keeps 32 slices (its latency path) —
   // the same window-count cut as the k_proj1 layers (wh_runtime.hip p1_active), so the
-  // rule holds for greedy and small beams too.
-  // Tuning: WHISPER_HIP_LP_NS=8 / 32 forces the other counts (A/B)
-  const char* nse = tune_env("WHISPER_HIP_LP_NS");
-  const int ns_force = nse ? atoi(nse) : 16;  // slices for >= 2 windows
+  // rule holds for greedy and small beams too.  8 slices (16 elements per lane) serve the
+  // vocabularies too large for either.
   const bool one_win = nwin == 1;
-  if (sp && fused && !one_win && ns_force == 16 && o.ts_begin > 0 &&
-      (o.ts_begin + 14) / 15 <= LP_THREADS * 8 && o.V - o.ts_begin <= LP_THREADS * 8) {
-    if (merge && lp_win_fits(16)) k_logit_part<16, 8, true, true, true><<<dim3(rows, 16), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part<win>");
-    else if (merge) k_logit_part<16, 8, true, true><<<dim3(rows, 16), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part");
-    else k_logit_part<16, 8, true><<<dim3(rows, 16), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part");
-    return merge;
-  }
-  if (sp && o.ts_begin > 0 && (one_win || ns_force == 32) && (o.ts_begin + 30) / 31 <= LP_THREADS * 4 &&
-      o.V - o.ts_begin <= LP_THREADS * 4) {
-    if (fused) {
-      if (merge && lp_win_fits(32)) k_logit_part<32, 4, true, true, true><<<dim3(rows, 32), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part<win>");
-      else if (merge) k_logit_part<32, 4, true, true><<<dim3(rows, 32), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part");
-      else k_logit_part<32, 4, true><<<dim3(rows, 32), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part");
-      return merge;
-    }
-    k_logit_part<32, 4, false><<<dim3(rows, 32), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part");
-    k_logit_combine<32><<<rows, 64, 0, st>>>(s, o), wh_launched("k_logit_combine");
-    return false;
-  }
-  if (sp && o.ts_begin > 0 && (o.ts_begin + 6) / 7 <= LP_THREADS * 16 && o.V - o.ts_begin <= LP_THREADS * 16) {
-    if (fused) {
-      if (merge) k_logit_part<8, 16, true, true><<<dim3(rows, 8), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part");
-      else k_logit_part<8, 16, true><<<dim3(rows, 8), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part");
-      return merge;
-    }
-    k_logit_part<8, 16, false><<<dim3(rows, 8), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part");
-    k_logit_combine<8><<<rows, 64, 0, st>>>(s, o), wh_launched("k_logit_combine");
-    return false;
-  }
+  if (sp && !one_win && o.ts_begin > 0 && (o.ts_begin + 14) / 15 <= LP_THREADS * 8 && o.V - o.ts_begin <= LP_THREADS * 8)
+    LP(16, 8);
+  if (sp && o.ts_begin > 0 && one_win && (o.ts_begin + 30) / 31 <= LP_THREADS * 4 && o.V - o.ts_begin <= LP_THREADS * 4)
+    LP(32, 4);
+  if (sp && o.ts_begin > 0 && (o.ts_begin + 6) / 7 <= LP_THREADS * 16 && o.V - o.ts_begin <= LP_THREADS * 16)
+    LP(8, 16);
+#undef LP
   k_logit_rows<<<nwin * s.G, LR_THREADS, 0, st>>>(logits, ldl, s, o), wh_launched("k_logit_rows");
   return false;
 }
@@ -1167,513 +1045,6 @@ void launch_merge(const DecState& s, const DecOpts& o, int nwin, hipStream_t st,
 void launch_select_merge(float* logits, int ldl, const DecState& s, const DecOpts& o, int nwin, hipStream_t st,
                          const MergeEmbed& em) {
   if (!select_rows(logits, ldl, s, o, nwin, st, &em)) launch_merge(s, o, nwin, st, em);
-}
-
-// ------------------------------------------------------------ vocabulary + selection + merge, one window
-// The single-window step's whole token tail in ONE launch (round 4): k_vocab1's balanced
-// vocabulary projection (256 workgroups, 12-13 16-column tiles each, the final LayerNorm in
-// the prologue, a ring of D weight tiles in flight), then, per workgroup and row, the
-// selection of k_logit_part over the workgroup's own ~200 columns — filters, max, sum of
-// exp, top-(G+1) / argbest / Gumbel best — as a record per (row, part): part 0 the text
-// ids < timestamp_begin, part 1 the timestamp ids (only the workgroup straddling the
-// boundary has both), stored write-through.  The workgroup whose arrival completes the
-// launch merges every row's records (decoding.py:522-531: the timestamp-vs-text rule from
-// the combined normaliser and the two maxima; top-(G+1) across the records' sorted lists)
-// and then runs the window's candidate merge (merge_window) — no logits round trip, no
-// selection or merge launch.  Same choices as the sliced selection; the normaliser is
-// summed over other partitions, so log-probabilities can differ in the last bits.
-struct LpMasks {
-  int mlo[4], mhi[4], kid[5];
-};
-// the filters of decoding.py:450-532 for one row as four [lo, hi) masks and five ids
-__device__ __forceinline__ LpMasks lp_masks(const DecOpts& o, bool last_ts, bool penult_ts, bool first, int ts_last) {
-  const int tb = o.ts_begin, V = o.V;
-  LpMasks f;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) f.mlo[q] = f.mhi[q] = 0;
-#pragma unroll
-  for (int q = 0; q < 5; ++q) f.kid[q] = -1;
-  if (o.timestamps) {
-    if (last_ts) {
-      if (penult_ts) { f.mlo[0] = tb; f.mhi[0] = V; }
-      else { f.mlo[0] = 0; f.mhi[0] = o.eot; }
-    }
-    if (ts_last >= 0) {
-      f.mlo[1] = tb;
-      f.mhi[1] = (last_ts && !penult_ts) ? ts_last : ts_last + 1;
-    }
-    if (first) {
-      f.mlo[2] = 0; f.mhi[2] = tb;
-      if (o.max_initial >= 0) { f.mlo[3] = tb + o.max_initial + 1; f.mhi[3] = V; }
-    }
-    f.kid[4] = o.no_ts;
-  }
-  if (first && o.suppress_blank)
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-      if (b < o.n_blank) f.kid[b] = o.blank[b];
-  return f;
-}
-
-struct VsArgs {
-  DecState s;
-  DecOpts o;
-  MergeEmbed em;
-  float* rec;  // [VS_ROWS][2 parts][VS_NB workgroups][VS_REC]
-  int* cnt;    // the launch's arrival counter (zero between launches)
-};
-constexpr int VS_ROWS = 8, VS_NB = 256, VS_REC = 32, VS_TMAX = 13;
-// record words: 0 mx, 1 se, 2 bv, 3 bi, 4 gv, 5 gi, 6 gx, 8.. tv[KC], 20.. ti[KC] (the first
-// 8 of each list 16-byte aligned: two b128 loads)
-constexpr int VS_TV = 8, VS_TI = 20;
-static_assert(VS_TI + KC <= VS_REC, "record size");
-
-#if WH_TUNING
-// tuning build: per-workgroup wall-clock marks of the last k_vocab_sel launch (100 MHz),
-// read by wh_tune_vs_trace (profiles/vocab_sel_trace.py)
-constexpr int VS_MARKS = 10;
-__device__ unsigned long long g_vs_trace[VS_NB][VS_MARKS];
-#define VS_MARK(k)                                                                          \
-  do {                                                                                      \
-    if (threadIdx.x == 0) g_vs_trace[blockIdx.x][k] = __builtin_amdgcn_s_memrealtime();    \
-  } while (0)
-#else
-#define VS_MARK(k) \
-  do {             \
-  } while (0)
-#endif
-
-template <int D>
-__global__ __launch_bounds__(512) void k_vocab_sel(GemmArgs a, VsArgs v) {
-  constexpr int KW = 8, SW = 5, K = KW * SW * 32, TMAX = VS_TMAX;  // K 1280 (launcher)
-  constexpr int XROW = K * 2 + 16;
-  extern __shared__ __attribute__((aligned(16))) char vs_lds[];
-  float4_t* red = reinterpret_cast<float4_t*>(vs_lds + 8 * XROW);  // [TMAX tiles][KW][64]
-  float* lg = reinterpret_cast<float*>(vs_lds);                   // [8][TMAX * 16] logits (X dead)
-  MergeLds& mlds = *reinterpret_cast<MergeLds*>(vs_lds + 8 * XROW);  // red's space, after the records
-  __shared__ LpMasks fm[VS_ROWS];
-  __shared__ int s_last;
-  const DecState& s = v.s;
-  const DecOpts& o = v.o;
-  VS_MARK(0);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
-  const int nt = (a.N + 15) / 16, b = blockIdx.x, nb = gridDim.x;
-  const int t0 = range_split(b, nt, nb), t1 = range_split(b + 1, nt, nb), ntl = t1 - t0;
-  const half_t* W = reinterpret_cast<const half_t*>(a.W);
-  const int kb = wave * SW * 32;
-  // 1. the window's state first (its loads retire first), then the LayerNorm operands,
-  // then the first D - 1 weight tiles
-  const int done = s.done[0], len = s.len[0], sb = s.sample_begin[0];
-  auto load_tile = [&](int tl, Frag<half_t> (&wf)[SW]) {
-    const int tile = t0 + min(tl, ntl - 1);
-    const half_t* wp = W + (int64_t)min(tile * 16 + r, a.N - 1) * K + kb + 8 * g;
-#pragma unroll
-    for (int s2 = 0; s2 < SW; ++s2) frag_load_stream(wf[s2], wp + s2 * 32);
-  };
-  constexpr int CPLM = 5;
-  const int row = wave;
-  const bool lnrow = row < a.M;
-  float4_t xv[CPLM], gv[CPLM], bv[CPLM];
-  if (lnrow) {
-    const float* xr = a.xf32 + (int64_t)row * K;
-#pragma unroll
-    for (int i = 0; i < CPLM; ++i) {
-      const int c = lane + 64 * i;
-      xv[i] = load4f(xr + 4 * c);
-      gv[i] = load4f(a.ln_g + 4 * c);
-      bv[i] = load4f(a.ln_b + 4 * c);
-    }
-  }
-  Frag<half_t> wf[D][SW];
-#pragma unroll
-  for (int t = 0; t < D - 1; ++t) load_tile(t, wf[t]);
-  VS_MARK(1);
-  // 2. this row's history facts (decoding.py:503-508), in flight during the projection
-  const int tb = o.ts_begin, V = o.V;
-  const int c0 = t0 * 16, c1 = min(t1 * 16, a.N);
-  int hv[7], h1 = 0, h2 = 0;
-  unsigned sw[4] = {0u, 0u, 0u, 0u};  // suppress words of this lane's columns
-  unsigned long long seed = 0;
-  if (lnrow) {
-    const int* hist = s.hist + (int64_t)row * s.hctx;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) hv[i] = hist[min(sb + lane + 64 * i, max(len - 1, 0))];
-    h1 = hist[max(len - 1, 0)];
-    h2 = hist[max(len - 2, 0)];
-    if (o.suppress)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) sw[u] = o.suppress[min(c0 + lane + 64 * u, c1 - 1) >> 5];
-    seed = s.seed[0];
-  }
-  // 3. the final LayerNorm (k_vocab1's prologue) and the projection
-  {
-    half_t* dst = reinterpret_cast<half_t*>(vs_lds + row * XROW);
-    if (!lnrow) {
-      for (int c = lane; c < K / 4; c += 64) store4(dst + 4 * c, 0.f, 0.f, 0.f, 0.f);
-    } else {
-      float sm = 0.f;
-#pragma unroll
-      for (int i = 0; i < CPLM; ++i) sm += xv[i][0] + xv[i][1] + xv[i][2] + xv[i][3];
-      const float mean = wave_sum(sm) / (float)K;
-      float q = 0.f;
-#pragma unroll
-      for (int i = 0; i < CPLM; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = xv[i][e] - mean;
-          q += d * d;
-        }
-      const float rstd = rsqrtf(wave_sum(q) / (float)K + a.ln_eps);
-#pragma unroll
-      for (int i = 0; i < CPLM; ++i) {
-        const float4_t x4 = xv[i];
-        store4(dst + 4 * (lane + 64 * i), (x4[0] - mean) * rstd * gv[i][0] + bv[i][0],
-               (x4[1] - mean) * rstd * gv[i][1] + bv[i][1], (x4[2] - mean) * rstd * gv[i][2] + bv[i][2],
-               (x4[3] - mean) * rstd * gv[i][3] + bv[i][3]);
-      }
-    }
-  }
-  __syncthreads();
-  Frag<half_t> xf[SW];
-#pragma unroll
-  for (int s2 = 0; s2 < SW; ++s2)
-    frag_load(xf[s2], reinterpret_cast<const half_t*>(vs_lds + min(r, 7) * XROW) + kb + s2 * 32 + 8 * g);
-#pragma unroll
-  for (int t = 0; t < TMAX; ++t) {
-    if (t + D - 1 < TMAX) load_tile(t + D - 1, wf[(t + D - 1) % D]);
-    float4_t acc = (float4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s2 = 0; s2 < SW; ++s2) mfma_step(acc, wf[t % D][s2], xf[s2]);
-    if (t < ntl) red[(t * KW + wave) * 64 + lane] = acc;
-  }
-  VS_MARK(2);
-  // a finished window (the decode's last no-op steps): no selection; its rows are
-  // re-embedded (merge_window).  Checked only now, so that nothing of the projection's
-  // load stream waits on the window state.
-  if (done) {
-    if (b == 0) {
-      __syncthreads();  // every wave's X fragments are read: the merge scratch may overlap
-      merge_window<512, false>(s, o, v.em, 0, tid, mlds);
-    }
-    return;
-  }
-  // the row's masks (its history loads have long landed)
-  if (lnrow) {
-    int pm = -1, pt = -1;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int p = sb + lane + 64 * i;
-      if (p < len && hv[i] >= tb) { pm = p; pt = hv[i]; }
-    }
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) {
-      const int op = __shfl_xor(pm, o2, 64), ot = __shfl_xor(pt, o2, 64);
-      if (op > pm) { pm = op; pt = ot; }
-    }
-    const int nseq = len - sb;
-    const bool last_ts = nseq >= 1 && h1 >= tb, penult_ts = nseq < 2 || h2 >= tb, first = len == sb;
-    const LpMasks f = lp_masks(o, last_ts, penult_ts, first, pm >= 0 ? pt : -1);
-    if (lane == 0) fm[row] = f;
-  }
-  __syncthreads();
-  // 4. the logits of this workgroup's columns: the 8 eighths in wave order (k_vocab1)
-  constexpr int LGW = TMAX * 16;
-  for (int i = tid; i < ntl * 64; i += 512) {
-    const int tl = i >> 6, ln = i & 63, rr = ln & 15;
-    float4_t x4 = red[(tl * KW) * 64 + ln];
-#pragma unroll
-    for (int w2 = 1; w2 < KW; ++w2) x4 += red[(tl * KW + w2) * 64 + ln];
-    if (rr < a.M) *reinterpret_cast<float4_t*>(lg + rr * LGW + tl * 16 + 4 * (ln >> 4)) = x4;
-  }
-  __syncthreads();
-  VS_MARK(3);
-  // 5. one wave per row: a record per part of this workgroup's columns
-  const int need = s.G + 1;
-  if (lnrow) {
-    const LpMasks f = fm[row];
-    const unsigned long long key =
-        splitmix64(seed ^ ((unsigned long long)row << 40) ^ ((unsigned long long)len << 20));
-#pragma unroll
-    for (int part = 0; part < 2; ++part) {
-      const int lo = part ? max(c0, tb) : c0, hi = part ? c1 : min(c1, tb);
-      if (lo >= hi) continue;
-      const auto rs = wt_rsrc(v.rec + ((int64_t)(row * 2 + part) * VS_NB + b) * VS_REC);
-      float x[4];
-      float mx = -INFINITY;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = c0 + lane + 64 * u;
-        x[u] = -INFINITY;
-        if (i >= lo && i < hi) {
-          bool kill = (sw[u] >> (i & 31)) & 1u;
-#pragma unroll
-          for (int q = 0; q < 5; ++q) kill |= i == f.kid[q];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) kill |= (i >= f.mlo[q] && i < f.mhi[q]);
-          if (!kill) x[u] = lg[row * LGW + lane + 64 * u];
-        }
-        mx = fmaxf(mx, x[u]);
-      }
-      mx = wave_max(mx);
-      float se = 0.f;
-      if (mx > -INFINITY) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) se += __expf(x[u] - mx);
-      }
-      se = wave_sum(se);
-      if (lane == 0) { wt_store1(rs, 0, mx); wt_store1(rs, 4, se); }
-      if (!o.beam) {
-        float bvv = -INFINITY, gvv = -INFINITY, gx = -INFINITY;
-        int bi = 0x7fffffff, gi = 0x7fffffff;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int i = c0 + lane + 64 * u;
-          if (i < lo || i >= hi) continue;
-          if (better(x[u], i, bvv, bi)) { bvv = x[u]; bi = i; }
-          if (o.temperature > 0.f && x[u] != -INFINITY) {
-            const unsigned long long z = splitmix64(key + (unsigned long long)i);
-            const float uu = ((float)(z >> 40) + 0.5f) * (1.0f / 16777216.0f);
-            const float gsc = x[u] / o.temperature - logf(-logf(uu));
-            if (better(gsc, i, gvv, gi)) { gvv = gsc; gi = i; gx = x[u]; }
-          }
-        }
-        wave_argbest(bvv, bi);
-        const int mine = gi;
-        const float myx = gx;
-        wave_argbest(gvv, gi);
-        const unsigned long long own = __ballot(mine == gi && gi != 0x7fffffff);
-        const float gxw = own ? __shfl(myx, __ffsll((long long)own) - 1, 64) : -INFINITY;
-        if (lane == 0) {
-          wt_store1(rs, 8, bvv); wt_store1(rs, 12, __builtin_bit_cast(float, bi));
-          wt_store1(rs, 16, gvv); wt_store1(rs, 20, __builtin_bit_cast(float, gi));
-          wt_store1(rs, 24, gi != 0x7fffffff ? gxw : -INFINITY);
-        }
-      } else {
-        unsigned taken = 0u;
-        for (int q = 0; q < need; ++q) {
-          float bvv = -INFINITY;
-          int bi = 0x7fffffff;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int i = c0 + lane + 64 * u;
-            if (i >= lo && i < hi && !((taken >> u) & 1u) && better(x[u], i, bvv, bi)) { bvv = x[u]; bi = i; }
-          }
-          const int mine = bi;
-          wave_argbest(bvv, bi);
-          if (mine == bi && bi != 0x7fffffff) taken |= 1u << ((bi - c0 - lane) / 64);
-          if (lane == 0) {
-            wt_store1(rs, 4 * (VS_TV + q), bvv);
-            wt_store1(rs, 4 * (VS_TI + q), __builtin_bit_cast(float, bi));
-          }
-        }
-      }
-    }
-  }
-  // 6. arrival: every storing wave drains its records, one agent add per workgroup
-  VS_MARK(4);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  VS_MARK(5);
-  if (tid == 0) s_last = __hip_atomic_fetch_add(v.cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nb - 1;
-  __syncthreads();
-  VS_MARK(6);
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");  // no instruction: keeps the loads below the add
-  if (tid == 0) __hip_atomic_store(v.cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // 7. the combine, one wave per row: text records of the workgroups with columns below
-  // timestamp_begin (lane j: workgroups j, j + 64, ...), timestamp records of those above
-  if (lnrow) {
-    auto col0 = [&](int wb) { return range_split(wb, nt, nb) * 16; };
-    auto col1 = [&](int wb) { return min(range_split(wb + 1, nt, nb) * 16, a.N); };
-    const auto rsr = wt_rsrc(v.rec);
-    auto ld = [&](int part, int wb, int word) -> float {
-      return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                           rsr, (((row * 2 + part) * VS_NB + wb) * VS_REC + word) * 4, 0, 16));
-    };
-    // the first workgroup with timestamp columns (<= 64 of them: launcher)
-    int bts = nb;
-    for (int bb = lane; bb < nb; bb += 64)
-      if (col1(bb) > tb) bts = min(bts, bb);
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) bts = min(bts, __shfl_xor(bts, o2, 64));
-    // record k of this lane: k < 4 text (workgroup lane + 64 k), k == 4 timestamps
-    // (workgroup bts + lane); every word the combine reads is loaded here, in one round trip
-    constexpr int NR = 5;
-    auto rwb = [&](int k) { return k < 4 ? lane + 64 * k : bts + lane; };
-    auto ld4 = [&](int part, int wb, int word) -> float4_t {
-      return __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                              rsr, (((row * 2 + part) * VS_NB + wb) * VS_REC + word) * 4, 0, 16));
-    };
-    bool val[NR];
-    float rmx[NR], rse[NR];
-    float4_t w0[NR], w1[NR], tq0[NR], tq1[NR], iq0[NR], iq1[NR];
-    float tv8[NR], ti8[NR];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int wb = rwb(k), part = k == 4;
-      val[k] = wb < nb && (part ? col1(wb) > tb && col0(wb) < a.N : col0(wb) < min(tb, a.N));
-      const int wc = val[k] ? wb : 0;
-      w0[k] = ld4(part, wc, 0);
-      if (o.beam) {
-        tq0[k] = ld4(part, wc, VS_TV);
-        tq1[k] = ld4(part, wc, VS_TV + 4);
-        iq0[k] = ld4(part, wc, VS_TI);
-        iq1[k] = ld4(part, wc, VS_TI + 4);
-        tv8[k] = ld(part, wc, VS_TV + 8);
-        ti8[k] = ld(part, wc, VS_TI + 8);
-      } else {
-        w1[k] = ld4(part, wc, 4);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      rmx[k] = val[k] ? w0[k][0] : -INFINITY;
-      rse[k] = w0[k][1];
-    }
-    float m = -INFINITY, mtx = -INFINITY, mts = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      m = fmaxf(m, rmx[k]);
-      if (k < 4) mtx = fmaxf(mtx, rmx[k]);
-      else mts = fmaxf(mts, rmx[k]);
-    }
-    m = wave_max(m);
-    mtx = wave_max(mtx);
-    mts = wave_max(mts);
-    bool text_killed = false;
-    if (o.timestamps) {
-      float st0 = 0.f, sts = 0.f;
-#pragma unroll
-      for (int k = 0; k < NR; ++k)
-        if (rmx[k] > -INFINITY) {
-          st0 += rse[k] * __expf(rmx[k] - m);
-          if (k == 4) sts += rse[k] * __expf(rmx[k] - mts);
-        }
-      st0 = wave_sum(st0);
-      sts = wave_sum(sts);
-      const float lS0 = logf(st0);
-      const float lts = mts > -INFINITY ? (mts - m) - lS0 : -INFINITY;
-      const float ltx = mtx > -INFINITY ? (mtx - m) - lS0 : -INFINITY;
-      const float ts_lp = lts > -INFINITY ? lts + logf(sts) : -INFINITY;
-      text_killed = ts_lp > ltx;
-      if (text_killed) m = mts;
-    }
-    bool kept[NR];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) kept[k] = val[k] && (!text_killed || k == 4);
-    float se = 0.f;
-#pragma unroll
-    for (int k = 0; k < NR; ++k)
-      if (kept[k] && rmx[k] > -INFINITY) se += rse[k] * __expf(rmx[k] - m);
-    const float logS = logf(wave_sum(se));
-    const auto rcv = wt_rsrc(s.cand_val + (int64_t)row * KC), rci = wt_rsrc(s.cand_idx + (int64_t)row * KC);
-    if (!o.beam) {
-      const bool samp = o.temperature > 0.f;
-      float bvv = -INFINITY, bx = -INFINITY;
-      int bi = 0x7fffffff;
-#pragma unroll
-      for (int k = 0; k < NR; ++k) {
-        if (!kept[k]) continue;
-        const float cv = samp ? w1[k][0] : w0[k][2];
-        const int ci = __builtin_bit_cast(int, samp ? w1[k][1] : w0[k][3]);
-        const float cx = samp ? w1[k][2] : cv;
-        if (better(cv, ci, bvv, bi)) { bvv = cv; bi = ci; bx = cx; }
-      }
-      const int mine = bi;
-      const float myx = bx;
-      wave_argbest(bvv, bi);
-      const unsigned long long own = __ballot(mine == bi && bi != 0x7fffffff);
-      const float wx = own ? __shfl(myx, __ffsll((long long)own) - 1, 64) : -INFINITY;
-      if (lane == 0 && bi != 0x7fffffff) {
-        wt_store1(rci, 0, __builtin_bit_cast(float, bi));
-        wt_store1(rcv, 0, (wx - m) - logS);
-      }
-    } else {
-      // each lane's kept records' sorted lists; `need` rounds take the best head
-      float tv[NR][KC];
-      int ti[NR][KC];
-#pragma unroll
-      for (int k = 0; k < NR; ++k) {
-#pragma unroll
-        for (int q = 0; q < KC; ++q) {
-          const float x = q < 4 ? tq0[k][q] : q < 8 ? tq1[k][q - 4] : tv8[k];
-          const float xi = q < 4 ? iq0[k][q] : q < 8 ? iq1[k][q - 4] : ti8[k];
-          const bool ok = kept[k] && q < need;
-          tv[k][q] = ok ? x : -INFINITY;
-          ti[k][q] = ok ? __builtin_bit_cast(int, xi) : 0x7fffffff;
-        }
-      }
-      int hd[NR] = {0, 0, 0, 0, 0};
-      for (int q = 0; q < need; ++q) {
-        float hv2 = -INFINITY;
-        int hi2 = 0x7fffffff, hk = -1;
-#pragma unroll
-        for (int k = 0; k < NR; ++k) {
-          float cv = -INFINITY;
-          int ci = 0x7fffffff;
-#pragma unroll
-          for (int qq = 0; qq < KC; ++qq)
-            if (qq == hd[k]) { cv = tv[k][qq]; ci = ti[k][qq]; }
-          if (hd[k] < need && better(cv, ci, hv2, hi2)) { hv2 = cv; hi2 = ci; hk = k; }
-        }
-        float bvv = hv2;
-        int bi = hi2;
-        wave_argbest(bvv, bi);
-        if (bi == hi2 && bi != 0x7fffffff && hk >= 0) {
-#pragma unroll
-          for (int k = 0; k < NR; ++k)
-            if (k == hk) ++hd[k];
-        }
-        if (lane == 0) {
-          wt_store1(rcv, 4 * q, (bvv - m) - logS);
-          wt_store1(rci, 4 * q, __builtin_bit_cast(float, bi));
-        }
-      }
-    }
-  }
-  // 8. the window's candidate merge, with the candidates just written (sc1 loads)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  VS_MARK(7);
-  merge_window<512, true>(s, o, v.em, 0, tid, mlds);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  VS_MARK(8);
-}
-
-#if WH_TUNING
-extern "C" int wh_tune_vs_trace(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vs_trace), sizeof(g_vs_trace)) == hipSuccess ? 0 : -1;
-}
-#endif
-
-// one window's tail in one launch; -1 when the shape is not the single-window fp16 step
-bool vocab_select_on() {
-  static const bool on = [] {  // tuning build only: WHISPER_HIP_VOCAB_SEL=1
-    const char* e = tune_env("WHISPER_HIP_VOCAB_SEL");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
-int launch_vocab_select(const GemmArgs& a, const DecState& s, const DecOpts& o, const MergeEmbed& em, float* rec,
-                        int* cnt, hipStream_t st) {
-  const int nt = (a.N + 15) / 16;
-  if (!vocab_select_on() || !rec || !cnt || !a.xf32 || a.K != 1280 || a.bias || a.M < 1 || a.M > VS_ROWS || a.M != s.G ||
-      s.G > MG_MAXG || nt > VS_NB * VS_TMAX || nt < VS_NB || o.ts_begin <= 0 || o.ts_begin > a.N || a.N != o.V ||
-      a.N - o.ts_begin > 64 * 16 * (nt / VS_NB) - 16)  // <= 64 workgroups hold timestamp columns
-    return -1;
-  constexpr int D = 6;
-  const int lds = 8 * (1280 * 2 + 16) + VS_TMAX * 8 * 64 * 16;
-  static_assert(sizeof(MergeLds) <= VS_TMAX * 8 * 64 * 16, "merge scratch inside the reduction space");
-  // (the dynamic size itself: the kernel's static LDS counts against the 160 KB too)
-  static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vocab_sel<D>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
-  if (!attr) return -5;
-  VsArgs v;
-  v.s = s; v.o = o; v.em = em; v.rec = rec; v.cnt = cnt;
-  k_vocab_sel<D><<<VS_NB, 512, lds, st>>>(a, v), wh_launched("k_vocab_sel");
-  return 0;
 }
 
 // ------------------------------------------------------------ per-step ABI state updates

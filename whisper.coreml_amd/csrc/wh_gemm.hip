@@ -837,10 +837,10 @@ WH_DEV void vocab_store_tr(const GemmArgs& a, const float4_t (&acc)[MT], float* 
 // VC k-steps, the next chunk in flight while one is multiplied.  Accumulation runs over the
 // k-steps in ascending order into one accumulator per 16 x 16 block, as in k_vocab_small and
 // k_gemv_x: a row's logits are bit-identical whichever kernel the batch size selects.
-template <int MT, int DEPTH, bool TR = false>
+template <int MT>
 __global__ __launch_bounds__(1024) void k_vocab_2p(GemmArgs a) {
   CT_MARK(CT_VOCAB, 0);
-  constexpr int NW = 16, VC = DEPTH > 2 ? 4 : 5, KH = 640, SH = KH / 32, NCH = SH / VC;  // K 1280 (launcher)
+  constexpr int NW = 16, DEPTH = 3, VC = 4, KH = 640, SH = KH / 32, NCH = SH / VC;  // K 1280 (launcher)
   constexpr int XROW = KH * 2 + 16;
   extern __shared__ __attribute__((aligned(16))) char xs2[];
   constexpr int K = 2 * KH;
@@ -928,152 +928,9 @@ __global__ __launch_bounds__(1024) void k_vocab_2p(GemmArgs a) {
     }
   }
   CT_MARK(CT_VOCAB, 1);  // the MFMAs issued: the epilogue starts
-  if constexpr (TR) {
-    vocab_store_tr<MT, NW>(a, acc, reinterpret_cast<float*>(xs2), t0, t1, act, tid, wave, r, g);
-    CT_END(CT_VOCAB);
-    return;
-  }
-  if (!act) {
-    CT_END(CT_VOCAB);
-    return;
-  }
-  // lane holds rows mt*16 + r, columns tile*16 + 4g .. +3
-  const int n = tile * 16 + 4 * g;
-  const auto rs = wt_rsrc(a.out_f32);
-  // (no bias: the launcher requires none; a conditional bias load here made the compiler
-  // wait vmcnt(0) before every store — 28 serialized write-through stores, ~30 of 61 us)
-  const float4_t(&ov)[MT] = acc;
-  const bool full = n + 3 < a.N;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int m = mt * 16 + r;
-    if (m < a.M) {
-      if (full) {
-        // the lane's 4 columns as ONE 16-B write-through store (whole 64-B row segments per
-        // instruction): four 4-B stores per element took the epilogue 15.5 us, this 7.5
-        // (k_vocab_2p 49.5 -> 41.6 us at 100 rows, profiles/r05/ab_vocab_wide_stores.txt;
-        // rows of the odd-width logit matrix start 8-B aligned: buffer stores take any
-        // dword-aligned address)
-        wt_store4(rs, (m * a.ldo + n) * 4, ov[mt]);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (n + e < a.N) wt_store1(rs, (m * a.ldo + n + e) * 4, ov[mt][e]);
-      }
-    }
-  }
-  CT_END(CT_VOCAB);
-}
-
-// ============================================================ vocabulary projection, one pass over K
-// Round 6: k_vocab_2p's tiles, waves and k-step order with ONE pass
-// over K.  k_vocab_2p's first pass over K took ~22 us and its second ~9 whichever half went
-// first (profiles/r05/vocab_pass_order.txt): the first pulls whole 2560-B embedding rows
-// through the memory side and the second re-reads its half from there.  Here each wave
-// streams its 16 weight rows front to back once.  LDS holds X k-step-major: slot s =
-// [rows][32 halves] (64 B per row, a fragment read is 1 KB contiguous), 24 slots = k-steps
-// 0..23 staged up front; k-steps 24..39 refill slots 0..15 once every wave is past k-step
-// 15 (their loads issued a chunk earlier, ahead of that chunk's weight loads, so the LDS
-// writes wait on nothing the next MFMAs do not), with a second barrier before k-step 24.
-// Accumulation order per 16 x 16 block = ascending k-steps, as k_vocab_2p: bit-identical
-// logits.  Needs 24 x M x 64 B of LDS (M <= 106).  Measured: no faster than k_vocab_2p
-// (the weights stream at ~4.4 TB/s in both, profiles/r06/ab_vocab_1p_kco.txt) — the first
-// pass's ~22 us was the HBM stream, not a pass effect; tuning build only (WHISPER_HIP_V1P=1).  GATHER: rows of X named by a.x_rows (a
-// template choice: a wave-uniform pointer test per staging load made hipcc wait on each)
-constexpr int V1P_SLOTS = 24;
-template <int MT, bool GATHER>
-__global__ __launch_bounds__(1024) void k_vocab_1p(GemmArgs a) {
-  CT_MARK(CT_VOCAB, 0);
-  constexpr int NW = 16, VC = 4, DEPTH = 3, K = 1280, S = K / 32, SL = V1P_SLOTS, SR = S - SL, NCH = S / VC;
-  static_assert(S % VC == 0 && SR % VC == 0 && SR <= SL, "chunk / slot geometry");
-  constexpr int C_FREE = SR / VC;       // first chunk after the refilled slots' last use (k-steps 0..SR-1)
-  constexpr int C_REFILL = SL / VC;     // first chunk that reads refilled slots (k-step SL)
-  extern __shared__ __attribute__((aligned(16))) char xs1[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
-  const int M = a.M, slotB = M * 64;
-  const int nt = (a.N + 15) / 16;
-  const int t0 = range_split(blockIdx.x, nt, gridDim.x), t1 = range_split(blockIdx.x + 1, nt, gridDim.x);
-  const int tile = t0 + wave;
-  const bool act = tile < t1;
-  const half_t* X = reinterpret_cast<const half_t*>(a.X);
-  const int* const xrows = a.x_rows;
-  const half_t* wrow = reinterpret_cast<const half_t*>(a.W) + (int64_t)min(tile * 16 + r, a.N - 1) * K + 8 * g;
-  float4_t acc[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) acc[mt] = (float4_t){0.f, 0.f, 0.f, 0.f};
-  Frag<half_t> wbuf[DEPTH][VC];
-  auto load_chunk = [&](int c, Frag<half_t>(&wf)[VC]) {
-    const half_t* wp = wrow + c * VC * 32;
-#pragma unroll
-    for (int u = 0; u < VC; ++u) frag_load_stream(wf[u], wp + u * 32);
-  };
-  // chunk i of a k-step range: (k-step ks0 + i / (M*4), row, 16-B column) <- X (32-bit
-  // buffer offsets: one register per in-flight chunk, not a 64-bit address pair)
-  const auto rx = wt_rsrc(X);
-  auto src = [&](Frag<half_t>& f, int ks0, int i) {
-    const int kk = i / (M * 4), rem = i - kk * M * 4, row = rem >> 2, col = rem & 3;
-    const int xr = GATHER ? xrows[row] : row;
-    frag_load_buf(f, rx, (xr * a.ldx + (ks0 + kk) * 32 + col * 8) * 2);
-  };
-  if (act) {
-#pragma unroll
-    for (int c = 0; c < DEPTH - 1; ++c) load_chunk(c, wbuf[c]);
-  }
-  {
-    constexpr int SU = (106 * SL * 4 + 1023) / 1024;
-    const int tot = M * SL * 4;
-    Frag<half_t> tmp[SU];
-#pragma unroll
-    for (int u = 0; u < SU; ++u) src(tmp[u], 0, min(tid + 1024 * u, tot - 1));
-#pragma unroll
-    for (int u = 0; u < SU; ++u) {
-      const int i = tid + 1024 * u;
-      if (i < tot) *reinterpret_cast<half8_t*>(xs1 + i * 16) = tmp[u].v;  // slot kk, row, col: i * 16
-    }
-  }
-  __syncthreads();
-  // the refill in two parts (the whole refill live across a chunk's MFMAs spilled at MT 7):
-  // part j's loads issued at chunk C_FREE - 1 + j ahead of that chunk's weight loads, its LDS
-  // writes at chunk C_FREE + j (part 0 after the barrier that frees the slots)
-  constexpr int RU = (106 * SR * 4 + 1023) / 1024, RU0 = (RU + 1) / 2;
-  static_assert(C_FREE + 1 < C_REFILL, "two refill parts between the barriers");
-  const int rtot = M * SR * 4;
-  Frag<half_t> rf[RU0];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int u0 = j ? RU0 : 0, u1 = j ? RU : RU0;
-      if (c == C_FREE + j) {
-        if (j == 0) __syncthreads();  // every wave is past k-step SR - 1: slots 0..SR-1 are free
-#pragma unroll
-        for (int u = u0; u < u1; ++u) {
-          const int i = tid + 1024 * u;
-          if (i < rtot) *reinterpret_cast<half8_t*>(xs1 + i * 16) = rf[u - u0].v;
-        }
-      }
-      if (c == C_FREE - 1 + j) {
-#pragma unroll
-        for (int u = u0; u < u1; ++u) src(rf[u - u0], SL, min(tid + 1024 * u, rtot - 1));
-      }
-    }
-    if (c == C_REFILL) __syncthreads();  // the refilled slots written
-    if (act) {
-      if (c + DEPTH - 1 < NCH) load_chunk(c + DEPTH - 1, wbuf[(c + DEPTH - 1) % DEPTH]);
-#pragma unroll
-      for (int u = 0; u < VC; ++u) {
-        const int ks = c * VC + u, slot = ks < SL ? ks : ks - SL;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          Frag<half_t> xf;
-          frag_load(xf, reinterpret_cast<const half_t*>(xs1 + slot * slotB + min(mt * 16 + r, M - 1) * 64 + 16 * g));
-          mfma_step(acc[mt], wbuf[c % DEPTH][u], xf);
-        }
-      }
-    }
-  }
-  CT_MARK(CT_VOCAB, 1);  // the MFMAs issued: the epilogue starts
-  vocab_store_tr<MT, NW>(a, acc, reinterpret_cast<float*>(xs1), t0, t1, act, tid, wave, r, g);
+  // the epilogue through LDS, one 1-KB row segment per store instruction: 41.7 / 42.0 ->
+  // 37.4 / 37.4 us at 100 rows against 16-B stores per lane (profiles/r05/ab_vocab_epilogue_lds.txt)
+  vocab_store_tr<MT, NW>(a, acc, reinterpret_cast<float*>(xs2), t0, t1, act, tid, wave, r, g);
   CT_END(CT_VOCAB);
 }
 
@@ -1226,11 +1083,7 @@ int launch_gemm_tiles(const GemmArgs& a, int epi, int tile_sel, hipStream_t st);
 
 template <typename T>
 int launch_gemm(const GemmArgs& a, int epi, hipStream_t st) {
-  static const int tile_sel = [] {  // WHISPER_HIP_GEMM=128 keeps the 128x128 kernel (A/B)
-    const char* e = tune_env("WHISPER_HIP_GEMM");
-    return e ? atoi(e) : 256;
-  }();
-  return launch_gemm_tiles<T>(a, epi, tile_sel, st);
+  return launch_gemm_tiles<T>(a, epi, 256, st);
 }
 
 template <typename T>
@@ -1342,51 +1195,16 @@ int launch_gemm_tiles(const GemmArgs& a, int epi, int tile_sel, hipStream_t st) 
     if (sizeof(T) == 2 && vocab_small && epi == EPI_F32_COLS && !a.bias && a.N >= 16384 && a.M > 32 && a.M <= 112 &&
         !a.xf32 &&
         a.K == 1280 && a.M * (a.K + 16) <= 150 * 1024) {
-      // two 4-step weight chunks in flight per wave (DEPTH 3; WHISPER_HIP_V2P_DEPTH=2 in the
-      // tuning build: one 5-step chunk) — step graph 3.5456 -> 3.5413 ms at 20 windows,
-      // profiles/r03/step_tail_ab.txt
-      const char* de = tune_env("WHISPER_HIP_V2P_DEPTH");
-      const bool d3 = !(de && de[0] == '2');
-      // the epilogue through LDS, one 1-KB row segment per store instruction: 41.7 / 42.0 ->
-      // 37.4 / 37.4 us at 100 rows, step graph 3.244 / 3.251 -> 3.237 / 3.238 ms
-      // (profiles/r05/ab_vocab_epilogue_lds.txt).  Tuning: WHISPER_HIP_V2P_TR=0 -> per lane
-      const char* te = tune_env("WHISPER_HIP_V2P_TR");
-      const bool tr = !(te && te[0] == '0');
       const int nt = (a.N + 15) / 16;
       const int grid = std::max((nt + 15) / 16, std::min(256, nt));
-      const int lds = a.M * (a.K + 16);  // rows x (K / 2 halves x 2 B + 16)
-      // tuning build, WHISPER_HIP_V1P=1: k_vocab_1p (one pass over K) when its 24 k-step
-      // slots fit (M <= 106).  Measured equal: weights-in to epilogue start ~30 us either way
-      // (20 windows: step 3.186 / 3.187 ms at 12 tokens, profiles/r06/ab_vocab_1p_kco.txt)
-      const char* v1e = tune_env("WHISPER_HIP_V1P");
-      const bool v1p = v1e && v1e[0] == '1' && tr && V1P_SLOTS * a.M * 64 <= 160 * 1024;
+      // rows x (K / 2 halves x 2 B + 16), or the epilogue's staged tiles (M x 1 KB + pad)
+      const int lds = std::max(a.M * (a.K + 16), a.M * (16 * 16 + 4) * 4);
       auto go = [&](auto mtc) {
         constexpr int MTV = decltype(mtc)::value;
-        if (v1p) {
-          const int lds1 = std::max(V1P_SLOTS * a.M * 64, a.M * (16 * 16 + 4) * 4);
-          static bool attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vocab_1p<MTV, true>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-                              hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vocab_1p<MTV, false>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-          if (!attr1) return -5;
-          if (a.x_rows) k_vocab_1p<MTV, true><<<grid, 1024, lds1, st>>>(a), wh_launched("k_vocab_1p");
-          else k_vocab_1p<MTV, false><<<grid, 1024, lds1, st>>>(a), wh_launched("k_vocab_1p");
-          return 0;
-        }
-        static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vocab_2p<MTV, 2>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-                           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vocab_2p<MTV, 3>),
+        static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vocab_2p<MTV>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
         if (!attr) return -5;
-        if (tr) {  // the LDS-transposed epilogue (needs the staged rows' LDS: M x 1 KB + pad)
-          static bool attr_t = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vocab_2p<MTV, 3, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-          if (!attr_t) return -5;
-          k_vocab_2p<MTV, 3, true><<<grid, 1024, std::max(lds, a.M * (16 * 16 + 4) * 4), st>>>(a), wh_launched("k_vocab_2p");
-          return 0;
-        }
-        if (d3) k_vocab_2p<MTV, 3><<<grid, 1024, lds, st>>>(a), wh_launched("k_vocab_2p");
-        else k_vocab_2p<MTV, 2><<<grid, 1024, lds, st>>>(a), wh_launched("k_vocab_2p");
+        k_vocab_2p<MTV><<<grid, 1024, lds, st>>>(a), wh_launched("k_vocab_2p");
         return 0;
       };
       switch ((a.M + 15) / 16) {
@@ -1400,17 +1218,9 @@ int launch_gemm_tiles(const GemmArgs& a, int epi, int tile_sel, hipStream_t st) 
     if (mt >= 3 && epi == EPI_F32_COLS && a.N >= 16384) {
       // vocabulary projection: NW column tiles share each staged X subchunk, so X
       // (re-read from L2 by every workgroup) costs 112/(16 NW) of the weight bytes
-      static const int nw = [] {
-        const char* e = tune_env("WHISPER_HIP_VOCAB_WAVES");
-        const int v = e ? atoi(e) : 8;
-        return v == 4 ? 4 : 8;  // 16 waves spill
-      }();
+      constexpr int nw = 8;  // (16 waves spill)
       dim3 gv((a.N + 16 * nw - 1) / (16 * nw), (a.M + 16 * rows_per - 1) / (16 * rows_per), 1);
-#define LAUNCHV(MT_)                                                                                  \
-  switch (nw) {                                                                                      \
-    case 4: k_gemv_x<T, MT_, EPI_F32_COLS, 4><<<gv, 256, 0, st>>>(a), wh_launched("k_gemv_x"); break;                         \
-    default: k_gemv_x<T, MT_, EPI_F32_COLS, 8><<<gv, 512, 0, st>>>(a), wh_launched("k_gemv_x"); break;                        \
-  }
+#define LAUNCHV(MT_) k_gemv_x<T, MT_, EPI_F32_COLS, nw><<<gv, 64 * nw, 0, st>>>(a), wh_launched("k_gemv_x");
       switch (rows_per) {
         case 3: LAUNCHV(3) break;
         case 4: LAUNCHV(4) break;
@@ -1429,16 +1239,7 @@ int launch_gemm_tiles(const GemmArgs& a, int epi, int tile_sel, hipStream_t st) 
     // batch-invariant like the step (fc1 used to switch to k_gemv_x from 33 rows)
     if (mt >= 3 && epi == EPI_PARTIAL) {
       dim3 gx((a.N + 63) / 64, (a.M + 16 * rows_per - 1) / (16 * rows_per), ks);
-#define LAUNCHX(MT_)                                                                            \
-  switch (epi) {                                                                               \
-    case EPI_STORE: k_gemv_x<T, MT_, EPI_STORE><<<gx, 256, 0, st>>>(a), wh_launched("k_gemv_x"); break;                  \
-    case EPI_STORE_GELU: k_gemv_x<T, MT_, EPI_STORE_GELU><<<gx, 256, 0, st>>>(a), wh_launched("k_gemv_x"); break;        \
-    case EPI_RESID: k_gemv_x<T, MT_, EPI_RESID><<<gx, 256, 0, st>>>(a), wh_launched("k_gemv_x"); break;                  \
-    case EPI_QKV_DEC: k_gemv_x<T, MT_, EPI_QKV_DEC><<<gx, 256, 0, st>>>(a), wh_launched("k_gemv_x"); break;              \
-    case EPI_F32_COLS: k_gemv_x<T, MT_, EPI_F32_COLS><<<gx, 256, 0, st>>>(a), wh_launched("k_gemv_x"); break;            \
-    case EPI_PARTIAL: k_gemv_x<T, MT_, EPI_PARTIAL><<<gx, 256, 0, st>>>(a), wh_launched("k_gemv_x"); break;              \
-    default: return -1;                                                                        \
-  }
+#define LAUNCHX(MT_) k_gemv_x<T, MT_, EPI_PARTIAL><<<gx, 256, 0, st>>>(a), wh_launched("k_gemv_x");
       switch (rows_per) {
         case 3: LAUNCHX(3) break;
         case 4: LAUNCHX(4) break;

@@ -13,27 +13,9 @@ void launch_layernorm(const float* x, T* y, const float* g, const float* b, int 
 // Split-K slabs of the decoder-step projections (k_proj EPI_PARTIAL) are fp32, or fp16 in
 // fp16 contexts (GemmArgs::slab_half): `part` then points at half_t
 // elements and slab_half is 1.  Strides count elements.
-// Round 6: an L2 prefetch ridden by a latency-bound launch for the NEXT launch of the same
-// stream.  Workgroup b of the carrying launch runs on XCD b % 8 (round-robin dispatch, as
-// xcd_remap assumes; speed only), and the workgroups on XCD x pull bytes [lo[x], hi[x]) x
-// unit of `base` into that XCD's L2 by LDS-DMA into a scratch block (no registers; the
-// carrying workgroup waits for them before it ends, so its LDS is never reallocated under
-// a transfer).  Used for the step cross-attention's W_q head slices (k_xattn_seg<qproj>):
-// read by 25 workgroups per XCD at once, they missed the L2 together and streamed from
-// memory at ~4 TB/s (profiles/r06/xattn_trace_xqv.txt).
-struct L2Prefetch {
-  const char* base = nullptr;
-  int64_t unit = 0;  // bytes per index (a W_q head slice: 64 rows x n)
-  int lo[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-};
 template <typename T>
 void launch_resid_ln(float* x, const float* part, int nsplit, int64_t part_stride, const float* bias, T* y,
-                     const float* g, const float* b, int rows, int n, float eps, hipStream_t st, int slab_half = 0,
-                     const L2Prefetch* pf = nullptr);
-// the per-XCD head ranges of k_xattn_seg<qproj>'s workgroups for a batch (same grid and
-// xcd_remap as launch_cross_attn): pf->lo / hi in heads; false when the grid is too small
-// for the per-XCD runs (fewer than 16 workgroups)
-bool xattn_l2_ranges(int nwin, int H, int max_rows, L2Prefetch* pf);
+                     const float* g, const float* b, int rows, int n, float eps, hipStream_t st, int slab_half = 0);
 template <typename T>
 void launch_attn_enc(const T* qkv, int ld, int ns, int H, int Tlen, int nwin, int64_t wsi, const T* vt, int tkp, T* out,
                      int64_t wso, hipStream_t st);
@@ -64,20 +46,11 @@ struct XQPart {
   float* split_rec = nullptr;
   int* split_cnt = nullptr;
   int max_pairs = 0;
-  // round 6: the query projected inside the step kernel (xattn_fused_q): q = qx qw^T + bias
-  // with qx the LayerNorm'd rows [rows][n] and qw = W_q [n][n] (T); q / part unused
+  // round 6: the query projected inside the step kernel (xattn_fused_q): q = qx W_q^T + bias
+  // with qx the LayerNorm'd rows [rows][n] (T) and qwf = W_q [n][n] (T) in fragment order
+  // (launch_wq_frag); q / part unused
   const void* qx = nullptr;
-  const void* qw = nullptr;
-  const void* qwf = nullptr;  // W_q in fragment order (launch_wq_frag), read instead of qw when set
-  // the single-window step (k_proj1 layers): qx is the fp32 residual rows and the kernel
-  // computes their LayerNorm (ln_g, ln_b, ln_eps) itself — no cross-q k_proj1 launch
-  const float* ln_g = nullptr;
-  const float* ln_b = nullptr;
-  float ln_eps = 1e-5f;
-  // ... with the projection split over the pair's workgroups (k_xattn_seg QV 6): the partial
-  // queries [pair][XQ1_P][4][64] float4 and per pair {arrivals, departures} (zero between launches)
-  float* q_part = nullptr;
-  int* q_cnt = nullptr;
+  const void* qwf = nullptr;
 };
 // the shapes the in-kernel query projection serves: fp16, n = 1280 (large-v3, turbo), <= 8
 // rows per window; the choice depends on the model and the beam group only, never on the
@@ -89,15 +62,10 @@ inline bool xattn_fused_q(int n, int rows_per_window, int elem_size) {
 // ((((h * 4 + c) * 2 + kh) * (n / 64) + s) * 64 + lane) holds row h * 64 + 16 c + (lane & 15),
 // columns kh * n / 2 + 32 s + 8 (lane >> 4) .. + 7 (a wave's k-step s is 1 KB contiguous)
 void launch_wq_frag(const void* w, void* f, int n, hipStream_t st);
-// round-6 probe (tuning build): pull a layer's cross K / V blocks of nwin windows (slots from
-// win_slot, slot_bytes each, a multiple of 32 KB) through the memory side; nwg one-wave workgroups
-void launch_kv_pull(const void* ck, const void* cv, const int* win_slot, int nwin, int64_t slot_bytes, int nwg,
-                    unsigned* sink, hipStream_t st);
 constexpr int XREC = 16 * 64 + 32;  // floats per segment record: O[16][64], m[16], l[16]
 // step cross-attention (k_xattn_seg): one softmax partial per 64-key tile, at most
 // XS_NSP tiles per (window, head) pair (Tk <= 1536), at most XS_QP pairs per workgroup
 constexpr int XS_NSP = 24;
-constexpr int XQ1_P = 8;  // workgroups per pair of the split single-window query projection (k_xattn_seg QV 6)
 constexpr int XS_QP = 4;
 int xattn_seg_grid(int npair, int nsp, int smax);
 inline bool cross_attn_q_slabs(int z) { return z == 4 || z == 8 || z == 10; }
@@ -178,19 +146,9 @@ struct MergeEmbed {
   int n = 0, pmax = 0, half = 0;
 };
 void launch_merge(const DecState& s, const DecOpts& o, int nwin, hipStream_t st, const MergeEmbed& em = MergeEmbed());
-// the single-window step's whole token tail (vocabulary projection with the final
-// LayerNorm, selection, merge) in one launch; -1 when the shape does not fit it
-struct GemmArgs;
-bool vocab_select_on();
-int self_attn_grp_mode();
-bool self_attn_pipe_on();
-bool self_attn_kco_on();  // the coalesced-K self-attention passes (round 6)
-int self_attn_kco_min();   // ... from this many cached keys on
-int launch_vocab_select(const GemmArgs& a, const DecState& s, const DecOpts& o, const MergeEmbed& em, float* rec,
-                        int* cnt, hipStream_t st);
-constexpr size_t VS_REC_FLOATS = 8 * 2 * 256 * 32;  // k_vocab_sel records [rows][part][workgroup][32]
+int self_attn_kco_min();  // fp16: the coalesced-K self-attention passes (round 6) run from this many cached keys on
 // token selection + candidate merge of one update: one k_logit_part launch whose last
-// row combiner of each window runs the merge (round 4), or k_logit_* then k_merge
+// row combiner of each window runs the merge (round 4), or the selection then k_merge
 void launch_select_merge(float* logits, int ldl, const DecState& s, const DecOpts& o, int nwin, hipStream_t st,
                          const MergeEmbed& em);
 // per-step ABI (wh_step / wh_reorder_kv): append host-chosen tokens, reorder rows

@@ -65,21 +65,22 @@ void launch_layernorm(const float* x, T* y, const float* g, const float* b, int 
 }
 
 // x[r] += bias + sum_s part[s][r] (fixed order: deterministic split-K reduction of the
-// residual GEMVs), then y = LayerNorm(x).  One 256-thread block per row; every load
-// of the row is issued before the first reduction (latency-bound at decode sizes).
-// PF (round 6): the workgroup also carries its share of an L2Prefetch (wh_kernels.h) for the
-// next launch, issued after its own loads (they return first) and waited for at its end.
-template <typename T, int NS, int MAXV = 2, typename S = float, bool PF = false>
+// residual GEMVs), then y = LayerNorm(x).  One block of ceil(n / 256) waves per row, one
+// float4 per thread (n <= 2048); every load of the row is issued before the first
+// reduction (latency-bound at decode sizes).
+template <typename T, int NS, typename S = float>
 __global__ __launch_bounds__(512) void k_resid_ln(float* __restrict__ x, const S* __restrict__ part, int nsplit,
                                                   int64_t part_stride, const float* __restrict__ bias,
                                                   T* __restrict__ y, const float* __restrict__ gamma,
-                                                  const float* __restrict__ beta, int n, float eps, L2Prefetch pf) {
+                                                  const float* __restrict__ beta, int n, float eps) {
   __shared__ float red[2][8];
-  __shared__ __attribute__((aligned(16))) char pf_sink[PF ? 1024 : 16];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, NT = blockDim.x, nwv = NT >> 6;
   CT_MARK(CT_RESID_LN, 0);
   float* xr = x + (int64_t)row * n;
-  // NT * 4 * MAXV >= n (n <= 2048): 256 threads x 2 float4, or ceil(n / 256) waves x 1
+  // NT * 4 >= n (n <= 2048): ceil(n / 256) waves, one float4 per thread.  The one-element
+  // arrays and their loops stay: as straight-line code the kernel compiled 40-48 B shorter and
+  // the 20-window step ran 1.2 % slower (96 launches per step; DESIGN.md "Removed variants")
+  constexpr int MAXV = 1;
   const int nv = n >> 2;
   float4_t v[MAXV], gm[MAXV], bt[MAXV];
 #pragma unroll
@@ -103,15 +104,6 @@ __global__ __launch_bounds__(512) void k_resid_ln(float* __restrict__ x, const S
         if (sp < nsplit) a += (float4_t){(float)pp[sp][0], (float)pp[sp][1], (float)pp[sp][2], (float)pp[sp][3]};
       v[i] = a;
     }
-  }
-  if constexpr (PF) {
-    // this workgroup's share of its XCD's byte range, in 1 KB blocks dealt to its waves
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, m = ((int)gridDim.x - xcd + 7) >> 3;
-    const int64_t b0 = pf.lo[xcd] * pf.unit, nb = (pf.hi[xcd] - pf.lo[xcd]) * pf.unit / 1024;
-    const int64_t k0 = nb * idx / m, k1 = nb * (idx + 1) / m;
-    for (int64_t k = k0 + wv; k < k1; k += nwv)
-      __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(pf.base + b0 + k * 1024 + lane * 16),
-                                       (__attribute__((address_space(3))) void*)(pf_sink), 16, 0, 0);
   }
   float s = 0.f;
 #pragma unroll
@@ -151,41 +143,29 @@ __global__ __launch_bounds__(512) void k_resid_ln(float* __restrict__ x, const S
       store4(yr + 4 * c, (v[i][0] - mean) * rstd * gm[i][0] + bt[i][0], (v[i][1] - mean) * rstd * gm[i][1] + bt[i][1],
              (v[i][2] - mean) * rstd * gm[i][2] + bt[i][2], (v[i][3] - mean) * rstd * gm[i][3] + bt[i][3]);
   }
-  if constexpr (PF) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA outlives the workgroup
   CT_END(CT_RESID_LN);
 }
 
-
 template <typename T>
 void launch_resid_ln(float* x, const float* part, int nsplit, int64_t part_stride, const float* bias, T* y,
-                     const float* g, const float* b, int rows, int n, float eps, hipStream_t st, int slab_half,
-                     const L2Prefetch* pf) {
+                     const float* g, const float* b, int rows, int n, float eps, hipStream_t st, int slab_half) {
   if (rows <= 0) return;
-  const L2Prefetch none;
-  // one float4 per thread (n <= 2048; 1280: 5 waves); tuning builds WHISPER_HIP_RLN_256=1
-  // for the round-3 form (256 threads, up to two float4 each)
-  const char* e = tune_env("WHISPER_HIP_RLN_256");
-  const int nt = (e && atoi(e) == 1) ? 256 : ((n >> 2) + 63) / 64 * 64;
-  if (slab_half && nsplit > 0 && nt != 256) {  // fp16 slabs (fp16 contexts, k_proj)
-    const half_t* ph = reinterpret_cast<const half_t*>(part);
-    if (pf && pf->base) {
-      if (nsplit <= 4) k_resid_ln<T, 4, 1, half_t, true><<<rows, nt, 0, st>>>(x, ph, nsplit, part_stride, bias, y, g, b, n, eps, *pf), wh_launched("k_resid_ln<pf>");
-      else k_resid_ln<T, 16, 1, half_t, true><<<rows, nt, 0, st>>>(x, ph, nsplit, part_stride, bias, y, g, b, n, eps, *pf), wh_launched("k_resid_ln<pf>");
-      return;
+  const int nt = ((n >> 2) + 63) / 64 * 64;  // one float4 per thread (n <= 2048; 1280: 5 waves)
+  if (slab_half && nsplit > 0) {  // fp16 slabs (k_proj in fp16 contexts)
+    if constexpr (sizeof(T) == 2) {
+      const half_t* ph = reinterpret_cast<const half_t*>(part);
+      if (nsplit <= 4) k_resid_ln<T, 4, half_t><<<rows, nt, 0, st>>>(x, ph, nsplit, part_stride, bias, y, g, b, n, eps), wh_launched("k_resid_ln");
+      else k_resid_ln<T, 16, half_t><<<rows, nt, 0, st>>>(x, ph, nsplit, part_stride, bias, y, g, b, n, eps), wh_launched("k_resid_ln");
+    } else {
+      wh_set_launch_error("launch_resid_ln: fp16 slabs in an fp32 context");
     }
-    if (nsplit <= 4) k_resid_ln<T, 4, 1, half_t><<<rows, nt, 0, st>>>(x, ph, nsplit, part_stride, bias, y, g, b, n, eps, none), wh_launched("k_resid_ln");
-    else k_resid_ln<T, 16, 1, half_t><<<rows, nt, 0, st>>>(x, ph, nsplit, part_stride, bias, y, g, b, n, eps, none), wh_launched("k_resid_ln");
     return;
   }
-#define RLN(NS_, MV_) \
-  k_resid_ln<T, NS_, MV_><<<rows, nt, 0, st>>>(x, part, NS_ ? nsplit : 0, part_stride, bias, y, g, b, n, eps, none), wh_launched("k_resid_ln")
-  if (nsplit <= 0) {
-    if (nt == 256) RLN(0, 2); else RLN(0, 1);
-  } else if (nsplit <= 4) {
-    if (nt == 256) RLN(4, 2); else RLN(4, 1);
-  } else {
-    if (nt == 256) RLN(16, 2); else RLN(16, 1);
-  }
+#define RLN(NS_) \
+  k_resid_ln<T, NS_><<<rows, nt, 0, st>>>(x, part, NS_ ? nsplit : 0, part_stride, bias, y, g, b, n, eps), wh_launched("k_resid_ln")
+  if (nsplit <= 0) RLN(0);
+  else if (nsplit <= 4) RLN(4);
+  else RLN(16);
 #undef RLN
 }
 
@@ -426,10 +406,8 @@ WH_DEV void kco_pass(const float (&qd8)[8], const Frag<T> (&k)[NU], const Frag<T
 // One wave per (row, head).  Keys = positions 0..pos of the row's sequence; position
 // p < pos lives in beam slot anc[win][slot][p] (beam reorder by index indirection,
 // no KV copies), position pos in the row's own slot.  Cache: [win][slot][head][ctx][64].
-// PIPE (fp16, round 4): 64-key passes with the next pass's loads in flight, as
-// k_self_attn_qkv<T, true>.  KCO (fp16, round 6): the 128-key passes with K read like V
-// (kco_pass)
-template <typename T, bool PIPE = false, bool KCO = false>
+// fp16 (round 6): from kco_min keys on, the 128-key passes with K read like V (kco_pass)
+template <typename T>
 __global__ __launch_bounds__(64) void k_self_attn(const T* __restrict__ q, int ldq, const T* __restrict__ kc,
                                                   const T* __restrict__ vc, const int* __restrict__ row_win,
                                                   const int* __restrict__ row_slot, const int* __restrict__ row_pos,
@@ -462,82 +440,7 @@ __global__ __launch_bounds__(64) void k_self_attn(const T* __restrict__ q, int l
   constexpr int TB = (int)sizeof(T), ROWB = 64 * TB;
   const int slotB = H * ctx * ROWB, baseB = ((int)wbase * H + h) * ctx * ROWB;
   const auto rk = wt_rsrc(kc), rv = wt_rsrc(vc);
-  if constexpr (sizeof(T) == 2 && PIPE) {
-    int sv[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sv[i] = an[min(lane + 64 * i, ctx - 1)];
-    qs[lane] = to_f32(q_lane);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int pp = lane + 64 * i;
-      if (pp <= pos) slot_of[pp] = (pp == pos ? sl : sv[i]) * slotB;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // one wave: its own LDS writes
-    unpack_q();
-    const int kg = lane >> 3, dc = (lane & 7) * 8;
-    float m = -INFINITY, lsum = 0.f, o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = 0.f;
-    auto load = [&](int p0, Frag<T>(&k)[8], Frag<T>(&v)[8]) {
-      const int pa = min(p0 + lane, pos);
-      const int ra = baseB + slot_of[pa] + pa * ROWB;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) frag_load_buf(k[c], rk, ra + 8 * c * TB);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int pc = min(p0 + kg + 8 * u, pos);
-        frag_load_buf(v[u], rv, baseB + slot_of[pc] + pc * ROWB + dc * TB);
-      }
-    };
-    auto pass = [&](int p0, const Frag<T>(&k)[8], const Frag<T>(&v)[8]) {
-      float sa = 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sa += qv[8 * c + e] * to_f32(k[c].v[e]);
-      const bool va = p0 + lane <= pos;
-      const float mp = wave_max(va ? sa : -INFINITY);
-      const float mn = fmaxf(m, mp), scale = __expf(m - mn);
-      m = mn;
-      const float ea = va ? __expf(sa - m) : 0.f;
-      lsum = lsum * scale + wave_sum(ea);
-      sc[lane] = ea;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] *= scale;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const float pw = sc[kg + 8 * u];  // 0 past the end
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] += pw * to_f32(v[u].v[e]);
-      }
-    };
-    Frag<T> ka[8], va[8], kb[8], vb[8];
-    load(0, ka, va);
-    int p0 = 0;
-    for (; p0 + 64 <= pos; p0 += 128) {
-      load(p0 + 64, kb, vb);
-      pass(p0, ka, va);
-      if (p0 + 128 <= pos) load(p0 + 128, ka, va);
-      pass(p0 + 64, kb, vb);
-    }
-    if (p0 <= pos) pass(p0, ka, va);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      o[e] = xor8_sum(o[e]);
-      o[e] = xor16_sum(o[e]);
-      o[e] = xor32_sum(o[e]);
-    }
-    if (kg == 0) {
-      const float inv = 1.f / lsum;
-      T* op = out + (int64_t)row * ldo + h * 64 + dc;
-      store4(op, o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv);
-      store4(op + 4, o[4] * inv, o[5] * inv, o[6] * inv, o[7] * inv);
-    }
-    CT_END(CT_SELF_ATTN);
-    return;
-  }
-  if constexpr (sizeof(T) == 2 && KCO) {
+  if constexpr (sizeof(T) == 2) {
     if (pos + 1 > kco_min) {  // (one 128-key pass below: the lane-per-key form)
       int sv[8];
 #pragma unroll
@@ -739,25 +642,8 @@ void launch_self_attn(const T* q, int ldq, const T* kc, const T* vc, const int* 
                       const int* anc, int anc_beams, int nbeam, int H, int ctx, T* out, int ldo, int rows,
                       hipStream_t st) {
   if (rows <= 0) return;
-  // tuning build only (WHISPER_HIP_SA_PIPE1=1): the pipelined 64-key passes at one window
-  // measured p50 1.670 -> 1.679 ms per token (profiles/r04/self_attn_pipe_ab.txt): not kept
-  static const bool pipe = [] {
-    const char* e = tune_env("WHISPER_HIP_SA_PIPE1");
-    return e && e[0] == '1';
-  }();
-  if constexpr (sizeof(T) == 2) {
-    if (self_attn_kco_on()) {
-      k_self_attn<T, false, true><<<dim3(rows, H), 64, 0, st>>>(q, ldq, kc, vc, rw, rs, rp, anc, anc_beams, nbeam, H,
-                                                                ctx, out, ldo, self_attn_kco_min()), wh_launched("k_self_attn");
-      return;
-    }
-    if (pipe) {
-      k_self_attn<T, true><<<dim3(rows, H), 64, 0, st>>>(q, ldq, kc, vc, rw, rs, rp, anc, anc_beams, nbeam, H, ctx, out,
-                                                         ldo), wh_launched("k_self_attn");
-      return;
-    }
-  }
-  k_self_attn<T><<<dim3(rows, H), 64, 0, st>>>(q, ldq, kc, vc, rw, rs, rp, anc, anc_beams, nbeam, H, ctx, out, ldo), wh_launched("k_self_attn");
+  k_self_attn<T><<<dim3(rows, H), 64, 0, st>>>(q, ldq, kc, vc, rw, rs, rp, anc, anc_beams, nbeam, H, ctx, out, ldo,
+                                               self_attn_kco_min()), wh_launched("k_self_attn");
 }
 
 // Step-mode variant: the QKV projection arrives as split-K fp32 partial slabs
@@ -771,17 +657,17 @@ void launch_self_attn(const T* q, int ldq, const T* kc, const T* vc, const int* 
 // position) rows, run on one XCD and share its L2 (x-fastest order put them on G
 // different XCDs).
 //
-// PIPE (fp16, round 4): passes of 64 keys, the NEXT pass's K and V loads issued before
+// fp16 (round 4): passes of 64 keys, the NEXT pass's K and V loads issued before
 // the current pass is computed (two register buffers of 8 K + 8 V fragments), q read from
 // LDS: at long contexts the passes' round trips overlap instead of adding up (the step's
 // growth over the decode is those round trips, profiles/r04/self_attn_grp64_ab.txt).
-// PIPE 3 (round 6): the PIPE 1 passes with K read like V — lane (kg, dc) holds the 16-B
+// From kco_min cached keys on (round 6) the passes read K like V — lane (kg, dc) holds the 16-B
 // chunk dc of keys kg + 8u, eight lanes per 128-B key row — so one load instruction covers
 // 8 whole rows (the lane-per-key form touched 64 rows, 16 B of each, per instruction, and
 // the rows' other chunks came back by later instructions from wherever the lines still
 // were).  A key's score is its 8 chunk partials summed across the group's lanes (DPP) and
 // lands in the lanes whose V chunks it weights: no LDS hand-off of the probabilities.
-template <typename T, int PIPE = 0, typename S = float>
+template <typename T, typename S = float>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_self_attn_qkv(const S* __restrict__ part, int nsplit, int64_t part_stride,
                                                       const float* __restrict__ bqkv, int ns, T* __restrict__ kc,
                                                       T* __restrict__ vc, const int* __restrict__ row_win,
@@ -860,7 +746,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
   // the block is one wave: its LDS writes are visible to all its lanes once they have
   // completed (no barrier, and no wait for the K/V row stores above)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if constexpr (sizeof(T) == 2 && PIPE) {
+  if constexpr (sizeof(T) == 2) {
     const int kg = lane >> 3, dc = (lane & 7) * 8;
     float m = s_cur, lsum = 0.f, o[8];
 #pragma unroll
@@ -922,45 +808,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
         for (int e = 0; e < 8; ++e) o[e] += pw * to_f32(v[u].v[e]);
       }
     };
-    // the coalesced-K passes (PIPE 3) from kco_min cached keys on: below that (one pass)
+    // the coalesced-K passes from kco_min cached keys on: below that (one pass)
     // the lane-per-key form measured faster (20-window step 3.186 -> 3.198 ms at 12
     // tokens, 3.475 -> 3.448 at 162, profiles/r06/ab_self_attn_kco.txt)
     auto run = [&](auto kc) {
       Frag<T> ka[8], va[8], kb[8], vb[8];
       if (pos > 0) load(kc, 0, ka, va);
       int p0 = 0;
-      if constexpr (PIPE == 2) {
-        // two passes in flight ahead of the one computed (three register sets, <= 256
-        // VGPRs: still two waves per SIMD, every (row, head) wave resident at once); the
-        // passes are computed in the same order, so the result is bit-identical to PIPE 1
-        Frag<T> kx[8], vx[8];
-        if (pos > 64) load(kc, 64, kb, vb);
-        for (; p0 + 128 < pos; p0 += 192) {
-          load(kc, p0 + 128, kx, vx);
-          pass(kc, p0, ka, va);
-          if (p0 + 192 < pos) load(kc, p0 + 192, ka, va);
-          pass(kc, p0 + 64, kb, vb);
-          if (p0 + 256 < pos) load(kc, p0 + 256, kb, vb);
-          pass(kc, p0 + 128, kx, vx);
-        }
-        if (p0 < pos) pass(kc, p0, ka, va);
-        if (p0 + 64 < pos) pass(kc, p0 + 64, kb, vb);
-      } else {
-        for (; p0 + 64 < pos; p0 += 128) {
-          load(kc, p0 + 64, kb, vb);
-          pass(kc, p0, ka, va);
-          if (p0 + 128 < pos) load(kc, p0 + 128, ka, va);
-          pass(kc, p0 + 64, kb, vb);
-        }
-        if (p0 < pos) pass(kc, p0, ka, va);
+      for (; p0 + 64 < pos; p0 += 128) {
+        load(kc, p0 + 64, kb, vb);
+        pass(kc, p0, ka, va);
+        if (p0 + 128 < pos) load(kc, p0 + 128, ka, va);
+        pass(kc, p0 + 64, kb, vb);
       }
+      if (p0 < pos) pass(kc, p0, ka, va);
     };
-    if constexpr (PIPE == 3) {
-      if (pos > kco_min) run(std::true_type());
-      else run(std::false_type());
-    } else {
-      run(std::false_type());
-    }
+    if (pos > kco_min) run(std::true_type());
+    else run(std::false_type());
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       o[e] = xor8_sum(o[e]);
@@ -981,71 +845,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
   float qv[64];
 #pragma unroll
   for (int c = 0; c < 64; ++c) qv[c] = qs[c];
-  if constexpr (sizeof(T) == 2) {
-    // passes of 128 cached keys, K and V of the pass in ONE round trip (V's addresses do
-    // not depend on the scores), online softmax across passes: K rows lane per key (two
-    // keys per lane), V lane = (key group kg, 16 B chunk dc) keys kg, kg+8, .. kg+120
-    const int kg = lane >> 3, dc = (lane & 7) * 8;
-    float m = s_cur, lsum = 0.f, o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = 0.f;
-    for (int p0 = 0; p0 < pos; p0 += 128) {
-      const int pa = min(p0 + lane, plast), pb = min(p0 + 64 + lane, plast);
-      const int ra = baseB + slot_of[pa] + pa * ROWB, rb = baseB + slot_of[pb] + pb * ROWB;
-      Frag<T> ka[8], kb[8], vf[16];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) frag_load_buf(ka[c], rk, ra + 8 * c * TB);
-#pragma unroll
-      for (int c = 0; c < 8; ++c) frag_load_buf(kb[c], rk, rb + 8 * c * TB);
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int pc = min(p0 + kg + 8 * u, plast);
-        frag_load_buf(vf[u], rv, baseB + slot_of[pc] + pc * ROWB + dc * TB);
-      }
-      __builtin_amdgcn_sched_barrier(0);  // every load of the pass ahead of the math
-      float sa = 0.f, sb = 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          sa += qv[8 * c + e] * to_f32(ka[c].v[e]);
-          sb += qv[8 * c + e] * to_f32(kb[c].v[e]);
-        }
-      const bool va = p0 + lane < pos, vb = p0 + 64 + lane < pos;
-      const float mp = wave_max(fmaxf(va ? sa : -INFINITY, vb ? sb : -INFINITY));
-      const float mn = fmaxf(m, mp), scale = __expf(m - mn);
-      m = mn;
-      const float ea = va ? __expf(sa - m) : 0.f, eb = vb ? __expf(sb - m) : 0.f;
-      lsum = lsum * scale + wave_sum(ea + eb);
-      sc[lane] = ea;
-      sc[64 + lane] = eb;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] *= scale;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const float pw = sc[kg + 8 * u];  // 0 past the end
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] += pw * to_f32(vf[u].v[e]);
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      o[e] = xor8_sum(o[e]);
-      o[e] = xor16_sum(o[e]);
-      o[e] = xor32_sum(o[e]);
-    }
-    if (kg == 0) {
-      const float e_cur = __expf(s_cur - m), inv = 1.f / (lsum + e_cur);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (o[e] + e_cur * vs[dc + e]) * inv;
-      T* op = out + (int64_t)row * ldo + h * 64 + dc;
-      store4(op, o[0], o[1], o[2], o[3]);
-      store4(op + 4, o[4], o[5], o[6], o[7]);
-    }
-    CT_END(CT_SELF_ATTN);
-    return;
-  }
   // fp32 (parity context): scores of the cached positions p < pos: lane per key, two
   // keys per lane per pass with all 16 row loads in flight (clamped addresses, no branch
   // around a load), then P.V
@@ -1124,219 +923,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
   CT_END(CT_SELF_ATTN);
 }
 
-// Grouped form (fp16, a window's G <= 8 beams as the G waves of one workgroup per
-// (window, head)).  Per wave the arithmetic is k_self_attn_qkv's fp16 path operation for
-// operation (same passes of 128 keys, same lane roles and orders: bit-identical outputs);
-// only where the cached K / V rows come from changes.  Beam histories form a tree: beam b
-// names beam 0's (slot, position) rows exactly on [0, d_b), d_b = the first position where
-// their ancestries differ, and never again after it.  So each pass stages beam 0's 128 K
-// and V rows in LDS once (global_load_lds, 32 KB shared by the G waves) and a lane reads a
-// key from LDS below its beam's d_b and from HBM at or above it (profiles/ancestry_probe.py:
-// at 20 windows the beams share 37-97 % of their context, 1.1-2.4 distinct rows per
-// position, where every wave streamed its own rows).  K rows are stored with their 16 B
-// chunks XOR-swizzled by (row >> 1) & 7, so lane-per-row reads of a chunk are conflict-free.
-WH_DEV void sa_glds16(const void* src, void* lds) {
-  __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(src),
-                                   (__attribute__((address_space(3))) void*)(lds), 16, 0, 0);
-}
-
-constexpr int SA_GMAX = 8;
-// PK keys per pass: 128 (k_self_attn_qkv's passes, bit-identical) or 64 (half the register
-// buffers: at <= 168 VGPRs two 5-wave workgroups share a CU, so the 400 (window, head)
-// workgroups of 20 windows run in one round; its own passes, so its own bits)
-template <typename T, int PK>
-__global__ __launch_bounds__(64 * SA_GMAX) void k_self_attn_grp(const float* __restrict__ part, int nsplit,
-                                                                 int64_t part_stride, const float* __restrict__ bqkv,
-                                                                 int ns, T* __restrict__ kc, T* __restrict__ vc,
-                                                                 const int* __restrict__ row_pos,
-                                                                 const int* __restrict__ anc, int G, int nbeam, int H,
-                                                                 int ctx, T* __restrict__ out, int ldo) {
-  static_assert(sizeof(T) == 2, "fp16 path");
-  static_assert(PK == 128 || PK == 64, "keys per pass");
-  constexpr int NKI = PK / 8;  // glds instructions of 8 rows per K (and per V) stage
-  constexpr int VU = PK / 8;   // V rows per lane per pass
-  __shared__ __attribute__((aligned(1024))) T kref[PK * 64];
-  __shared__ __attribute__((aligned(1024))) T vref[PK * 64];
-  __shared__ int slot_of[SA_GMAX][512];
-  __shared__ __attribute__((aligned(16))) float qs[SA_GMAX][64], vs[SA_GMAX][64], sc[SA_GMAX][PK];
-  const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const int h = blockIdx.x % H, w = blockIdx.x / H, row = w * G + sl;
-  const int* an = anc + ((int64_t)w * G + sl) * ctx;
-  const int64_t head_stride = (int64_t)ctx * 64;
-  const int64_t wbase = (int64_t)w * nbeam;
-  auto kv_off = [&](int slot, int p) -> int64_t { return ((wbase + slot) * H + h) * head_stride + (int64_t)p * 64; };
-  // the prologue of k_self_attn_qkv (one round trip: position, ancestry, q/k/v slabs)
-  const int pos = row_pos[row];
-  int sv[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) sv[i] = an[min(lane + 64 * i, ctx - 1)];
-  float qd, kd, vd;
-  {
-    const float* pr = part + (int64_t)row * 3 * ns + h * 64 + lane;
-    float a0[16], a1[16], a2[16];
-#pragma unroll
-    for (int z = 0; z < 16; ++z)
-      if (z < nsplit) {
-        a0[z] = pr[z * part_stride];
-        a1[z] = pr[z * part_stride + ns];
-        a2[z] = pr[z * part_stride + 2 * ns];
-      }
-    qd = bqkv[h * 64 + lane];
-    kd = bqkv[ns + h * 64 + lane];
-    vd = bqkv[2 * ns + h * 64 + lane];
-#pragma unroll
-    for (int z = 0; z < 16; ++z)
-      if (z < nsplit) {
-        qd += a0[z];
-        kd += a1[z];
-        vd += a2[z];
-      }
-  }
-  for (int i = 0; i < 8; ++i)
-    if (lane + 64 * i < pos) slot_of[sl][lane + 64 * i] = sv[i];
-  const int plast = max(pos - 1, 0);
-  const T qT = from_f32<T>(qd), kT = from_f32<T>(kd), vT = from_f32<T>(vd);
-  kc[kv_off(sl, pos) + lane] = kT;
-  vc[kv_off(sl, pos) + lane] = vT;
-  qs[sl][lane] = to_f32(qT);
-  vs[sl][lane] = to_f32(vT);
-  const float s_cur = wave_sum(to_f32(qT) * to_f32(kT));
-  __syncthreads();  // every beam's ancestry in LDS
-  // d: the first position where this beam's ancestry leaves beam 0's
-  int d = pos;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int p = lane + 64 * i;
-    if (p < pos && slot_of[sl][p] != slot_of[0][p]) d = min(d, p);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) d = min(d, __shfl_xor(d, o, 64));
-  // q stays in LDS (broadcast reads in the dot products: 64 VGPRs fewer than a register copy)
-  const int kg = lane >> 3, dc = (lane & 7) * 8;
-  float m = s_cur, lsum = 0.f, o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = 0.f;
-  for (int p0 = 0; p0 < pos; p0 += PK) {
-    // beam 0's rows p0 .. p0 + PK - 1 (< pos) -> LDS: PK / 8 K and PK / 8 V instructions of
-    // 8 rows, dealt over the G waves; lane (row r0 + lane / 8, chunk lane % 8)
-    for (int i = sl; i < 2 * NKI; i += G) {
-      const int r0 = (i % NKI) * 8, r = r0 + (lane >> 3), p = p0 + r;
-      if (p <= plast) {
-        const int pc = lane & 7;
-        if (i < NKI) {  // K: physical chunk pc holds logical chunk pc ^ ((r >> 1) & 7)
-          sa_glds16(kc + kv_off(slot_of[0][p], p) + 8 * (pc ^ ((r >> 1) & 7)), kref + r0 * 64);
-        } else {
-          sa_glds16(vc + kv_off(slot_of[0][p], p) + 8 * pc, vref + r0 * 64);
-        }
-      }
-    }
-    // this beam's own rows at or past d, straight from HBM into registers
-    const int pa = min(p0 + lane, plast), pb = min(p0 + 64 + lane, plast);
-    const bool la = pa < d, lb = pb < d;
-    Frag<T> ka[8], kb[PK == 128 ? 8 : 1], vf[VU];
-    if (!la) {
-      const T* ra = kc + kv_off(slot_of[sl][pa], pa);
-#pragma unroll
-      for (int c = 0; c < 8; ++c) frag_load(ka[c], ra + 8 * c);
-    }
-    if constexpr (PK == 128) {
-      if (!lb) {
-        const T* rb = kc + kv_off(slot_of[sl][pb], pb);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) frag_load(kb[c], rb + 8 * c);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < VU; ++u) {
-      const int pc = min(p0 + kg + 8 * u, plast);
-      if (pc >= d) frag_load(vf[u], vc + kv_off(slot_of[sl][pc], pc) + dc);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // the staged rows of every wave
-    if (la) {
-      const int r = pa - p0, sw = (r >> 1) & 7;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) ka[c].v = *reinterpret_cast<const half8_t*>(kref + r * 64 + 8 * (c ^ sw));
-    }
-    if constexpr (PK == 128) {
-      if (lb) {
-        const int r = pb - p0, sw = (r >> 1) & 7;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) kb[c].v = *reinterpret_cast<const half8_t*>(kref + r * 64 + 8 * (c ^ sw));
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < VU; ++u) {
-      const int pc = min(p0 + kg + 8 * u, plast);
-      if (pc < d) vf[u].v = *reinterpret_cast<const half8_t*>(vref + (pc - p0) * 64 + dc);
-    }
-    float sa = 0.f, sb = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const float4_t q0 = *reinterpret_cast<const float4_t*>(&qs[sl][8 * c]);
-      const float4_t q1 = *reinterpret_cast<const float4_t*>(&qs[sl][8 * c + 4]);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float qe = e < 4 ? q0[e] : q1[e - 4];
-        sa += qe * to_f32(ka[c].v[e]);
-        if constexpr (PK == 128) sb += qe * to_f32(kb[c].v[e]);
-      }
-    }
-    const bool va = p0 + lane < pos, vb = PK == 128 && p0 + 64 + lane < pos;
-    const float mp = wave_max(fmaxf(va ? sa : -INFINITY, vb ? sb : -INFINITY));
-    const float mn = fmaxf(m, mp), scale = __expf(m - mn);
-    m = mn;
-    const float ea = va ? __expf(sa - m) : 0.f, eb = vb ? __expf(sb - m) : 0.f;
-    lsum = lsum * scale + wave_sum(ea + eb);
-    sc[sl][lane] = ea;
-    if constexpr (PK == 128) sc[sl][64 + lane] = eb;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] *= scale;
-#pragma unroll
-    for (int u = 0; u < VU; ++u) {
-      const float pw = sc[sl][kg + 8 * u];  // 0 past the end
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] += pw * to_f32(vf[u].v[e]);
-    }
-    __syncthreads();  // the staged rows are read: the next pass may overwrite them
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    o[e] = xor8_sum(o[e]);
-    o[e] = xor16_sum(o[e]);
-    o[e] = xor32_sum(o[e]);
-  }
-  if (kg == 0) {
-    const float e_cur = __expf(s_cur - m), inv = 1.f / (lsum + e_cur);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (o[e] + e_cur * vs[sl][dc + e]) * inv;
-    T* op = out + (int64_t)row * ldo + h * 64 + dc;
-    store4(op, o[0], o[1], o[2], o[3]);
-    store4(op + 4, o[4], o[5], o[6], o[7]);
-  }
-}
-
-// the self-attention form launch_self_attn_qkv picks (also what wh_step_kernels reports):
-// the grouped form only in the tuning build with WHISPER_HIP_SA_GRP set; the pipelined
-// 64-key passes unless WHISPER_HIP_SA_PIPE=0 (tuning build)
-int self_attn_grp_mode() {
-  static const int grp = [] {
-    const char* e = tune_env("WHISPER_HIP_SA_GRP");
-    return e ? atoi(e) : 0;
-  }();
-  return grp;
-}
-// the coalesced-K passes (PIPE 3) of the fp16-slab step form; WHISPER_HIP_SA_KCO=0 in the
-// tuning build: the lane-per-key K loads (PIPE 1)
-bool self_attn_kco_on() {
-  static const bool on = [] {
-    const char* e = tune_env("WHISPER_HIP_SA_KCO");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-// the cached-key count from which the coalesced-K passes run (tuning WHISPER_HIP_SA_KCO_MIN)
+// the cached-key count from which the fp16 coalesced-K passes run (tuning WHISPER_HIP_SA_KCO_MIN)
 int self_attn_kco_min() {
   static const int v = [] {
     const char* e = tune_env("WHISPER_HIP_SA_KCO_MIN");
@@ -1344,87 +931,24 @@ int self_attn_kco_min() {
   }();
   return v;
 }
-bool self_attn_pipe_on() {
-  static const bool pipe = [] {
-    const char* e = tune_env("WHISPER_HIP_SA_PIPE");
-    return !(e && e[0] == '0');
-  }();
-  return pipe;
-}
-
-
 template <typename T>
 int launch_self_attn_qkv(const float* part, int nsplit, int64_t part_stride, const float* bqkv, int ns, T* kc, T* vc,
                           const int* rw, const int* rs, const int* rp, const int* anc, int anc_beams, int nbeam, int H,
                           int ctx, T* out, int ldo, int rows, hipStream_t st, int slab_half) {
   if (rows <= 0) return 0;
   // the kernel takes window and beam from the row index: step rows are w * G + beam
-  // fp16 slabs: the pipelined fp16 form only (round 4 measured an fp16-slab form of the
-  // 128-key kernel 8.7 -> 13.9 us per launch)
   if (anc_beams < 1 || rows % anc_beams || nsplit > 16) return -1;
-  if (slab_half) {
+  if (slab_half) {  // fp16 slabs: fp16 contexts only
     if constexpr (sizeof(T) == 2) {
-      if (self_attn_pipe_on() && !self_attn_grp_mode()) {
-        if (self_attn_kco_on()) {
-          k_self_attn_qkv<T, 3, half_t><<<rows * H, 64, 0, st>>>(reinterpret_cast<const half_t*>(part), nsplit,
-                                                                part_stride, bqkv, ns, kc, vc, rw, rs, rp, anc,
-                                                                anc_beams, nbeam, H, ctx, out, ldo,
-                                                                self_attn_kco_min()), wh_launched("k_self_attn_qkv");
-          return 0;
-        }
-        k_self_attn_qkv<T, 1, half_t><<<rows * H, 64, 0, st>>>(reinterpret_cast<const half_t*>(part), nsplit,
-                                                              part_stride, bqkv, ns, kc, vc, rw, rs, rp, anc,
-                                                              anc_beams, nbeam, H, ctx, out, ldo), wh_launched("k_self_attn_qkv");
-        return 0;
-      }
+      k_self_attn_qkv<T, half_t><<<rows * H, 64, 0, st>>>(reinterpret_cast<const half_t*>(part), nsplit, part_stride,
+                                                         bqkv, ns, kc, vc, rw, rs, rp, anc, anc_beams, nbeam, H, ctx,
+                                                         out, ldo, self_attn_kco_min()), wh_launched("k_self_attn_qkv");
+      return 0;
     }
     return -1;
   }
-  // fp16 beams, tuning build only (WHISPER_HIP_SA_GRP=1): the grouped form, same arithmetic
-  // per row.  Measured slower at every context length (20 windows: step 3.456 -> 3.655 ms
-  // at 12 tokens, 3.834 -> 4.114 at 220, profiles/r04/self_attn_grp_ab.txt): at 238 VGPRs a
-  // CU holds one 5-wave workgroup, so the 400 (window, head) workgroups run in two rounds.
-  // WHISPER_HIP_SA_GRP=2: 64-key passes, 132 VGPRs, one round — slower still (3.423 -> 3.523
-  // ms at 12 tokens, 3.819 -> 4.145 at 220, profiles/r04/self_attn_grp64_ab.txt): the
-  // growth with the context is the passes' round trips, not the bytes the beams share
-  const int grp = self_attn_grp_mode();
-  if constexpr (sizeof(T) == 2) {
-    if (grp && anc_beams >= 2 && anc_beams <= SA_GMAX && ctx <= 512) {
-      if (grp == 2)
-        k_self_attn_grp<T, 64><<<(rows / anc_beams) * H, 64 * anc_beams, 0, st>>>(
-            part, nsplit, part_stride, bqkv, ns, kc, vc, rp, anc, anc_beams, nbeam, H, ctx, out, ldo), wh_launched("k_self_attn_grp");
-      else
-        k_self_attn_grp<T, 128><<<(rows / anc_beams) * H, 64 * anc_beams, 0, st>>>(
-            part, nsplit, part_stride, bqkv, ns, kc, vc, rp, anc, anc_beams, nbeam, H, ctx, out, ldo), wh_launched("k_self_attn_grp");
-      return 0;
-    }
-  }
-  // fp16: the pipelined 64-key passes (WHISPER_HIP_SA_PIPE=0 in the tuning build: the
-  // 128-key passes): 20-window step 3.419 -> 3.363 ms at 12 tokens, 3.810 -> 3.756 at 220,
-  // config 3 675.6 -> 684.6 xRT (profiles/r04/self_attn_pipe_ab.txt)
-  const bool pipe = self_attn_pipe_on();
-  if constexpr (sizeof(T) == 2) {
-    if (pipe) {
-      // WHISPER_HIP_SA_DEPTH=2 (tuning): two passes in flight ahead (A/B)
-      static const int depth = [] {
-        const char* e = tune_env("WHISPER_HIP_SA_DEPTH");
-        return e && e[0] == '2' ? 2 : 1;
-      }();
-      if (self_attn_kco_on())
-        k_self_attn_qkv<T, 3><<<rows * H, 64, 0, st>>>(part, nsplit, part_stride, bqkv, ns, kc, vc, rw, rs, rp, anc,
-                                                      anc_beams, nbeam, H, ctx, out, ldo, self_attn_kco_min()),
-            wh_launched("k_self_attn_qkv");
-      else if (depth == 2)
-        k_self_attn_qkv<T, 2><<<rows * H, 64, 0, st>>>(part, nsplit, part_stride, bqkv, ns, kc, vc, rw, rs, rp, anc,
-                                                      anc_beams, nbeam, H, ctx, out, ldo), wh_launched("k_self_attn_qkv");
-      else
-        k_self_attn_qkv<T, 1><<<rows * H, 64, 0, st>>>(part, nsplit, part_stride, bqkv, ns, kc, vc, rw, rs, rp, anc,
-                                                      anc_beams, nbeam, H, ctx, out, ldo), wh_launched("k_self_attn_qkv");
-      return 0;
-    }
-  }
   k_self_attn_qkv<T><<<rows * H, 64, 0, st>>>(part, nsplit, part_stride, bqkv, ns, kc, vc, rw, rs, rp, anc, anc_beams,
-                                             nbeam, H, ctx, out, ldo), wh_launched("k_self_attn_qkv");
+                                             nbeam, H, ctx, out, ldo, self_attn_kco_min()), wh_launched("k_self_attn_qkv");
   return 0;
 }
 
@@ -1467,10 +991,14 @@ void launch_reduce_store(const float* part, int nsplit, int64_t part_stride, con
   }
   const int64_t tot = (int64_t)M * N / 4;
   const unsigned nb = (unsigned)((tot + 255) / 256);
-  if (slab_half) {
-    const half_t* ph = reinterpret_cast<const half_t*>(part);
-    if (gelu) k_reduce_store<T, 1, half_t><<<nb, 256, 0, st>>>(ph, nsplit, part_stride, bias, out, ldo, M, N), wh_launched("k_reduce_store");
-    else k_reduce_store<T, 0, half_t><<<nb, 256, 0, st>>>(ph, nsplit, part_stride, bias, out, ldo, M, N), wh_launched("k_reduce_store");
+  if (slab_half) {  // fp16 slabs (k_proj in fp16 contexts)
+    if constexpr (sizeof(T) == 2) {
+      const half_t* ph = reinterpret_cast<const half_t*>(part);
+      if (gelu) k_reduce_store<T, 1, half_t><<<nb, 256, 0, st>>>(ph, nsplit, part_stride, bias, out, ldo, M, N), wh_launched("k_reduce_store");
+      else k_reduce_store<T, 0, half_t><<<nb, 256, 0, st>>>(ph, nsplit, part_stride, bias, out, ldo, M, N), wh_launched("k_reduce_store");
+    } else {
+      wh_set_launch_error("launch_reduce_store: fp16 slabs in an fp32 context");
+    }
     return;
   }
   if (gelu) k_reduce_store<T, 1><<<nb, 256, 0, st>>>(part, nsplit, part_stride, bias, out, ldo, M, N), wh_launched("k_reduce_store");
@@ -1749,26 +1277,12 @@ __device__ unsigned long long g_xs_trace[256][XS_MARKS];
 // the biases live in the tile partials' LDS (dead until the first tile).  Reference:
 // decoder.py:73-91 (cross-attention query), :42 (the 0.125 query scale, folded in W_q).
 //
-// Load order variants (QV; the arithmetic is the same in all three):
-//  0: X (registers), bias, W_q, then the first tile's K / V; the second tile is loaded by the
-//     tile loop.  Traced at 20 windows (profiles/r06/xattn_trace_qv.txt): X staged at 8.8 us
-//     — the X and bias requests queue behind every CU's W_q and first-tile K / V (63 MB asked
-//     for at once), so the query was staged at 10.5 us against 4.4 with the slabs.
-//  1: X and biases by LDS-DMA (no VGPRs), the first two tiles' K / V with W_q.  hipcc puts a
-//     vmcnt(0) ahead of the first LDS read after an LDS-DMA (it cannot tell the DMA's slot
-//     in the count), so the projection waits for both tiles as well.
-//  2: X and bias (registers) and W_q first; the two tiles' K / V are issued only once X is
-//     staged, so the few KB the projection waits on are not queued behind 25 MB of K / V;
-//     the tiles then stream while W_q lands and the projection runs.
-//  4: variant 2 with the W_q fragments issued first, ahead of the window-row metadata round
-//     trip (their addresses need only the pair's head); 5: variant 4 with the two tiles'
-//     K / V issued only after the projection's MFMAs (nothing competes with W_q and X).
-//  3: variant 2 for the single-window step (k_proj1 layers, no k_resid_ln): X is the fp32
-//     residual rows and each workgroup computes their LayerNorm (k_proj1's arithmetic: one
-//     wave per row, two register passes) into the staged fp16 rows; the grid gives every
-//     workgroup tiles of ONE pair (launch_cross_attn).
+// Load order: X and bias (registers) and W_q first; the first two tiles' K / V are issued only
+// once X is staged, so the few KB the projection waits on are not queued behind 25 MB of
+// K / V; the tiles then stream while W_q lands and the projection runs (issued with X they
+// staged the query at 10.5 us against 4.4 with the slabs, profiles/r06/xattn_trace_qv.txt).
 constexpr int XS_QF = 3;
-template <typename T, int QK, int RR, int QV, typename PairWH, typename LoadKV>
+template <typename T, int QK, int RR, typename PairWH, typename LoadKV>
 WH_DEV void xq_project(const XQPart& xq, int pa, int plast, int cnt, const int* __restrict__ win_row0,
                        const int* __restrict__ win_nrows, PairWH pair_wh, LoadKV load_kv, Frag<T> (&kA)[4][2],
                        Frag<T> (&vA)[4][2], Frag<T> (&kB)[4][2], Frag<T> (&vB)[4][2], char* xst, T (*qs)[16][72],
@@ -1776,11 +1290,8 @@ WH_DEV void xq_project(const XQPart& xq, int pa, int plast, int cnt, const int* 
   static_assert(sizeof(T) == 2, "fused query projection: fp16 contexts");
   constexpr int N = QK * 64;                           // model width = K
   constexpr int CPR = N * (int)sizeof(T) / 16;         // 16-B chunks per row
-  constexpr bool DMA = QV == 1;                        // X / bias by LDS-DMA
-  constexpr int XROWB = DMA ? N * (int)sizeof(T) : N * (int)sizeof(T) + 16;  // LDS row (bytes)
+  constexpr int XROWB = N * (int)sizeof(T) + 16;       // LDS row (bytes)
   constexpr int XPT = (RR * CPR + 511) / 512;          // chunks per thread per pair
-  static_assert(!DMA || (RR * CPR) % 64 == 0, "whole 1 KB LDS-DMA blocks per pair");
-  static_assert(!DMA || CPR % 8 == 0, "the row swizzle stays inside the row");
   // LDS (byte offsets in xst): X rows, the K-half sums [2][XS_QF][4][64] float4, the biases
   constexpr int RED_OFF = XS_QF * RR * XROWB, BIAS_OFF = RED_OFF + 2 * XS_QF * 4 * 64 * 16;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
@@ -1793,141 +1304,51 @@ WH_DEV void xq_project(const XQPart& xq, int pa, int plast, int cnt, const int* 
     const int pj = __builtin_amdgcn_readfirstlane(min(pa + j, plast));
     pair_wh(pj, q_w[j], q_h[j]);
   }
-  // QV 4 / 5: the wave's W_q fragments leave first, ahead of the metadata round trip
-  constexpr bool W_FIRST = QV >= 4;
   Frag<T> wf[QK];
-  auto load_w = [&](int h) {
-    if (xq.qwf) {  // fragment order (launch_wq_frag): each k-step one 1 KB contiguous wave load
-      const T* wp = reinterpret_cast<const T*>(xq.qwf) + ((int64_t)((h * 4 + c) * 2 + kh) * QK * 64 + lane) * 8;
+  auto load_w = [&](int h) {  // fragment order (launch_wq_frag): each k-step one 1 KB contiguous wave load
+    const T* wp = reinterpret_cast<const T*>(xq.qwf) + ((int64_t)((h * 4 + c) * 2 + kh) * QK * 64 + lane) * 8;
 #pragma unroll
-      for (int s = 0; s < QK; ++s) frag_load_stream(wf[s], wp + s * 512);
-    } else {
-      const T* wp = reinterpret_cast<const T*>(xq.qw) + (int64_t)(h * 64 + c * 16 + r) * N + kh * QK * 32 + 8 * g;
-#pragma unroll
-      for (int s = 0; s < QK; ++s) frag_load_stream(wf[s], wp + s * 32);
-    }
+    for (int s = 0; s < QK; ++s) frag_load_stream(wf[s], wp + s * 512);
   };
-  if constexpr (W_FIRST) {
-    load_w(q_h[0]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
 #pragma unroll
   for (int j = 0; j < XS_QF; ++j) {
     q_nr[j] = win_nrows[q_w[j]];
     q_r0[j] = win_row0[q_w[j]];
   }
-  // 1. each pair's window rows and head biases
-  constexpr bool LN = QV == 3;
-  constexpr int CPL = N / 256;  // (LN) float4 chunks of a fp32 row per lane
-  float4_t xv[DMA ? 1 : XS_QF][DMA ? 1 : XPT];
-  float bv[DMA ? 1 : XS_QF];
-  float4_t lx[LN ? CPL : 1], lg[LN ? CPL : 1], lb[LN ? CPL : 1];
-  if constexpr (LN) {
-    // wave w: row min(w, nr - 1) of the range's one pair (every LDS row a real row)
-    const float* xr = reinterpret_cast<const float*>(xq.qx) + (int64_t)(q_r0[0] + min(wave, q_nr[0] - 1)) * N;
+  // 1. each pair's window rows and head biases: unconditional buffer loads, the buffer limit
+  // is the window's rows (0 past it and for pairs past the range); the biases by wave 0, one
+  // float per lane and pair
+  float4_t xv[XS_QF][XPT];
+  float bv[XS_QF];
 #pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      lx[i] = load4f(xr + 4 * (lane + 64 * i));
-      lg[i] = load4f(xq.ln_g + 4 * (lane + 64 * i));
-      lb[i] = load4f(xq.ln_b + 4 * (lane + 64 * i));
+  for (int j = 0; j < XS_QF; ++j) {
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<T*>(reinterpret_cast<const T*>(xq.qx)) + (int64_t)q_r0[j] * N, 0, j < np ? q_nr[j] * N * (int)sizeof(T) : 0,
+        0x00020000);
+#pragma unroll
+    for (int i = 0; i < XPT; ++i) {
+      const int ch = tid + 512 * i, off = (ch / CPR) * (N * (int)sizeof(T)) + (ch % CPR) * 16;
+      xv[j][i] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
     }
-    bv[0] = xq.bias[q_h[0] * 64 + lane];
-  } else if constexpr (DMA) {
-    // LDS chunk q of pair j's block holds row q / CPR, chunk (q % CPR) ^ (row & 7) (rows past
-    // the window repeat its last row, pairs past the range the last pair: never read)
-    constexpr int NBLK = RR * CPR / 64, BPW = (NBLK + 7) / 8;  // 1 KB blocks per pair, per wave
-#pragma unroll
-    for (int j = 0; j < XS_QF; ++j) {
-      const int jj = min(j, np - 1);
-      const char* src = reinterpret_cast<const char*>(xq.qx) + (int64_t)q_r0[jj] * (N * (int)sizeof(T));
-#pragma unroll
-      for (int t = 0; t < BPW; ++t) {
-        const int blk = min(wave + 8 * t, NBLK - 1), q = blk * 64 + lane, row = q / CPR, cs = q - row * CPR;
-        const char* sp = src + min(row, q_nr[jj] - 1) * (N * (int)sizeof(T)) + ((cs ^ (row & 7)) * 16);
-        __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(sp),
-                                         (__attribute__((address_space(3))) void*)(xst + (j * RR * CPR + blk * 64) * 16),
-                                         16, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < XS_QF; ++j)
-      if (lane < 16)  // 16 lanes x 16 B: the head's 64 fp32 biases
-        __builtin_amdgcn_global_load_lds(
-            (__attribute__((address_space(1))) void*)(xq.bias + q_h[min(j, np - 1)] * 64 + 4 * lane),
-            (__attribute__((address_space(3))) void*)(xst + BIAS_OFF + j * 256), 16, 0, 0);
-  } else {
-    // unconditional buffer loads: the buffer limit is the window's rows (0 past it and for
-    // pairs past the range); the biases by wave 0, one float per lane and pair
-    static_assert(N % 256 == 0 || !LN, "LN rows: whole float4 chunks per lane");
-#pragma unroll
-    for (int j = 0; j < XS_QF; ++j) {
-      const auto rs = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<T*>(reinterpret_cast<const T*>(xq.qx)) + (int64_t)q_r0[j] * N, 0, j < np ? q_nr[j] * N * (int)sizeof(T) : 0,
-          0x00020000);
-#pragma unroll
-      for (int i = 0; i < XPT; ++i) {
-        const int ch = tid + 512 * i, off = (ch / CPR) * (N * (int)sizeof(T)) + (ch % CPR) * 16;
-        xv[j][i] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < XS_QF; ++j) bv[j] = xq.bias[q_h[min(j, np - 1)] * 64 + lane];
   }
+#pragma unroll
+  for (int j = 0; j < XS_QF; ++j) bv[j] = xq.bias[q_h[min(j, np - 1)] * 64 + lane];
   __builtin_amdgcn_sched_barrier(0);
   // 2. the wave's W_q fragments for the first pair's head: rows h*64 + 16c + r, K half kh
-  if constexpr (!W_FIRST) {
-    load_w(q_h[0]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  // 3. (QV 0 / 1) the first tile's K / V, (1) the second's too
-  if constexpr (QV <= 1) {
-    load_kv(min(wave, cnt - 1), kA, vA);
-    if constexpr (QV == 1) load_kv(min(wave + 8, cnt - 1), kB, vB);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  // 4. X (and the biases) -> LDS: waits for them alone (issued first; vmcnt retires in order)
-  if constexpr (LN) {
-    // LayerNorm of the wave's row (biased variance, two passes in registers: k_proj1's
-    // prologue arithmetic), stored as the fp16 row
-    float sm = 0.f;
+  load_w(q_h[0]);
+  __builtin_amdgcn_sched_barrier(0);
+  // 3. X (and the biases) -> LDS: waits for them alone (issued first; vmcnt retires in order)
 #pragma unroll
-    for (int i = 0; i < CPL; ++i) sm += lx[i][0] + lx[i][1] + lx[i][2] + lx[i][3];
-    const float mean = wave_sum(sm) / (float)N;
-    float qv2 = 0.f;
+  for (int j = 0; j < XS_QF; ++j)
 #pragma unroll
-    for (int i = 0; i < CPL; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = lx[i][e] - mean;
-        qv2 += d * d;
-      }
-    const float rstd = rsqrtf(wave_sum(qv2) / (float)N + xq.ln_eps);
-    if (wave < RR) {
-#pragma unroll
-      for (int i = 0; i < CPL; ++i) {
-        const float4_t v = lx[i];
-        store4(reinterpret_cast<T*>(xst + wave * XROWB) + 4 * (lane + 64 * i), (v[0] - mean) * rstd * lg[i][0] + lb[i][0],
-               (v[1] - mean) * rstd * lg[i][1] + lb[i][1], (v[2] - mean) * rstd * lg[i][2] + lb[i][2],
-               (v[3] - mean) * rstd * lg[i][3] + lb[i][3]);
-      }
+    for (int i = 0; i < XPT; ++i) {
+      const int ch = tid + 512 * i;
+      if (ch < RR * CPR)
+        *reinterpret_cast<float4_t*>(xst + (j * RR + ch / CPR) * XROWB + (ch % CPR) * 16) = xv[j][i];
     }
-    if (wave == 0) reinterpret_cast<float*>(xst + BIAS_OFF)[lane] = bv[0];
-  } else if constexpr (DMA) {
-    static_assert(QK + 32 <= 63, "vmcnt range");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(QK + 32) : "memory");
-  } else {
+  if (wave == 0) {
 #pragma unroll
-    for (int j = 0; j < XS_QF; ++j)
-#pragma unroll
-      for (int i = 0; i < XPT; ++i) {
-        const int ch = tid + 512 * i;
-        if (ch < RR * CPR)
-          *reinterpret_cast<float4_t*>(xst + (j * RR + ch / CPR) * XROWB + (ch % CPR) * 16) = xv[j][i];
-      }
-    if (wave == 0) {
-#pragma unroll
-      for (int j = 0; j < XS_QF; ++j) reinterpret_cast<float*>(xst + BIAS_OFF)[j * 64 + lane] = bv[j];
-    }
+    for (int j = 0; j < XS_QF; ++j) reinterpret_cast<float*>(xst + BIAS_OFF)[j * 64 + lane] = bv[j];
   }
   if (tid == 0) {  // the merge's window rows (LDS, behind the barriers below)
 #pragma unroll
@@ -1938,11 +1359,9 @@ WH_DEV void xq_project(const XQPart& xq, int pa, int plast, int cnt, const int* 
   }
   wh_lds_barrier();
   XS_MARK(7);  // X staged
-  // 3'. (QV 2 - 4) the first two tiles' K / V leave now, behind the few KB the projection waited on
-  if constexpr (QV >= 2 && QV <= 4) {
-    load_kv(min(wave, cnt - 1), kA, vA);
-    load_kv(min(wave + 8, cnt - 1), kB, vB);
-  }
+  // 4. the first two tiles' K / V leave now, behind the few KB the projection waited on
+  load_kv(min(wave, cnt - 1), kA, vA);
+  load_kv(min(wave + 8, cnt - 1), kB, vB);
   // 5. pair by pair: MFMAs in k-step order (W reloaded only where the head changes); each
   // pair's K-half sum goes to LDS at once (no register per pair)
   float4_t* red2 = reinterpret_cast<float4_t*>(xst + RED_OFF);  // [kh][pair][c][lane]
@@ -1957,16 +1376,11 @@ WH_DEV void xq_project(const XQPart& xq, int pa, int plast, int cnt, const int* 
       for (int s = 0; s < QK; ++s) {
         Frag<T> xf;
         const int ch = kh * QK * 4 + 4 * s + g;  // 16-B chunk of k = kh * N / 2 + 32 s + 8 g
-        frag_load(xf, reinterpret_cast<const T*>(xl + (DMA ? (ch ^ (rr & 7)) : ch) * 16));
+        frag_load(xf, reinterpret_cast<const T*>(xl + ch * 16));
         mfma_step(acc, wf[s], xf);
       }
       red2[((kh * XS_QF + j) * 4 + c) * 64 + lane] = acc;
     }
-  }
-  // 3''. (QV 5) the first two tiles' K / V only once the projection has its operands
-  if constexpr (QV == 5) {
-    load_kv(min(wave, cnt - 1), kA, vA);
-    load_kv(min(wave + 8, cnt - 1), kB, vB);
   }
   XS_MARK(8);  // this wave's (thread 0's) MFMAs done: its W_q fragments landed
   // 6. the K halves meet (half 0 + half 1, then the bias) -> qs[pair][row][64] (fp16)
@@ -1983,135 +1397,7 @@ WH_DEV void xq_project(const XQPart& xq, int pa, int plast, int cnt, const int* 
   }
 }
 
-// QV 6 (round 6, the single-window step): the query projection split over the XQ1_P workgroups
-// of each (window, head) pair instead of computed whole by each of them (QV 3: every one of
-// the 240 workgroups ingested its head's 164 KB W_q slice before any tile, 6.1 -> 15.3 us).
-// The grid gives every workgroup nsp / XQ1_P tiles of ONE pair; workgroup kpart of the pair
-// computes the partial query over k-steps [kpart KS, kpart KS + KS) (KS = 2 QK / XQ1_P), stores
-// it write-through into xq.q_part, drains and counts it on the pair's arrival counter; the
-// query is the XQ1_P partials summed in kpart order + the bias (the same arithmetic in every
-// workgroup of the pair).  Roles: waves < cnt (the tile waves) issue their tile's K / V first
-// and wait at the barriers; waves 3-7 compute the LayerNorm of the window's rows (k_proj1's
-// arithmetic) into LDS; waves 4-7 (column tile c = wave - 4) run the partial projection; wave
-// 3 polls the counter (sc1 loads, bounded: a lost arrival ends the wait with a wrong query,
-// never a hang).  Every workgroup of the pair is resident at once (XQ1_P x npair <= 256
-// one-workgroup-per-CU launches: the launcher checks).  The last of the pair's workgroups to
-// read the partials re-arms both counters (departure count).
-template <typename T, int QK, int RR, typename PairWH, typename LoadKV>
-WH_DEV void xq_project_split(const XQPart& xq, int pa, int kpart, int cnt, const int* __restrict__ win_row0,
-                             const int* __restrict__ win_nrows, PairWH pair_wh, LoadKV load_kv, Frag<T> (&kA)[4][2],
-                             Frag<T> (&vA)[4][2], char* xst, T (*qs)[16][72], int* s_wnr, int* s_wr0) {
-  static_assert(sizeof(T) == 2, "fused query projection: fp16 contexts");
-  constexpr int N = QK * 64, KS = 2 * QK / XQ1_P, CPL = N / 256, XROWB = N * (int)sizeof(T) + 16;
-  static_assert((2 * QK) % XQ1_P == 0 && N % 256 == 0 && RR <= 10, "split geometry");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
-  int wi, h;
-  pair_wh(pa, wi, h);
-  // the tile waves' K / V leave first (nothing of theirs waits on the query until the tiles)
-  if (wave < cnt) load_kv(wave, kA, vA);
-  const int nr = win_nrows[wi], r0 = win_row0[wi];
-  if (tid == 0) {
-    s_wnr[0] = nr;
-    s_wr0[0] = r0;
-  }
-  const bool pw = wave >= 4;  // projection waves: column tile c = wave - 4
-  const int c = wave - 4;
-  Frag<T> wf[KS];
-  if (pw) {  // W_q rows h*64 + 16c + r, k-steps kpart*KS .. + KS - 1
-    const T* wp = reinterpret_cast<const T*>(xq.qw) + (int64_t)(h * 64 + c * 16 + r) * N + kpart * KS * 32 + 8 * g;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) frag_load_stream(wf[s], wp + s * 32);
-  }
-  // LayerNorm: waves 3..7 take rows wave - 3 and wave + 2 (rows past the window repeat its last)
-  if (wave >= 3) {
-    float4_t lg[CPL], lb[CPL];
-#pragma unroll
-    for (int i = 0; i < CPL; ++i) {
-      lg[i] = load4f(xq.ln_g + 4 * (lane + 64 * i));
-      lb[i] = load4f(xq.ln_b + 4 * (lane + 64 * i));
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int row = wave - 3 + 5 * t;
-      if (row < RR) {
-        const float* xr = reinterpret_cast<const float*>(xq.qx) + (int64_t)(r0 + min(row, nr - 1)) * N;
-        float4_t lx[CPL];
-#pragma unroll
-        for (int i = 0; i < CPL; ++i) lx[i] = load4f(xr + 4 * (lane + 64 * i));
-        float sm = 0.f;
-#pragma unroll
-        for (int i = 0; i < CPL; ++i) sm += lx[i][0] + lx[i][1] + lx[i][2] + lx[i][3];
-        const float mean = wave_sum(sm) / (float)N;
-        float qv2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < CPL; ++i)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float d = lx[i][e] - mean;
-            qv2 += d * d;
-          }
-        const float rstd = rsqrtf(wave_sum(qv2) / (float)N + xq.ln_eps);
-#pragma unroll
-        for (int i = 0; i < CPL; ++i) {
-          const float4_t v = lx[i];
-          store4(reinterpret_cast<T*>(xst + row * XROWB) + 4 * (lane + 64 * i), (v[0] - mean) * rstd * lg[i][0] + lb[i][0],
-                 (v[1] - mean) * rstd * lg[i][1] + lb[i][1], (v[2] - mean) * rstd * lg[i][2] + lb[i][2],
-                 (v[3] - mean) * rstd * lg[i][3] + lb[i][3]);
-        }
-      }
-    }
-  }
-  wh_lds_barrier();
-  XS_MARK(7);  // rows staged
-  const auto rq = wt_rsrc(xq.q_part);
-  const int pbase = pa * XQ1_P * 4 * 64 * 16;  // bytes: [pair][kpart][c][lane] float4
-  int* const arr = xq.q_cnt + 2 * pa;          // [pair]{arrivals, departures}
-  if (pw) {
-    float4_t acc = (float4_t){0.f, 0.f, 0.f, 0.f};
-    const char* xl = xst + min(r, RR - 1) * XROWB;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      Frag<T> xf;
-      frag_load(xf, reinterpret_cast<const T*>(xl + ((kpart * KS + s) * 4 + g) * 16));
-      mfma_step(acc, wf[s], xf);
-    }
-    wt_store4(rq, pbase + ((kpart * 4 + c) * 64 + lane) * 16, acc);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's partial is written through
-    if (lane == 0) __hip_atomic_fetch_add(arr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else if (wave == 3) {
-    const auto ra = wt_rsrc(arr);
-    int v = 0;
-    for (int it = 0; it < (1 << 16); ++it) {  // (~65 ms: a normal wait is a few us)
-      v = (int)__builtin_amdgcn_raw_buffer_load_b32(ra, 0, 0, 16);
-      if (v >= 4 * XQ1_P) break;
-      __builtin_amdgcn_s_sleep(1);
-    }
-    (void)v;
-  }
-  wh_lds_barrier();  // wave 3 has seen every partial of the pair arrive
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the loads below
-  if (pw) {
-    float4_t pv[XQ1_P];
-#pragma unroll
-    for (int j = 0; j < XQ1_P; ++j)
-      pv[j] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rq, pbase + ((j * 4 + c) * 64 + lane) * 16, 0, 16));
-    float4_t q = pv[0];
-#pragma unroll
-    for (int j = 1; j < XQ1_P; ++j) q += pv[j];
-    q += load4f(xq.bias + h * 64 + c * 16 + 4 * g);
-    store4(&qs[0][r][c * 16 + 4 * g], q[0], q[1], q[2], q[3]);
-    if (wave == 4 && lane == 0) {
-      // every workgroup of the pair departs once it has read the partials; the last re-arms
-      if (__hip_atomic_fetch_add(arr + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == XQ1_P - 1) {
-        __hip_atomic_store(arr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(arr + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  }
-  XS_MARK(8);  // query summed
-}
-
-template <typename T, int QZ, int RR, typename S = float, bool FULL = false, int QK = 0, int QV = 0>
+template <typename T, int QZ, int RR, typename S = float, bool FULL = false, int QK = 0>
 __global__ __launch_bounds__(512, 1) void k_xattn_seg(const T* __restrict__ q, int ldq, const T* ck, const T* cvt, int Tk,
                                                      int H, int npair, int nsp, const int* __restrict__ win_row0,
                                                      const int* __restrict__ win_nrows,
@@ -2119,7 +1405,7 @@ __global__ __launch_bounds__(512, 1) void k_xattn_seg(const T* __restrict__ q, i
                                                      T* __restrict__ out, int ldo) {
   constexpr int NW = 8, SMAX = XsShape<RR>::SMAX, PPASS = 512 / (RR * 16);  // pairs merged per pass
   constexpr bool QP = QZ > 0;
-  // QK > 0 (round 6): the query projection itself runs here (xq.qx rows x xq.qw^T + bias,
+  // QK > 0 (round 6): the query projection itself runs here (xq.qx rows x W_q^T + bias,
   // QK k-steps per K half), pairs are numbered head-major (p = head * nwin + window: a
   // workgroup's pairs share one head's 64 x n slice of W_q) and workgroups are laid over
   // the XCDs in contiguous logical runs, so a head's slice crosses HBM about once per XCD
@@ -2240,12 +1526,8 @@ __global__ __launch_bounds__(512, 1) void k_xattn_seg(const T* __restrict__ q, i
     static_assert(XS_QF * RR * (QK * 64 * sizeof(T) + 16) + 2 * XS_QF * 4 * 64 * 16 + XS_QF * 256 <= sizeof(seg_o),
                   "X rows, K-half sums and biases in the partials' LDS");
     static_assert(XS_QF * 4 * 64 * 16 <= sizeof(seg_o), "K-half sums in the partials' LDS");
-    if constexpr (QV == 6)
-      xq_project_split<T, QK, RR>(xq, pa, (s0 - pa * nsp) / max(cnt, 1), cnt, win_row0, win_nrows, pair_wh, load_kv, kA,
-                                  vA, reinterpret_cast<char*>(&seg_o[0][0][0]), qs, s_wnr, s_wr0);
-    else
-      xq_project<T, QK, RR, QV>(xq, pa, plast, cnt, win_row0, win_nrows, pair_wh, load_kv, kA, vA, kB, vB,
-                                reinterpret_cast<char*>(&seg_o[0][0][0]), qs, s_wnr, s_wr0);
+    xq_project<T, QK, RR>(xq, pa, plast, cnt, win_row0, win_nrows, pair_wh, load_kv, kA, vA, kB, vB,
+                          reinterpret_cast<char*>(&seg_o[0][0][0]), qs, s_wnr, s_wr0);
   } else {
   // FULL (the launcher: every workgroup holds >= 8 tiles, one per wave at least): the order
   // above; otherwise (few windows, <= 1 tile per wave) the first tile leaves first, as the
@@ -2315,10 +1597,8 @@ __global__ __launch_bounds__(512, 1) void k_xattn_seg(const T* __restrict__ q, i
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // LDS only
   XS_MARK(1);
 
-  if (QF && QV == 6) {
-    if (wave < cnt) tile(kA, vA, wave);  // (the launcher: <= NW tiles per workgroup)
-  } else if (QF && QV >= 1 && wave < cnt) {
-    // (QV 1 / 2) kB / vB already hold tile wave + NW (clamped): the next tile is in flight on
+  if (QF && wave < cnt) {
+    // (xq_project) kB / vB already hold tile wave + NW (clamped): the next tile is in flight on
     // entry, so each iteration refills the buffer it has just computed
     int i = wave;
     for (; i + 2 * NW < cnt; i += 2 * NW) {
@@ -2456,25 +1736,6 @@ int xattn_seg_grid(int npair, int nsp, int smax) {
   return nwg;
 }
 
-bool xattn_l2_ranges(int nwin, int H, int max_rows, L2Prefetch* pf) {
-  const int npair = nwin * H, nsp = XS_NSP, nseg = npair * nsp;
-  const int nwg = xattn_seg_grid(npair, nsp, max_rows <= 8 ? XsShape<8>::SMAX : XsShape<16>::SMAX);
-  if (nwg < 16) return false;
-  const int q = nwg / 8, r = nwg % 8;
-  for (int x = 0; x < 8; ++x) {
-    const int L0 = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q, cnt = q + (x < r ? 1 : 0);
-    const unsigned s0 = (unsigned)L0 * (unsigned)nseg / (unsigned)nwg,
-                   s1 = (unsigned)(L0 + cnt) * (unsigned)nseg / (unsigned)nwg;  // range_split
-    if (cnt == 0 || s1 <= s0) {
-      pf->lo[x] = pf->hi[x] = 0;
-      continue;
-    }
-    pf->lo[x] = (int)(s0 / nsp) / nwin;             // head-major pairs: p = head * nwin + window
-    pf->hi[x] = (int)((s1 - 1) / nsp) / nwin + 1;
-  }
-  return true;
-}
-
 __global__ __launch_bounds__(256) void k_wq_frag(const half_t* __restrict__ w, half_t* __restrict__ f, int n) {
   const int QK = n / 64, total = n * n / 8;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
@@ -2485,42 +1746,6 @@ __global__ __launch_bounds__(256) void k_wq_frag(const half_t* __restrict__ w, h
 }
 void launch_wq_frag(const void* w, void* f, int n, hipStream_t st) {
   k_wq_frag<<<256, 256, 0, st>>>(reinterpret_cast<const half_t*>(w), reinterpret_cast<half_t*>(f), n), wh_launched("k_wq_frag");
-}
-
-// Round 6 probe (tuning build, WHISPER_HIP_XKV_PF=<workgroups>): pull one layer's cross-
-// attention K and V blocks of the batch's windows through the memory side on a second
-// stream beside the layer's launch chain, so that k_xattn_seg reads them from the Infinity
-// Cache (256 MiB; 157 MB at 20 windows) instead of HBM.  (Register loads folded into a
-// dummy word: hipcc copied the loop-carried registers and waited on every load.)
-__global__ __launch_bounds__(256) void k_kv_pull(const char* __restrict__ ck, const char* __restrict__ cv,
-                                                 const int* __restrict__ win_slot, int nwin, int64_t slot_bytes) {
-  // workgroup b: 32-KB pieces b, b + grid, ... of the windows' K then V blocks; each wave
-  // moves 8 KB of a piece by LDS-DMA into a 1-KB sink (no registers, nothing read back) and
-  // keeps at most 24 KB in flight (explicit vmcnt: the DMA's only consumer is the exit)
-  constexpr int64_t CH = 32768;
-  __shared__ __attribute__((aligned(16))) char sink[1024];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int cpb = (int)(slot_bytes / CH), total = 2 * nwin * cpb;
-  for (int c = blockIdx.x; c < total; c += gridDim.x) {
-    const int blk = c / cpb, w = blk >> 1;
-    int slot;  // a scalar load: a vector one would retire behind the DMA loads (vmcnt in order)
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(slot) : "s"(win_slot + w) : "memory");
-    const char* p = ((blk & 1) ? cv : ck) + (int64_t)slot * slot_bytes + (int64_t)(c - blk * cpb) * CH + tid * 16;
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(p + u * 4096),
-                                       (__attribute__((address_space(3))) void*)(sink), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA into the sink after the workgroup ends
-  (void)lane;
-}
-void launch_kv_pull(const void* ck, const void* cv, const int* win_slot, int nwin, int64_t slot_bytes, int nwg,
-                    unsigned* sink, hipStream_t st) {
-  (void)sink;
-  if (nwin <= 0 || nwg <= 0 || slot_bytes % 32768) return;
-  k_kv_pull<<<nwg, 256, 0, st>>>(reinterpret_cast<const char*>(ck), reinterpret_cast<const char*>(cv), win_slot, nwin,
-                                 slot_bytes), wh_launched("k_kv_pull");
 }
 
 template <typename T>
@@ -2537,58 +1762,22 @@ void launch_cross_attn(const T* q, int ldq, const T* ck, const T* cv, int Tk, in
     // FULL: every workgroup's range holds >= 8 tiles (one per wave), e.g. 20 windows
     const int nwg_xs = xattn_seg_grid(npair, nsp, xq.max_rows <= 8 ? XsShape<8>::SMAX : XsShape<16>::SMAX);
     const bool full = (npair * nsp) / nwg_xs >= 8;
+    if (xq.part_half && sizeof(T) != 2) {
+      wh_set_launch_error("launch_cross_attn: fp16 query slabs in an fp32 context");
+      return;
+    }
     if (xq.qx) {  // the query projected in the kernel (round 6)
       if constexpr (sizeof(T) == 2) {
-        if (!xq.qw || !xq.bias || !xattn_fused_q(H * 64, xq.max_rows, (int)sizeof(T)) || nsp != XS_NSP) {
+        if (!xq.qwf || !xq.bias || !xattn_fused_q(H * 64, xq.max_rows, (int)sizeof(T)) || nsp != XS_NSP) {
           wh_set_launch_error("launch_cross_attn: fused query projection outside its shapes");
           return;
         }
-        if (xq.ln_g) {
-          // the single-window step: fp32 rows + LayerNorm in the kernel; every workgroup holds
-          // 2 tiles of ONE pair (nsp even): 12 workgroups per pair, merged through records
-          if (nwin != 1 || !xq.ln_b || nsp % 2) {
-            wh_set_launch_error("launch_cross_attn: in-kernel LayerNorm query is the single-window form");
-            return;
-          }
-          if (xq.q_part && xq.q_cnt) {
-            // QV 6: the projection split over the XQ1_P workgroups of each pair (all resident:
-            // one 512-thread workgroup per CU, npair x XQ1_P <= 256)
-            if (nsp % XQ1_P || nsp / XQ1_P > 8 || npair * XQ1_P > 256 || xq.max_rows > 10) {
-              wh_set_launch_error("launch_cross_attn: split query projection outside its shapes");
-              return;
-            }
-            k_xattn_seg<T, 0, 8, float, false, 20, 6><<<npair * XQ1_P, 512, 0, st>>>(
-                q, ldq, ck, cv, Tk, H, npair, nsp, win_row0, win_nrows, win_slot, win_stride, xq, out, ldo),
-                wh_launched("k_xattn_seg<qproj-split+ln>");
-            return;
-          }
-          k_xattn_seg<T, 0, 8, float, false, 20, 3><<<npair * nsp / 2, 512, 0, st>>>(
-              q, ldq, ck, cv, Tk, H, npair, nsp, win_row0, win_nrows, win_slot, win_stride, xq, out, ldo),
-              wh_launched("k_xattn_seg<qproj,ln>");
-          return;
-        }
-        // load-order variant (xq_project): 2 unless the tuning build's WHISPER_HIP_XQV says 0 / 1
-        static const int qv = [] {
-          const char* e = tune_env("WHISPER_HIP_XQV");
-          return e ? atoi(e) : 2;
-        }();
-#define XQF(FULL_, QV_)                                                                                            \
-  k_xattn_seg<T, 0, 8, float, FULL_, 20, QV_><<<nwg_xs, 512, 0, st>>>(q, ldq, ck, cv, Tk, H, npair, nsp, win_row0, \
-                                                                      win_nrows, win_slot, win_stride, xq, out, ldo), \
+#define XQF(FULL_)                                                                                            \
+  k_xattn_seg<T, 0, 8, float, FULL_, 20><<<nwg_xs, 512, 0, st>>>(q, ldq, ck, cv, Tk, H, npair, nsp, win_row0, \
+                                                                 win_nrows, win_slot, win_stride, xq, out, ldo), \
       wh_launched("k_xattn_seg<qproj>")
-        if (full) {
-          if (qv == 2) XQF(true, 2);
-          else if (qv == 4) XQF(true, 4);
-          else if (qv == 5) XQF(true, 5);
-          else if (qv == 1) XQF(true, 1);
-          else XQF(true, 0);
-        } else {
-          if (qv == 2) XQF(false, 2);
-          else if (qv == 4) XQF(false, 4);
-          else if (qv == 5) XQF(false, 5);
-          else if (qv == 1) XQF(false, 1);
-          else XQF(false, 0);
-        }
+        if (full) XQF(true);
+        else XQF(false);
 #undef XQF
       } else {
         wh_set_launch_error("launch_cross_attn: fused query projection in an fp32 context");
@@ -2602,12 +1791,14 @@ void launch_cross_attn(const T* q, int ldq, const T* ck, const T* cv, int Tk, in
   else                                                                                                          \
     k_xattn_seg<T, QZ_, RR_, S_, false><<<nwg_xs, 512, 0, st>>>(q, ldq, ck, cv, Tk, H, npair, nsp, win_row0,      \
                                                                 win_nrows, win_slot, win_stride, xq, out, ldo), wh_launched("k_xattn_seg")
-#define XS(QZ_, RR_)          \
-  if (xq.part_half) {         \
-    XSF(QZ_, RR_, half_t);    \
-  } else {                    \
-    XSF(QZ_, RR_, float);     \
-  }
+#define XS(QZ_, RR_)                          \
+  if constexpr (sizeof(T) == 2 && QZ_ > 0) {  \
+    if (xq.part_half) {                       \
+      XSF(QZ_, RR_, half_t);                  \
+      return;                                 \
+    }                                         \
+  }                                           \
+  XSF(QZ_, RR_, float)
 #define XSR(QZ_)                        \
   if (xq.max_rows <= 8) {               \
     XS(QZ_, 8);                         \
@@ -2872,7 +2063,7 @@ void launch_mel_seg(const float* audio, const MelFile* files, int n_files, int64
   template void launch_layernorm<T>(const float*, T*, const float*, const float*, int, int, float, const int*,     \
                                     hipStream_t);                                                                   \
   template void launch_resid_ln<T>(float*, const float*, int, int64_t, const float*, T*, const float*, const float*, \
-                                   int, int, float, hipStream_t, int, const L2Prefetch*);                           \
+                                   int, int, float, hipStream_t, int);                           \
   template int launch_self_attn_qkv<T>(const float*, int, int64_t, const float*, int, T*, T*, const int*, const int*, \
                                         const int*, const int*, int, int, int, int, T*, int, int, hipStream_t, int); \
   template void launch_reduce_store<T>(const float*, int, int64_t, const float*, T*, int, int, int, int, hipStream_t, \

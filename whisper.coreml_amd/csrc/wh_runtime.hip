@@ -224,8 +224,6 @@ struct Ctx : public wh_ctx {
   int* fp_anc = nullptr;
   static constexpr int P1_SLABS = 2048;  // k_proj1 split-K slabs: zs x 16-column tiles <= 16 x 80 at n = 1280
   float* p1_slab = nullptr;  // k_proj1 in-launch split-K slabs [zs][N/16][256]
-  float* vs_rec = nullptr;   // k_vocab_sel records
-  int* vs_cnt = nullptr;     // and its arrival counter (zero between launches)
   int* p1_cnt = nullptr;     // and arrival counters [4n/16] (zero between launches)
   // single-window encoder: the residual GEMMs' K halves (k_gemm_tile KZ = 2) meet through
   // these fp32 slabs (64 KB per 128 x 64 tile, 12 x n/64 tiles at 1500 rows) and
@@ -235,8 +233,6 @@ struct Ctx : public wh_ctx {
   float* xs_rec = nullptr;   // step cross-attention segment records [pair][XS_NSP][XREC]
   float* x2_d = nullptr;     // k_proj1 path: second residual buffer (deferred residual ping-pong)
   int* xs_cnt = nullptr;     // and (window, head) arrival counters
-  float* xq1_part = nullptr; // single-window split query projection: partials [head][8][4][64] float4
-  int* xq1_cnt = nullptr;    // and {arrivals, departures} per head (zero between launches)
 
   // the step cross-attention's query / split arguments
   XQPart step_xq(int rows_per_window) const {
@@ -290,12 +286,6 @@ struct Ctx : public wh_ctx {
     if (gexec) rel(hipGraphExecDestroy(gexec), "hipGraphExecDestroy");
     if (graph) rel(hipGraphDestroy(graph), "hipGraphDestroy");
     if (st) rel(hipStreamDestroy(st), "hipStreamDestroy");
-    if (pst) {  // the tuning build's KV pull stream (kv_pull_setup)
-      rel(hipStreamSynchronize(pst), "hipStreamSynchronize(pull)");
-      rel(hipStreamDestroy(pst), "hipStreamDestroy(pull)");
-      for (auto& e : kv_ev) rel(hipEventDestroy(e), "hipEventDestroy(pull)");
-      rel(hipFree(kv_sink), "hipFree(pull sink)");
-    }
     if (wbase) rel(hipFree(wbase), "hipFree(weights)");
     if (abase) rel(hipFree(abase), "hipFree(activations)");
     if (d_audio) rel(hipFree(d_audio), "hipFree(audio)");
@@ -421,13 +411,11 @@ struct Ctx : public wh_ctx {
     addA((size_t)Wcap * Gcap * KC * 4); addA((size_t)Wcap * Gcap * KC * 4);
     addA((size_t)Wcap * Gcap * LP_SLICES * LP_REC * 4); addA((size_t)Wcap * Gcap * 4);
     addA((size_t)Wcap * 4);  // window arrival counters of the merging selection
-    addA(VS_REC_FLOATS * 4); addA(64);  // single-window tail records + arrival counter
     addA(64);
     addA(64);
     addA((size_t)P1_SLABS * 256 * 4); addA((size_t)(4 * n / 16) * 4);  // k_proj1 split-K slabs + counters
     addA((size_t)Wcap * nh * XS_NSP * XREC * 4); addA((size_t)Wcap * nh * 4);  // cross-attention segment records
     addA((size_t)8 * n * 4);  // k_proj1 path (<= 8 rows, wh_proj.h P1_RMAX): the second residual buffer
-    addA((size_t)nh * XQ1_P * 4 * 64 * 16); addA((size_t)nh * 2 * 4);  // split query partials + counters
     addA((size_t)EKZ_TILES(n) * 65536); addA((size_t)EKZ_TILES(n) * 4 * 4);  // single-window encoder K halves
     HIPCHK(hipMalloc(&abase, ab));
     HIPCHK(hipMemset(abase, 0, ab));
@@ -462,15 +450,12 @@ struct Ctx : public wh_ctx {
     S.cand_val = fa((size_t)Wcap * Gcap * KC); S.cand_idx = ia((size_t)Wcap * Gcap * KC);
     S.lpart = fa((size_t)Wcap * Gcap * LP_SLICES * LP_REC); S.lp_cnt = ia((size_t)Wcap * Gcap);  // zeroed with the arena
     S.lpw_cnt = ia((size_t)Wcap);
-    vs_rec = fa(VS_REC_FLOATS); vs_cnt = ia(16);  // zeroed with the arena
     S.seed = (unsigned long long*)aa.take(64);
     p1_slab = fa((size_t)P1_SLABS * 256); p1_cnt = ia(4 * n / 16);  // zeroed with the arena
     xs_rec = fa((size_t)Wcap * nh * XS_NSP * XREC); xs_cnt = ia((size_t)Wcap * nh);
     x2_d = fa((size_t)8 * n);
-    xq1_part = fa((size_t)nh * XQ1_P * 4 * 64 * 4); xq1_cnt = ia((size_t)nh * 2);  // zeroed with the arena
     ekz_slab = fa((size_t)EKZ_TILES(n) * 16384); ekz_cnt = ia((size_t)EKZ_TILES(n) * 4);  // zeroed with the arena
-    if (!fp_anc || !S.seed || !S.cand_idx || !S.lp_cnt || !S.lpw_cnt || !vs_cnt || !p1_cnt || !xs_cnt || !x2_d || !ekz_cnt ||
-        !xq1_cnt)
+    if (!fp_anc || !S.seed || !S.cand_idx || !S.lp_cnt || !S.lpw_cnt || !p1_cnt || !xs_cnt || !x2_d || !ekz_cnt)
       return fail(-3, "activation arena overflow");
     S.nw = Wcap; S.G = 1; S.ctx = CTX; S.hctx = HCTX; S.maxc = 16;
     HIPCHK(hipMalloc(&d_gmax, 64));
@@ -927,7 +912,7 @@ struct Ctx : public wh_ctx {
   // X[R][K] W^T into the split-K partial slabs part[z][R][N]: k_proj where a tile
   // configuration fits (decode rows <= 112), the k_gemv path otherwise; *ks = z
   // fp16 contexts store the slabs as fp16 (slab_h = 1 after such a partial(); the QKV
-  // projection's too when the self-attention is the pipelined fp16 form): half the bytes
+  // projection's too unless WHISPER_HIP_SLAB16_QKV=0, slab16_qkv below): half the bytes
   // written by every k_proj and read by k_resid_ln / k_reduce_store / k_xattn_seg.  Round 4
   // measured 0.3 % and kept fp32; after round 5's issue-side fixes the 20-window step graph
   // is 3.378 -> 3.276 ms (early) and 3.661 -> 3.559 ms (150 tokens) with it
@@ -942,7 +927,7 @@ struct Ctx : public wh_ctx {
     }();
     return on;
   }
-  // the QKV projection's slabs (read by k_self_attn_qkv's fp16 pipelined form) fp16 too:
+  // the QKV projection's slabs (read by k_self_attn_qkv<T, half_t>) fp16 too:
   // 20-window step graph 3.261 / 3.258 -> 3.255 / 3.246 ms, 3.557 -> 3.546 at 150 tokens
   // (profiles/r05/ab_slab16_qkv.txt).  Tuning build: WHISPER_HIP_SLAB16_QKV=0 keeps them fp32
   static bool slab16_qkv() {
@@ -973,9 +958,7 @@ struct Ctx : public wh_ctx {
     return gemm(X, ldx, W, nullptr, R, N, K, EPI_PARTIAL, g);
   }
 
-  // pf: an L2 prefetch for the next launch, carried by the split-K reduction (round 6)
-  int resid(const T* X, int K, const T* W, const float* b, int R, const float* lg, const float* lb,
-            const L2Prefetch* pf = nullptr) {
+  int resid(const T* X, int K, const T* W, const float* b, int R, const float* lg, const float* lb) {
     const int n = ns;
     GemmArgs g;
     if (R > 128) {
@@ -985,65 +968,10 @@ struct Ctx : public wh_ctx {
     } else {
       int ks = 0;
       TRY(partial(X, K, W, R, n, K, &ks));
-      launch_resid_ln<T>(x_d, part, ks, (int64_t)R * n, b, xn_d, lg, lb, R, n, 1e-5f, st, slab_h, pf);
+      launch_resid_ln<T>(x_d, part, ks, (int64_t)R * n, b, xn_d, lg, lb, R, n, 1e-5f, st, slab_h);
     }
     return 0;
   }
-  // the step cross-attention's W_q head slices into the L2 of the XCDs whose k_xattn_seg
-  // workgroups read them, by the k_resid_ln before it: tuning build only, WHISPER_HIP_XQ_PF=1.
-  // Measured slower (profiles/r06/ab_xq_l2_prefetch.txt: the k_resid_ln 1.4 us longer, the
-  // cross-attention not shorter — its query phase does not wait on L2 misses)
-  static bool xq_pf_on() {
-    static const bool on = [] {
-      const char* e = tune_env("WHISPER_HIP_XQ_PF");
-      return e && e[0] == '1';
-    }();
-    return on;
-  }
-
-  // round-6 probe, tuning build only: WHISPER_HIP_XKV_PF=<workgroups> pulls each layer's
-  // cross K / V through the memory side on a second stream (k_kv_pull), forked after the
-  // previous layer's cross-attention, joined at the end of the layers
-  static int xkv_pf_wg() {
-    static const int v = [] {
-      const char* e = tune_env("WHISPER_HIP_XKV_PF");
-      return e ? atoi(e) : 0;
-    }();
-    return v;
-  }
-  hipStream_t pst = nullptr;
-  std::vector<hipEvent_t> kv_ev;
-  unsigned* kv_sink = nullptr;
-  int kv_pull_setup() {
-    if (pst) return 0;
-    // WHISPER_HIP_XKV_PRIO=1: the pull stream at the device's greatest priority
-    const char* pe = tune_env("WHISPER_HIP_XKV_PRIO");
-    if (pe && pe[0] == '1') {
-      int lo = 0, hi = 0;
-      HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      HIPCHK(hipStreamCreateWithPriority(&pst, hipStreamNonBlocking, hi));
-    } else {
-      HIPCHK(hipStreamCreateWithFlags(&pst, hipStreamNonBlocking));
-    }
-    kv_ev.resize(Ld + 1);
-    for (auto& e : kv_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIPCHK(hipMalloc((void**)&kv_sink, 256));
-    return 0;
-  }
-  int kv_pull(int l, int nwin, const int* wsl) {
-    HIPCHK(hipEventRecord(kv_ev[l], st));
-    HIPCHK(hipStreamWaitEvent(pst, kv_ev[l], 0));
-    const size_t n = ns;
-    launch_kv_pull(ckv + (size_t)(2 * l) * Wcap * TKP * n, ckv + (size_t)(2 * l + 1) * Wcap * TKP * n, wsl, nwin,
-                   (int64_t)TKP * n * sizeof(T), xkv_pf_wg(), kv_sink, pst);
-    return 0;
-  }
-  int kv_join() {
-    HIPCHK(hipEventRecord(kv_ev[Ld], pst));
-    HIPCHK(hipStreamWaitEvent(st, kv_ev[Ld], 0));
-    return 0;
-  }
-
   // out = act(xn W^T + b) for R rows (cross-attention query, MLP fc1): split-K
   // partial slabs + fixed-order reduce in step mode, the direct GEMM otherwise
   int proj(const T* W, const float* b, int R, int N, T* out, int gelu, bool skinny) {
@@ -1080,16 +1008,11 @@ struct Ctx : public wh_ctx {
     if (step && !qkmap && p1_active(R, nwin))
       return dec_layers_p1(R, rw, rs, rp, ancG, nwin, wr0, wnr, wsl, A);
     launch_layernorm<T>(x_d, xn_d, dec[0].ln1_g, dec[0].ln1_b, R, n, 1e-5f, nullptr, st);
-    const bool kvpf = skinny && nwin >= 2 && xkv_pf_wg() > 0;
-    if (kvpf) {
-      TRY(kv_pull_setup());
-      TRY(kv_pull(0, nwin, wsl));
-    }
     for (int l = 0; l < Ld; ++l) {
       auto& e = dec[l];
       if (skinny) {
         int ks = 0;
-        TRY(partial(xn_d, n, e.wqkv, R, 3 * n, n, &ks, slab16_qkv() && self_attn_pipe_on() && !self_attn_grp_mode()));
+        TRY(partial(xn_d, n, e.wqkv, R, 3 * n, n, &ks, slab16_qkv()));
         sa_probe_ks = ks;
         sa_probe_half = slab_h;
         if (launch_self_attn_qkv<T>(part, ks, (int64_t)R * 3 * n, e.bqkv, n, kc[l], vc[l], rw, rs, rp, A, ancG,
@@ -1102,21 +1025,14 @@ struct Ctx : public wh_ctx {
         TRY(gemm(xn_d, n, e.wqkv, e.bqkv, R, 3 * n, n, EPI_QKV_DEC, g));
         launch_self_attn<T>(q_d, n, kc[l], vc[l], rw, rs, rp, A, ancG, Gcap, nh, CTX, att_d, n, R, st);
       }
-      L2Prefetch pf;
-      const bool use_pf = skinny && xq_proj_active(ancG) && xq_pf_on() && xattn_l2_ranges(nwin, nh, ancG, &pf);
-      if (use_pf) {
-        pf.base = reinterpret_cast<const char*>(e.wqx);
-        pf.unit = (int64_t)64 * n * sizeof(T);
-      }
-      TRY(resid(att_d, n, e.wo, e.bo, R, e.lnx_g, e.lnx_b, use_pf ? &pf : nullptr));
+      TRY(resid(att_d, n, e.wo, e.bo, R, e.lnx_g, e.lnx_b));
       // cross-attention query: in step mode its split-K slabs are reduced inside
       // k_cross_attn (rows per window <= Gcap <= 8), otherwise projected directly
       XQPart xq;
       if (skinny) xq = step_xq(ancG);
       if (skinny && xq_proj_active(ancG)) {
         // round 6: no cross-q launch; k_xattn_seg projects the LayerNorm'd rows itself
-        xq.qx = xn_d; xq.qw = e.wqx; xq.bias = e.bqx;
-        if (xq_frag_on()) xq.qwf = e.wqx_f;
+        xq.qx = xn_d; xq.qwf = e.wqx_f; xq.bias = e.bqx;
       } else if (skinny && xq_fused) {
         int ks = 0;
         TRY(partial(xn_d, n, e.wqx, R, n, n, &ks));
@@ -1132,13 +1048,11 @@ struct Ctx : public wh_ctx {
       const T* cv = ckv + (size_t)(2 * l + 1) * Wcap * TKP * n;
       launch_cross_attn<T>(q_d, n, ck, cv, 1500, nh, NSPLIT, nwin, wr0, wnr, wsl, (int64_t)TKP * n, po, pm, pl, att_d,
                            n, R, aqk, qkmap ? qkmap + l * nh : nullptr, qkrows, st, xq);
-      if (kvpf && l + 1 < Ld) TRY(kv_pull(l + 1, nwin, wsl));
       TRY(resid(att_d, n, e.wox, e.box, R, e.ln2_g, e.ln2_b));
       TRY(proj(e.w1, e.b1, R, 4 * n, hm_d, 1, skinny));
       const bool last = l + 1 == Ld;
       TRY(resid(hm_d, 4 * n, e.w2, e.b2, R, last ? ln_g : dec[l + 1].ln1_g, last ? ln_b : dec[l + 1].ln1_b));
     }
-    if (kvpf) TRY(kv_join());
     return 0;
   }
 
@@ -1188,7 +1102,6 @@ struct Ctx : public wh_ctx {
                        {nullptr, n, e.w1, e.b1, 4 * n, EPI_STORE_GELU, e.ln2_g, e.ln2_b, hm_d},
                        {hm_d, 4 * n, e.w2, e.b2, n, EPI_RESID, nullptr, nullptr, nullptr}};
       for (const Q& q : qs) {
-        if (q.W == e.wqx && xq_proj1_active(R)) continue;  // the step projects the cross-q in k_xattn_seg
         g = GemmArgs();
         g.W = q.W; g.bias = q.b; g.M = R; g.N = q.N; g.K = q.K;
         if (q.lg) {
@@ -1219,13 +1132,9 @@ struct Ctx : public wh_ctx {
   std::string step_kernels(int n_win, int group) const override {
     const bool p1 = p1_active(n_win * group, n_win), h = sizeof(T) == 2;
     return std::string("proj=") + (p1 ? "k_proj1" : "k_proj") + ",xattn=k_xattn_seg" +
-           (!p1 && xq_proj_active(group) ? "<qproj>" : p1 && xq_proj1_active(group) ? (xq_proj1_mode() == 2 ? "<qproj-split+ln>" : "<qproj+ln>") : "") +
-           ",self_attn=" +
-           (p1 ? (h && self_attn_kco_on() ? "k_self_attn<kco>" : "k_self_attn")
-               : h && group >= 2 && self_attn_grp_mode() ? "k_self_attn_grp"
-                                                           : h && self_attn_pipe_on() ? (self_attn_kco_on() ? "k_self_attn_qkv<pipe+kco>" : "k_self_attn_qkv<pipe>")
-                                                                                      : "k_self_attn_qkv") +
-           ",tail=" + (p1 && h && ns == 1280 && vocab_select_on() ? "k_vocab_sel" : "vocab+k_logit_part");
+           (!p1 && xq_proj_active(group) ? "<qproj>" : "") + ",self_attn=" +
+           (p1 ? (h ? "k_self_attn<kco>" : "k_self_attn") : h ? "k_self_attn_qkv<pipe+kco>" : "k_self_attn_qkv") +
+           ",tail=vocab+k_logit_part";
   }
 
   int dec_layers_p1(int R, const int* rw, const int* rs, const int* rp, int ancG, int nwin, const int* wr0,
@@ -1267,23 +1176,12 @@ struct Ctx : public wh_ctx {
       TRY(resid(att_d, n, e.wo, e.bo, false));  // deferring it measured +1.0 us on cross-q, -0.2 here
       // cross-attention block
       XQPart xq = step_xq(ancG);
-      if (xq_proj1_active(ancG) && !pend) {
-        // round 6: no cross-q k_proj1 launch; the cross-attention normalises the window's
-        // fp32 rows and projects its query itself
-        xq.qx = xc; xq.qw = e.wqx; xq.bias = e.bqx; xq.ln_g = e.lnx_g; xq.ln_b = e.lnx_b; xq.ln_eps = 1e-5f;
-        if (xq_proj1_mode() == 2) {
-          xq.q_part = xq1_part; xq.q_cnt = xq1_cnt;
-        } else if (xq_frag_on()) {
-          xq.qwf = e.wqx_f;
-        }
-      } else {
-        g = GemmArgs();
-        g.W = e.wqx; g.bias = e.bqx; g.M = R; g.N = n; g.K = n;
-        ln_in(g, e.lnx_g, e.lnx_b);
-        g.out = q_d; g.ldo = n;
-        TRY(p1(g, EPI_STORE, true));
-        ln_done();
-      }
+      g = GemmArgs();
+      g.W = e.wqx; g.bias = e.bqx; g.M = R; g.N = n; g.K = n;
+      ln_in(g, e.lnx_g, e.lnx_b);
+      g.out = q_d; g.ldo = n;
+      TRY(p1(g, EPI_STORE, true));
+      ln_done();
       const T* ck = ckv + (size_t)(2 * l) * Wcap * TKP * n;
       const T* cv = ckv + (size_t)(2 * l + 1) * Wcap * TKP * n;
       launch_cross_attn<T>(q_d, n, ck, cv, 1500, nh, NSPLIT, nwin, wr0, wnr, wsl, (int64_t)TKP * n, po, pm, pl, att_d,
@@ -1525,15 +1423,6 @@ struct Ctx : public wh_ctx {
     const int R = cur_nwin * cur_G;
     TRY(dec_layers(R, st_row_win, st_row_slot, row_pos, cur_G, cur_nwin, st_win_row0, st_win_nrows, st_win_slot,
                    nullptr, nullptr, 0, true));
-    if (final_x && cur_nwin == 1 && sizeof(T) == 2) {
-      // one window (k_proj1 layers): vocabulary, selection and merge in one launch
-      GemmArgs g;
-      g.X = xn_d; g.ldx = ns; g.W = E; g.M = R; g.N = V; g.K = ns; g.out_f32 = logits; g.ldo = V;
-      g.xf32 = final_x; g.ln_g = ln_g; g.ln_b = ln_b; g.ln_eps = 1e-5f;
-      const int rc = launch_vocab_select(g, S, O, merge_embed(), vs_rec, vs_cnt, st);
-      if (rc == 0) return 0;
-      if (rc != -1) return fail(-20, "k_vocab_sel launch failed code " + std::to_string(rc));
-    }
     TRY(vocab(nullptr, R, logits));
     launch_select_merge(logits, V, S, O, cur_nwin, st, merge_embed());
     return 0;
@@ -1614,7 +1503,6 @@ struct Ctx : public wh_ctx {
     if (gexec && key == graph_key) return 0;
     if (gexec) { hipGraphExecDestroy(gexec); gexec = nullptr; }
     if (graph) { hipGraphDestroy(graph); graph = nullptr; }
-    if (xkv_pf_wg() > 0) TRY(kv_pull_setup());  // (no stream / event creation or hipMalloc under capture)
     HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     const int rc = step_body();
     hipGraph_t g = nullptr;
@@ -1642,33 +1530,9 @@ struct Ctx : public wh_ctx {
     }();
     return on;
   }
-  // the fragment-ordered W_q copy for it (WHISPER_HIP_XQ_FRAG=0: the [n][n] rows, A/B)
-  static bool xq_frag_on() {
-    static const bool on = [] {
-      const char* e = tune_env("WHISPER_HIP_XQ_FRAG");
-      return !(e && e[0] == '0');
-    }();
-    return on;
-  }
   bool xq_proj_active(int rows_per_window) const {
     return xq_proj_on() && xattn_fused_q(ns, rows_per_window, (int)sizeof(T));
   }
-  // and in the single-window step (k_proj1 layers: the LayerNorm too): tuning build only,
-  // WHISPER_HIP_XQP1=1.  Measured slower (profiles/r06/ab_xqp1_single_window.txt): at one
-  // window 240 workgroups each ingest the 164 KB W_q slice of their head before any tile can
-  // run, and the cross-attention launch grows 6.1 -> 17.4 us against the 5-7 us the cross-q
-  // k_proj1 launch and its boundary cost (turbo step graph 0.274 -> 0.300 ms)
-  // WHISPER_HIP_XQP1=2: the projection split over each pair's 8 workgroups (k_xattn_seg QV 6)
-  static int xq_proj1_mode() {
-    static const int v = [] {
-      const char* e = tune_env("WHISPER_HIP_XQP1");
-      return e ? atoi(e) : 0;
-    }();
-    return v;
-  }
-  static bool xq_proj1_on() { return xq_proj1_mode() > 0; }
-  bool xq_proj1_active(int rows_per_window) const { return xq_proj1_on() && xq_proj_active(rows_per_window); }
-
   // WHISPER_HIP_EAGER=1 launches the step kernels directly instead of replaying the
   // captured graph (same kernels; used under profilers that do not follow graphs)
   bool eager() const {
@@ -2041,19 +1905,9 @@ struct Ctx : public wh_ctx {
             const T* ck = ckv + (size_t)(2 * l) * Wcap * TKP * n;
             const T* cv = ckv + (size_t)(2 * l + 1) * Wcap * TKP * n;
             XQPart xq = step_xq(cur_G);  // the step's kernel (k_xattn_seg), query from q_d
-            if (p1_active(R, cur_nwin) ? xq_proj1_active(cur_G) : xq_proj_active(cur_G)) {
-              // or projected in the kernel (as the step does): from xn_d, or (single window)
-              // from the fp32 rows with the LayerNorm in the kernel
-              xq.qw = e.wqx; xq.bias = e.bqx;
-              if (xq_frag_on()) xq.qwf = e.wqx_f;
-              if (p1_active(R, cur_nwin)) {
-                xq.qx = x_d; xq.ln_g = e.lnx_g; xq.ln_b = e.lnx_b;
-                if (xq_proj1_mode() == 2) {  // the split projection, as the step runs it
-                  xq.q_part = xq1_part; xq.q_cnt = xq1_cnt; xq.qwf = nullptr;
-                }
-              } else {
-                xq.qx = xn_d;
-              }
+            if (!p1_active(R, cur_nwin) && xq_proj_active(cur_G)) {
+              // or projected in the kernel from xn_d (as the step does)
+              xq.qx = xn_d; xq.qwf = e.wqx_f; xq.bias = e.bqx;
             }
             launch_cross_attn<T>(q_d, n, ck, cv, 1500, nh, NSPLIT, cur_nwin, st_win_row0, st_win_nrows, st_win_slot,
                                  (int64_t)TKP * n, po, pm, pl, att_d, n, R, nullptr, nullptr, 0, st, xq);
