@@ -98,6 +98,38 @@ int wh_log_mel_frames(wh_ctx* ctx, const float* audio, int64_t n_samples, int64_
                       int64_t frame0, int64_t count, int normalize, int64_t* total_frames);
 /* keep audio resident in HBM; wh_log_mel(ctx, NULL, n, ...) then computes from it */
 int wh_audio_upload(wh_ctx* ctx, const float* audio, int64_t n_samples);
+
+/* ---- PCM ingest: a decoded file goes to the device as PCM and becomes the 16 kHz mono
+   float32 waveform there, bit for bit the one whisper/audio.py load_audio makes on the host.
+   pcm is interleaved [n_frames][channels]: int16 (WH_PCM_S16, bits <= 16), int32
+   (WH_PCM_S32, e.g. 24-bit FLAC as wh_flac_decode returns it) or, for WH_PCM_F32, a mono
+   float32 waveform already at 16 kHz (channels = up = down = 1, taps NULL), copied as it
+   is.  For the integer formats, with up = 16000 / g, down = rate / g, g = gcd(rate, 16000),
+   half = 10 * max(up, down), all in fp64:
+     x[m]   = (sum of frame m's channels) * 2^-(bits-1) / channels
+     y[k]   = sum over 0 <= m < n_frames of x[m] * taps[k*down - m*up + half],
+              tap index within [0, 2*half]          (frames outside the file are zeros)
+     out[k] = clip(rint(32768 * y[k]), -32768, 32767) / 32768,   k < ceil(n_frames * up / down)
+   (rint rounds half to even).  taps [n_taps = 2*half + 1] is the host's filter — the library
+   designs none; scipy.signal.resample_poly's is firwin(2*half + 1, 1 / max(up, down),
+   window=("kaiser", 5.0)) * up — and its device copy is cached per (up, down).  up == down
+   skips the filter (taps unused): mix and quantise only.
+   The context keeps the resident audio as segments lying back to back from sample 0:
+   dst_offset = 0 starts a new list, dst_offset = the end of the last segment appends, any
+   other offset is refused.  reserve (0 allowed) is the total the caller will hold; if the
+   buffer has to grow, the samples below dst_offset are kept.  *n_out = samples written.
+   wh_log_mel(ctx, NULL, n, ...) works while there is exactly one segment of length n;
+   wh_log_mel_batch(ctx, NULL, ...) takes the segments as its files.  A null pcm, n_frames < 1,
+   channels < 1, an unknown format, bits outside 1..32 (1..16 for S16), up or down < 1, an
+   n_taps other than 2*half + 1 when up != down, and a bad dst_offset are refused before
+   anything is launched: the resident segments and the context mel stay as they were. */
+enum { WH_PCM_S16 = 0, WH_PCM_S32 = 1, WH_PCM_F32 = 2 };
+int wh_audio_ingest(wh_ctx* ctx, const void* pcm, int format, int64_t n_frames, int channels, int bits,
+                    int up, int down, const double* taps, int n_taps,
+                    int64_t dst_offset, int64_t reserve, int64_t* n_out);
+/* resident samples [offset, offset + n) back to the host */
+int wh_audio_read(wh_ctx* ctx, float* out, int64_t offset, int64_t n);
+
 int wh_mel_max(wh_ctx* ctx, float* gmax);              /* raw log10 max of the last wh_log_mel */
 int wh_mel_normalize(wh_ctx* ctx, float gmax);         /* floor at gmax-8, (x+4)/4 */
 /* log-mel of n_files waveforms, concatenated in `audio` (file i has n_samples[i] floats),
@@ -108,7 +140,10 @@ int wh_mel_normalize(wh_ctx* ctx, float gmax);         /* floor at gmax-8, (x+4)
    then take absolute frames as before.  One upload, one descriptor copy, a constant
    number of launches and one synchronisation, whatever n_files is.  The call takes over
    the resident-audio buffer: a later wh_log_mel(ctx, NULL, n, ...) fails until
-   wh_audio_upload is called again.  n_files < 1, a file with n_samples < 1 or
+   wh_audio_upload is called again.  audio = NULL means the resident segments of
+   wh_audio_ingest: valid only when they are exactly n_files segments of these lengths
+   (otherwise refused, the message says "resident"); nothing is uploaded and the segments
+   stay resident, so the call can be repeated.  n_files < 1, a file with n_samples < 1 or
    n_samples + padding <= 200, and unset filters are refused before anything is launched;
    wh_last_error names the file's index. */
 int wh_log_mel_batch(wh_ctx* ctx, const float* audio, int n_files, const int64_t* n_samples, int64_t padding,
@@ -201,7 +236,8 @@ int wh_dtw(wh_ctx* ctx, const float* x, int n_rows, int n_cols, int* path, int* 
 int wh_step_kernels(wh_ctx* ctx, int n_win, int group, char* buf, int cap);
 
 /* cumulative stage wall times in ms: [0] mel [1] encode [2] prefill [3] steps
-   [4] step count [5] encode windows */
+   [4] step count [5] encode windows; device ms of wh_audio_ingest between HIP events:
+   [6] its host-to-device copies [7] its resampling kernel */
 int wh_stats(wh_ctx* ctx, double* out, int n);
 int wh_sync(wh_ctx* ctx);
 

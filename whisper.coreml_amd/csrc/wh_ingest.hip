@@ -1,0 +1,112 @@
+// PCM ingest kernel of libwhisper_hip (wh_audio_ingest).  A translation unit of its own: the
+// code object of wh_kernels.hip, whose kernels run in every decoder step, stays as it is.
+#include "wh_kernels.h"
+
+namespace wh {
+
+// ---------------------------------------------------------------- PCM ingest
+// Interleaved integer PCM [frames][channels] -> mono float32 at 16 kHz, the arithmetic of
+// whisper/audio.py pcm_to_waveform in fp64 (include/whisper_hip.h, wh_audio_ingest):
+//   x[m] = (sum of the frame's channels) * 2^-(bits-1) / channels   (exact up to the division)
+//   y[k] = sum_m x[m] * taps[k*down - m*up + half],  out[k] = clip(rint(32768 y[k])) / 32768
+// A workgroup owns `block` consecutive outputs.  Their inputs are one contiguous span of
+// frames, mixed down once into LDS (frames before 0 and from n on are zeros, never read);
+// thread k then walks the taps of its phase, taps[phase + j*up], against frames going
+// backwards from mt = (k*down + half) / up.  Every index that grows with the file is 64-bit.
+struct ResampleArgs {
+  const void* pcm;
+  int64_t n, n_out;
+  int channels, up, down, half, block, span_cap;
+  double scale;        // 2^-(bits-1)
+  const double* taps;  // [2*half + 1]; null: no filter (up == down), out[k] is x[k] quantised
+  float* out;
+};
+
+template <typename S>
+__device__ inline double pcm_frame(const S* __restrict__ pcm, int64_t m, int64_t n, int channels, double scale) {
+  if (m < 0 || m >= n) return 0.0;
+  const S* p = pcm + m * channels;
+  int64_t s = 0;
+  for (int c = 0; c < channels; ++c) s += p[c];
+  return (double)s * scale / (double)channels;
+}
+
+// MODE 1, 2: the span goes through LDS (span_cap doubles of dynamic LDS), and in mode 2 the
+// taps lie behind it (short filters: up = 1 gives every thread the same tap, and a vector
+// load of one shared global address costs as much as a gather).  MODE 0: every tap reads its
+// frame from global memory (ratios whose span does not fit, and the no-filter case).
+template <typename S, int MODE>
+__global__ __launch_bounds__(256) void k_pcm_resample(ResampleArgs a) {
+  extern __shared__ __align__(16) double pcm_span[];
+  const S* __restrict__ pcm = (const S*)a.pcm;
+  const int64_t k0 = (int64_t)blockIdx.x * a.block;
+  const int64_t k1 = k0 + a.block < a.n_out ? k0 + a.block : a.n_out;
+  if (k0 >= k1) return;
+  const int last_tap = 2 * a.half;
+  int64_t m_lo = 0;
+  constexpr bool STAGED = MODE != 0;
+  const double* taps_lds = pcm_span + a.span_cap;
+  if (STAGED) {
+    const int64_t m_hi = ((k1 - 1) * a.down + a.half) / a.up;
+    m_lo = (k0 * a.down + a.half) / a.up - last_tap / a.up;
+    const int64_t len = m_hi - m_lo + 1;
+    if (len > a.span_cap) return;  // cannot happen for the block the launcher chose
+    for (int i = threadIdx.x; i < (int)len; i += 256) pcm_span[i] = pcm_frame(pcm, m_lo + i, a.n, a.channels, a.scale);
+    if (MODE == 2)
+      for (int i = threadIdx.x; i <= last_tap; i += 256) pcm_span[a.span_cap + i] = a.taps[i];
+    __syncthreads();
+  }
+  for (int64_t k = k0 + threadIdx.x; k < k1; k += 256) {
+    double y;
+    if (!a.taps) {
+      y = pcm_frame(pcm, k, a.n, a.channels, a.scale);
+    } else {
+      const int64_t c = k * a.down + a.half;
+      int64_t m = c / a.up;                // the newest frame that reaches output k
+      int t = (int)(c - m * a.up);         // and its tap: the thread's phase
+      y = 0.0;
+      int i = (int)(m - m_lo);  // the frame's place in the span
+      for (; t <= last_tap; t += a.up, --m, --i) {
+        const double x = STAGED ? pcm_span[i] : pcm_frame(pcm, m, a.n, a.channels, a.scale);
+        y = fma(x, MODE == 2 ? taps_lds[t] : a.taps[t], y);
+      }
+    }
+    double r = rint(y * 32768.0);  // round half to even, as np.round
+    r = fmin(fmax(r, -32768.0), 32767.0);
+    a.out[k] = (float)r * (1.0f / 32768.0f);
+  }
+}
+
+void launch_pcm_resample(const void* pcm, int s32, int64_t n_frames, int channels, int bits, int up, int down,
+                         const double* taps, float* out, int64_t n_out, hipStream_t st) {
+  if (n_out < 1) return;
+  ResampleArgs a;
+  a.pcm = pcm; a.n = n_frames; a.n_out = n_out; a.channels = channels; a.up = up; a.down = down;
+  a.half = taps ? 10 * (up > down ? up : down) : 0;
+  a.scale = ldexp(1.0, -(bits - 1));
+  a.taps = taps; a.out = out;
+  // the largest block whose span of frames fits 64 KiB of LDS
+  a.block = 0;
+  a.span_cap = 0;
+  if (taps)
+    for (int b = 1024; b >= 256 && !a.block; b /= 2) {
+      const int64_t span = (int64_t)(b - 1) * down / up + 2 * a.half / up + 2;
+      if (span * 8 <= 65536) a.block = b, a.span_cap = (int)span;
+    }
+  const bool staged = a.block != 0;
+  if (!staged) a.block = 1024;
+  const bool taps_in_lds = staged && ((size_t)a.span_cap + 2 * a.half + 1) * 8 <= 65536;
+  const unsigned grid = (unsigned)((n_out + a.block - 1) / a.block);
+  const size_t lds = ((size_t)a.span_cap + (taps_in_lds ? 2 * a.half + 1 : 0)) * 8;
+#define LAUNCH_RESAMPLE(MODE_)                                                                          \
+  do {                                                                                                  \
+    if (s32) k_pcm_resample<int32_t, MODE_><<<grid, 256, lds, st>>>(a), wh_launched("k_pcm_resample"); \
+    else k_pcm_resample<int16_t, MODE_><<<grid, 256, lds, st>>>(a), wh_launched("k_pcm_resample");     \
+  } while (0)
+  if (taps_in_lds) LAUNCH_RESAMPLE(2);
+  else if (staged) LAUNCH_RESAMPLE(1);
+  else LAUNCH_RESAMPLE(0);
+#undef LAUNCH_RESAMPLE
+}
+
+}  // namespace wh

@@ -96,6 +96,12 @@ int mel_blocks(int64_t nframes);  // frame blocks one file takes (whole blocks)
 // segmented log-mel of every file, raw values then each file's own max-8 floor and scaling
 void launch_mel_seg(const float* audio, const MelFile* files, int n_files, int64_t n_blocks, const float* filters,
                     int n_mels, float* mel, int64_t ld, unsigned* gmax, hipStream_t st);
+// wh_audio_ingest's kernel: interleaved int16 (s32 = 0) or int32 PCM [n_frames][channels] of
+// `bits` significant bits -> n_out mono float32 samples at 16 kHz, accumulated in fp64 and
+// quantised to 16-bit steps.  taps [2*10*max(up, down) + 1] doubles on the device, or null
+// when up == down (mix and quantise only).  One launch.
+void launch_pcm_resample(const void* pcm, int s32, int64_t n_frames, int channels, int bits, int up, int down,
+                         const double* taps, float* out, int64_t n_out, hipStream_t st);
 
 // ------------------------------------------------------------ decode state (device)
 // Per window slot w (capacity nw) with G rows (beams / samples) each.

@@ -126,6 +126,9 @@ struct wh_ctx {
   virtual int log_mel_frames(const float* audio, int64_t n, int64_t pad, int n_mels, int64_t frame0, int64_t count,
                              int normalize, int64_t* total_frames) = 0;
   virtual int audio_upload(const float* audio, int64_t n) = 0;
+  virtual int audio_ingest(const void* pcm, int format, int64_t n, int channels, int bits, int up, int down,
+                           const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) = 0;
+  virtual int audio_read(float* out, int64_t offset, int64_t n) = 0;
   virtual int mel_max(float* g) = 0;
   virtual int log_mel_batch(const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
                             int64_t* frame_base) = 0;
@@ -192,6 +195,13 @@ struct Ctx : public wh_ctx {
   // mel
   float* d_audio = nullptr;
   size_t audio_cap = 0;
+  // resident audio: segments (offset, length) lying back to back in d_audio from sample 0
+  // (wh_audio_ingest appends; an upload leaves one; a host wh_log_mel_batch leaves none)
+  std::vector<std::pair<int64_t, int64_t>> audio_segs;
+  void* d_pcm = nullptr;  // wh_audio_ingest: the file's PCM as uploaded
+  size_t pcm_cap = 0;
+  std::map<std::pair<int, int>, double*> d_taps;  // resampling filters by (up, down)
+  Timer tm_in;
   float* d_mel = nullptr;
   size_t mel_cap = 0;
   int64_t mel_frames = 0;
@@ -289,6 +299,8 @@ struct Ctx : public wh_ctx {
     if (wbase) rel(hipFree(wbase), "hipFree(weights)");
     if (abase) rel(hipFree(abase), "hipFree(activations)");
     if (d_audio) rel(hipFree(d_audio), "hipFree(audio)");
+    if (d_pcm) rel(hipFree(d_pcm), "hipFree(pcm)");
+    for (auto& kv : d_taps) rel(hipFree(kv.second), "hipFree(resampling taps)");
     if (d_mel) rel(hipFree(d_mel), "hipFree(mel)");
     for (auto& kv : d_filters) rel(hipFree(kv.second), "hipFree(mel filters)");
     if (d_gmax) rel(hipFree(d_gmax), "hipFree(mel max)");
@@ -324,6 +336,7 @@ struct Ctx : public wh_ctx {
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     tm.create();
+    tm_in.create();
     HIPCHK(hipHostMalloc((void**)&h_done, sizeof(int) * 2 * Wcap));  // two poll buffers
     for (auto& e : poll_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     // ---------------- weights
@@ -616,7 +629,117 @@ struct Ctx : public wh_ctx {
     }
     HIPCHK(hipMemcpyAsync(d_audio, audio, n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
+    one_segment(n);
+    return 0;
+  }
+  void one_segment(int64_t n) {
+    audio_segs.assign(1, std::make_pair((int64_t)0, n));
     audio_n = n;
+  }
+  // room for `need` samples; the first `keep` survive a move to a larger buffer
+  int audio_grow(size_t need, size_t keep) {
+    if (need <= audio_cap) return 0;
+    float* p = nullptr;
+    const size_t cap = std::max<size_t>(need, 16000);
+    HIPCHK(hipMalloc(&p, cap * 4));
+    if (keep && d_audio) {
+      HIPCHK(hipMemcpyAsync(p, d_audio, keep * 4, hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+    if (d_audio) HIPCHK(hipFree(d_audio));
+    d_audio = p;
+    audio_cap = cap;
+    return 0;
+  }
+  // PCM of one file -> mono float32 at 16 kHz, appended to the resident segments at dst
+  // (include/whisper_hip.h).  Everything is checked before the first HIP call.
+  int audio_ingest(const void* pcm, int format, int64_t n, int channels, int bits, int up, int down,
+                   const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) override {
+    const std::string who = "audio_ingest: ";
+    if (!pcm) return fail(-1, who + "null pcm");
+    if (!n_out) return fail(-1, who + "null n_out");
+    if (format != WH_PCM_S16 && format != WH_PCM_S32 && format != WH_PCM_F32)
+      return fail(-7, who + "unknown format " + std::to_string(format));
+    if (n < 1 || n > ((int64_t)1 << 40)) return fail(-7, who + "n_frames = " + std::to_string(n) + " out of range");
+    if (channels < 1 || channels > 256) return fail(-7, who + "channels = " + std::to_string(channels) + " out of range");
+    if (up < 1 || down < 1 || up > (1 << 20) || down > (1 << 20))
+      return fail(-7, who + "up = " + std::to_string(up) + ", down = " + std::to_string(down) + " out of range");
+    const bool f32 = format == WH_PCM_F32;
+    const bool filt = !f32 && up != down;
+    if (f32) {
+      if (channels != 1 || up != 1 || down != 1)
+        return fail(-7, who + "format WH_PCM_F32 is a mono waveform at 16 kHz: channels, up and down must be 1");
+    } else {
+      if (bits < 1 || bits > 32 || (format == WH_PCM_S16 && bits > 16))
+        return fail(-7, who + "bits = " + std::to_string(bits) + " out of range for the format");
+      const int64_t want = 2 * 10 * (int64_t)std::max(up, down) + 1;
+      if (filt && (!taps || n_taps != want))
+        return fail(-7, who + "n_taps = " + std::to_string(taps ? n_taps : 0) + ", the filter of up = " +
+                            std::to_string(up) + ", down = " + std::to_string(down) + " has " + std::to_string(want));
+    }
+    const int64_t end = audio_segs.empty() ? 0 : audio_segs.back().first + audio_segs.back().second;
+    if (dst != 0 && dst != end)
+      return fail(-7, who + "dst_offset = " + std::to_string(dst) + " is neither 0 nor the end of the resident segments (" +
+                          std::to_string(end) + ")");
+    if (reserve < 0) return fail(-7, who + "negative reserve");
+    const int64_t no = filt ? (n * up + down - 1) / down : n;
+    double* dt = nullptr;
+    if (filt) {
+      const auto key = std::make_pair(up, down);
+      auto it = d_taps.find(key);
+      if (it == d_taps.end()) {
+        HIPCHK(hipMalloc(&dt, (size_t)n_taps * 8));
+        if (hipMemcpy(dt, taps, (size_t)n_taps * 8, hipMemcpyHostToDevice) != hipSuccess) {
+          (void)hipFree(dt);
+          return fail(-100, who + "copying the filter taps failed");
+        }
+        d_taps[key] = dt;
+      } else {
+        dt = it->second;
+      }
+    }
+    TRY(audio_grow((size_t)std::max(dst + no, reserve), (size_t)dst));
+    float copy_ms = 0, kernel_ms = 0;
+    if (f32) {
+      HIPCHK(hipEventRecord(tm_in.a, st));
+      HIPCHK(hipMemcpyAsync(d_audio + dst, pcm, (size_t)n * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(hipEventRecord(tm_in.b, st));
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipEventElapsedTime(&copy_ms, tm_in.a, tm_in.b));
+    } else {
+      const size_t bytes = (size_t)n * channels * (format == WH_PCM_S32 ? 4 : 2);
+      if (bytes > pcm_cap) {
+        if (d_pcm) HIPCHK(hipFree(d_pcm));
+        d_pcm = nullptr;
+        pcm_cap = 0;
+        HIPCHK(hipMalloc(&d_pcm, bytes));
+        pcm_cap = bytes;
+      }
+      HIPCHK(hipEventRecord(tm_in.a, st));
+      HIPCHK(hipMemcpyAsync(d_pcm, pcm, bytes, hipMemcpyHostToDevice, st));
+      HIPCHK(hipEventRecord(tm_in.b, st));
+      launch_pcm_resample(d_pcm, format == WH_PCM_S32, n, channels, bits, up, down, dt, d_audio + dst, no, st);
+      HIPCHK(hipEventRecord(tm.b, st));
+      HIPCHK(hipStreamSynchronize(st));
+      TRY(launch_status(__func__));
+      HIPCHK(hipEventElapsedTime(&copy_ms, tm_in.a, tm_in.b));
+      HIPCHK(hipEventElapsedTime(&kernel_ms, tm_in.b, tm.b));
+    }
+    stats[6] += copy_ms;
+    stats[7] += kernel_ms;
+    if (dst == 0) audio_segs.clear();
+    audio_segs.emplace_back(dst, no);
+    audio_n = audio_segs.size() == 1 ? no : -1;
+    *n_out = no;
+    return 0;
+  }
+  int audio_read(float* out, int64_t offset, int64_t n) override {
+    if (!out) return fail(-1, "audio_read: null out");
+    const int64_t end = audio_segs.empty() ? 0 : audio_segs.back().first + audio_segs.back().second;
+    if (offset < 0 || n < 0 || offset + n > end)
+      return fail(-8, "audio_read: [" + std::to_string(offset) + ", " + std::to_string(offset + n) +
+                          ") is outside the " + std::to_string(end) + " resident samples");
+    if (n) HIPCHK(hipMemcpy(out, d_audio + offset, (size_t)n * 4, hipMemcpyDeviceToHost));
     return 0;
   }
   // audio == nullptr: use the resident buffer of wh_audio_upload (n must match)
@@ -653,7 +776,7 @@ struct Ctx : public wh_ctx {
     HIPCHK(hipEventRecord(tm.a, st));
     if (audio) {
       HIPCHK(hipMemcpyAsync(d_audio, audio, n * 4, hipMemcpyHostToDevice, st));
-      audio_n = n;
+      one_segment(n);
     }
     HIPCHK(hipMemsetAsync(d_gmax, 0, 16, st));
     launch_mel(d_audio, n, n + pad, frame0, count, d_filters[n_mels], n_mels, d_mel, count, d_gmax, st);
@@ -676,7 +799,7 @@ struct Ctx : public wh_ctx {
   int log_mel_batch(const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
                     int64_t* frame_base) override {
     if (n_files < 1) return fail(-7, "log_mel_batch: n_files = " + std::to_string(n_files) + ", need at least one file");
-    if (!audio || !n_samples || !frame_base) return fail(-1, "null argument");
+    if (!n_samples || !frame_base) return fail(-1, "null argument");
     if (pad < 0) return fail(-7, "log_mel_batch: negative padding");
     if (!h_filters.count(n_mels)) return fail(-7, "mel filters for n_mels=" + std::to_string(n_mels) + " not set");
     std::vector<MelFile> files(n_files);
@@ -697,13 +820,24 @@ struct Ctx : public wh_ctx {
       blocks += mel_blocks(f.nframes);
     }
     if (blocks > 0x7fffffff) return fail(-7, "log_mel_batch: too many frames for one call");
-    if ((size_t)samples > audio_cap) {
-      if (d_audio) HIPCHK(hipFree(d_audio));
-      d_audio = nullptr;
-      audio_cap = std::max<size_t>(samples, 16000);
-      HIPCHK(hipMalloc(&d_audio, audio_cap * 4));
+    if (!audio) {
+      // the files are the resident segments (wh_audio_ingest), which stay resident
+      bool same = (int)audio_segs.size() == n_files;
+      for (int i = 0; same && i < n_files; ++i)
+        same = audio_segs[i].first == files[i].audio_off && audio_segs[i].second == files[i].n_real;
+      if (!same)
+        return fail(-7, "log_mel_batch: the " + std::to_string(audio_segs.size()) +
+                            " resident segments are not these " + std::to_string(n_files) + " files");
+    } else {
+      if ((size_t)samples > audio_cap) {
+        if (d_audio) HIPCHK(hipFree(d_audio));
+        d_audio = nullptr;
+        audio_cap = std::max<size_t>(samples, 16000);
+        HIPCHK(hipMalloc(&d_audio, audio_cap * 4));
+      }
+      audio_n = -1;  // the buffer now holds several files: no resident audio of any length
+      audio_segs.clear();
     }
-    audio_n = -1;  // the buffer now holds several files: no resident audio of any length
     const size_t need = (size_t)n_mels * frames;
     if (need > mel_cap) {
       if (d_mel) HIPCHK(hipFree(d_mel));
@@ -722,7 +856,7 @@ struct Ctx : public wh_ctx {
     }
     mel_batch_files = 0;
     HIPCHK(hipEventRecord(tm.a, st));
-    HIPCHK(hipMemcpyAsync(d_audio, audio, (size_t)samples * 4, hipMemcpyHostToDevice, st));
+    if (audio) HIPCHK(hipMemcpyAsync(d_audio, audio, (size_t)samples * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_mel_files, files.data(), n_files * sizeof(MelFile), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_gmax_files, 0, (size_t)n_files * 4, st));
     launch_mel_seg(d_audio, d_mel_files, n_files, blocks, d_filters[n_mels], n_mels, d_mel, frames, d_gmax_files, st);
@@ -2110,6 +2244,11 @@ int wh_audio_upload(wh_ctx* ctx, const float* audio, int64_t n) {
   if (!audio || n <= 0) return fail(-1, "bad audio");
   CTXCALL(ctx->audio_upload(audio, n));
 }
+int wh_audio_ingest(wh_ctx* ctx, const void* pcm, int format, int64_t n_frames, int channels, int bits, int up,
+                    int down, const double* taps, int n_taps, int64_t dst_offset, int64_t reserve, int64_t* n_out) {
+  CTXCALL(ctx->audio_ingest(pcm, format, n_frames, channels, bits, up, down, taps, n_taps, dst_offset, reserve, n_out));
+}
+int wh_audio_read(wh_ctx* ctx, float* out, int64_t offset, int64_t n) { CTXCALL(ctx->audio_read(out, offset, n)); }
 int wh_mel_max(wh_ctx* ctx, float* g) { CTXCALL(ctx->mel_max(g)); }
 int wh_log_mel_batch(wh_ctx* ctx, const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
                      int64_t* frame_base) {

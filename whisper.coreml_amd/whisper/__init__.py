@@ -19,7 +19,7 @@ from typing import List, Optional, Union
 
 import numpy as np
 
-from .audio import load_audio, log_mel_spectrogram, pad_or_trim
+from .audio import load_audio, load_audio_device, log_mel_spectrogram, pad_or_trim
 from .backend_hip import HipBackendError
 from .decoding import DecodingOptions, DecodingResult, decode, detect_language
 from .model import ModelDimensions, Whisper
@@ -113,5 +113,5 @@ def load_model(name: str, device: Optional[Union[str, int]] = None, download_roo
 
 
 __all__ = ["available_models", "load_model", "transcribe", "transcribe_batch", "decode", "detect_language", "DecodingOptions",
-           "DecodingResult", "log_mel_spectrogram", "pad_or_trim", "load_audio", "ModelDimensions", "Whisper",
-           "HipBackendError"]
+           "DecodingResult", "log_mel_spectrogram", "pad_or_trim", "load_audio", "load_audio_device", "ModelDimensions",
+           "Whisper", "HipBackendError"]

@@ -35,21 +35,31 @@ def load_audio(file: str, sr: int = SAMPLE_RATE) -> np.ndarray:
     16-bit PCM and scaled by 1/32768.  ffmpeg's own resampling filter is not
     reproduced, so samples differ from the reference's in the low bits wherever the
     file's rate is not ``sr`` (parity unpinned there; exact for 16-bit files at ``sr``)."""
+    return pcm_to_waveform(*read_pcm(file), sr)
+
+
+def read_pcm(file: str):
+    """The file's samples as stored: (pcm [frames][channels], sample rate, bits per sample).
+    FLAC gives int32 (``wh_flac_decode``), 16-bit PCM WAV gives int16."""
     low = file.lower()
     if low.endswith(".flac"):
         from .backend_hip import decode_flac
         with open(file, "rb") as f:
-            pcm, rate, bps = decode_flac(f.read())
-        x = pcm.astype(np.float64) / float(1 << (bps - 1))
-    elif low.endswith(".wav"):
+            return decode_flac(f.read())
+    if low.endswith(".wav"):
         with wave.open(file, "rb") as w:
             if w.getsampwidth() != 2:
                 raise RuntimeError(f"Failed to load audio: {file}: need 16-bit PCM WAV")
-            rate = w.getframerate()
-            x = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, w.getnchannels())
-            x = x.astype(np.float64) / 32768.0
-    else:
-        raise RuntimeError(f"Failed to load audio: {file}: only .flac and 16-bit PCM .wav are supported without ffmpeg")
+            pcm = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, w.getnchannels())
+            return pcm, w.getframerate(), 16
+    raise RuntimeError(f"Failed to load audio: {file}: only .flac and 16-bit PCM .wav are supported without ffmpeg")
+
+
+def pcm_to_waveform(pcm: np.ndarray, rate: int, bits: int, sr: int = SAMPLE_RATE) -> np.ndarray:
+    """Integer PCM [frames][channels] -> mono float32 at ``sr`` on the host, in float64:
+    channel mean, polyphase FIR, 16-bit quantisation, scaling by 1/32768.  The device path
+    (``HipContext.audio_ingest``) gives the same samples bit for bit."""
+    x = np.asarray(pcm).reshape(len(pcm), -1).astype(np.float64) / float(1 << (bits - 1))
     x = x.mean(axis=1)
     if rate != sr:
         from math import gcd
@@ -58,6 +68,26 @@ def load_audio(file: str, sr: int = SAMPLE_RATE) -> np.ndarray:
         x = resample_poly(x, sr // g, rate // g)
     pcm16 = np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)
     return pcm16.astype(np.float32) / 32768.0
+
+
+@lru_cache(maxsize=None)
+def resample_filter(rate: int, sr: int = SAMPLE_RATE):
+    """(up, down, taps) of the rate conversion ``pcm_to_waveform`` does: the float64 FIR
+    ``scipy.signal.resample_poly(x, up, down)`` designs by default, ``2 * 10 * max(up, down) + 1``
+    taps (read-only).  ``rate == sr``: (1, 1, None), there is no filter."""
+    from math import gcd
+    g = gcd(int(rate), int(sr))
+    up, down = int(sr) // g, int(rate) // g
+    if up == down:
+        return 1, 1, None
+    from scipy.signal import firwin
+    half = 10 * max(up, down)
+    taps = np.ascontiguousarray(firwin(2 * half + 1, 1.0 / max(up, down), window=("kaiser", 5.0)) * up, np.float64)
+    taps.setflags(write=False)
+    return up, down, taps
+
+
+MAX_DEVICE_TAPS = 32769  # longer filters (rates nearly coprime with 16000) are resampled on the host
 
 
 def pad_or_trim(array, length: int = N_SAMPLES, *, axis: int = -1):
@@ -132,6 +162,31 @@ def _device_index(device) -> int:
     if s.startswith("cpu"):
         raise RuntimeError("the whisper HIP backend computes on an AMD GPU only (device='cpu' is not supported)")
     return int(s.split(":")[1]) if ":" in s else 0
+
+
+def device_filter_taps(rate: int, sr: int = SAMPLE_RATE) -> int:
+    """Taps of the filter ``resample_filter(rate)`` would design (0: none), without designing it."""
+    from math import gcd
+    g = gcd(int(rate), int(sr))
+    up, down = int(sr) // g, int(rate) // g
+    return 0 if up == down else 2 * 10 * max(up, down) + 1
+
+
+def load_audio_device(model, file: str):
+    """``load_audio`` whose mixing, resampling and quantisation run on the GPU: the file's
+    PCM is uploaded (int16 or int32) and the 16 kHz waveform is made in the context's
+    resident audio buffer (``HipContext.audio_ingest``), the same samples bit for bit.
+    Returns the ``DeviceAudio`` that ``transcribe`` accepts.  ``model``: a ``Whisper``, a
+    ``HipContext``, or a device (the free-function context of ``log_mel_spectrogram``).
+    A rate whose filter would exceed ``MAX_DEVICE_TAPS`` is resampled on the host and
+    uploaded instead."""
+    ctx = getattr(model, "ctx", model)
+    if ctx is None or isinstance(ctx, (int, str)):
+        ctx = _mel_context(_device_index(ctx))
+    pcm, rate, bits = read_pcm(file)
+    if device_filter_taps(rate) > MAX_DEVICE_TAPS:
+        return ctx.audio_upload(pcm_to_waveform(pcm, rate, bits))
+    return ctx.audio_ingest(pcm, rate, bits)
 
 
 def log_mel_spectrogram(audio: Union[str, np.ndarray], n_mels: int = 80, padding: int = 0,

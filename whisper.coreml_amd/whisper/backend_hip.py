@@ -21,6 +21,7 @@ _DEFAULT_LIB = os.path.join(os.path.dirname(_PKG_DIR), "lib", "libwhisper_hip.so
 
 WH_F32 = 0
 WH_F16 = 1
+WH_PCM_S16, WH_PCM_S32, WH_PCM_F32 = 0, 1, 2
 
 
 class HipBackendError(RuntimeError):
@@ -54,6 +55,9 @@ _EXPORTS = {
     "wh_log_mel_frames": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_int64, c_int,
                                   POINTER(c_int64)]),
     "wh_audio_upload": (c_int, [c_void_p, c_void_p, c_int64]),
+    "wh_audio_ingest": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                c_int64, c_int64, POINTER(c_int64)]),
+    "wh_audio_read": (c_int, [c_void_p, c_void_p, c_int64, c_int64]),
     "wh_mel_max": (c_int, [c_void_p, POINTER(c_float)]),
     "wh_mel_normalize": (c_int, [c_void_p, c_float]),
     "wh_log_mel_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p]),
@@ -138,12 +142,15 @@ def decode_flac(data: bytes):
 
 
 class DeviceAudio:
-    """Audio already resident in a context's HBM (``HipContext.audio_upload``);
-    ``transcribe`` then starts from device memory (no host-to-device copy)."""
+    """Audio already resident in a context's HBM (``HipContext.audio_upload`` /
+    ``audio_ingest``); ``transcribe`` then starts from device memory (no host-to-device
+    copy).  ``offset``: where the segment starts in the resident buffer (0 unless it was
+    ingested behind other files)."""
 
-    def __init__(self, ctx, n_samples: int):
+    def __init__(self, ctx, n_samples: int, offset: int = 0):
         self.ctx = ctx
         self.n_samples = n_samples
+        self.offset = offset
 
 
 def max_windows_limit(dims: dict, dtype: str, max_group: int) -> int:
@@ -229,6 +236,49 @@ class HipContext:
         a = np.ascontiguousarray(audio, dtype=np.float32)
         self._check(self.lib.wh_audio_upload(self.h, _ptr(a), a.shape[0]), "wh_audio_upload")
         return DeviceAudio(self, a.shape[0])
+
+    def audio_ingest(self, pcm: np.ndarray, rate: int, bits: int, dst_offset: int = 0,
+                     reserve: int = 0) -> "DeviceAudio":
+        """A decoded file's PCM ([frames][channels] integers of ``bits`` bits at ``rate`` Hz)
+        -> the mono 16 kHz float32 waveform of ``audio.pcm_to_waveform``, computed on the
+        device (wh_audio_ingest) into the resident buffer at sample ``dst_offset`` (0: a new
+        list of segments; the end of the last one: appended).  int16 is uploaded when
+        ``bits <= 16``, else int32.  A 1-D float32 array with ``rate == 16000`` is a
+        waveform: copied unchanged."""
+        from .audio import SAMPLE_RATE, resample_filter
+        a = np.asarray(pcm)
+        n_out = c_int64()
+        if a.dtype == np.float32 and a.ndim == 1 and int(rate) == SAMPLE_RATE:
+            a = np.ascontiguousarray(a)
+            args = (_ptr(a), WH_PCM_F32, a.shape[0], 1, 32, 1, 1, None, 0)
+        else:
+            if not np.issubdtype(a.dtype, np.integer):
+                raise TypeError(f"audio_ingest: integer PCM or a float32 waveform at {SAMPLE_RATE} Hz, not "
+                                f"{a.dtype} at {rate} Hz")
+            a = a.reshape(a.shape[0], -1)
+            fmt = WH_PCM_S16 if bits <= 16 else WH_PCM_S32
+            a = np.ascontiguousarray(a, dtype=np.int16 if fmt == WH_PCM_S16 else np.int32)
+            up, down, taps = resample_filter(int(rate))
+            args = (_ptr(a), fmt, a.shape[0], a.shape[1], int(bits), up, down,
+                    None if taps is None else _ptr(taps), 0 if taps is None else taps.shape[0])
+        self._check(self.lib.wh_audio_ingest(self.h, *args, int(dst_offset), int(reserve), ctypes.byref(n_out)),
+                    "wh_audio_ingest")
+        return DeviceAudio(self, n_out.value, int(dst_offset))
+
+    def audio_read(self, offset: int, n: int) -> np.ndarray:
+        """Resident samples [offset, offset + n) as a host array."""
+        out = np.empty(max(int(n), 0), dtype=np.float32)
+        self._check(self.lib.wh_audio_read(self.h, _ptr(out), int(offset), int(n)), "wh_audio_read")
+        return out
+
+    def log_mel_batch_resident(self, n_samples: Sequence[int], n_mels: int, padding: int = 0) -> np.ndarray:
+        """``log_mel_batch`` of the resident segments (``audio_ingest`` back to back), which
+        must be exactly these lengths; nothing is uploaded and they stay resident."""
+        n = np.asarray(list(n_samples), dtype=np.int64)
+        base = np.zeros(len(n) + 1, dtype=np.int64)
+        self._check(self.lib.wh_log_mel_batch(self.h, None, len(n), _ptr(n) if len(n) else None, int(padding), n_mels,
+                                              _ptr(base)), "wh_log_mel_batch")
+        return base
 
     def log_mel_resident(self, n_samples: int, n_mels: int, padding: int = 0, normalize: bool = True) -> int:
         nf = c_int64()
@@ -429,7 +479,8 @@ class HipContext:
     def stats(self) -> dict:
         out = (c_double * 8)()
         self._check(self.lib.wh_stats(self.h, out, 8), "wh_stats")
-        keys = ["mel_ms", "encode_ms", "prefill_ms", "steps_ms", "steps", "encode_windows"]
+        keys = ["mel_ms", "encode_ms", "prefill_ms", "steps_ms", "steps", "encode_windows", "ingest_copy_ms",
+                "ingest_kernel_ms"]
         return {k: out[i] for i, k in enumerate(keys)}
 
     def sync(self):

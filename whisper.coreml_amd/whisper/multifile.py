@@ -7,19 +7,23 @@ each file is a lane (``transcribe._Lane``, the reference loop's state for one fi
 and every round encodes and decodes the next window of all live lanes together —
 the batched encoder, the batched step graph and ``find_alignment_batch``.
 
-Files are taken in groups whose log-mel fits ``mel_budget_frames``; one
-``log_mel_batch`` call computes a group's mel (each file normalised with its own
-max), the files' frames lying back to back in the context mel.  At most
+Files are taken in groups whose log-mel fits ``mel_budget_frames``.  A group's files
+are ingested back to back into the context's resident audio (a path's PCM is mixed
+down and resampled there, ``HipContext.audio_ingest``; an array is copied), and one
+``log_mel_batch_resident`` call computes the group's mel (each file normalised with
+its own max), the files' frames lying back to back in the context mel.  At most
 ``ctx.max_windows`` lanes are live; a lane that ends hands its slot to the next
 pending file of the group.  ``run_files`` is the scheduler alone, with the GPU work
 behind callables, so it can be driven without a device.
 """
 
+from math import gcd
 from typing import TYPE_CHECKING, Callable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .audio import HOP_LENGTH, N_FRAMES, N_SAMPLES, load_audio
+from .audio import (HOP_LENGTH, MAX_DEVICE_TAPS, N_FRAMES, N_SAMPLES, SAMPLE_RATE, device_filter_taps, pcm_to_waveform,
+                    read_pcm)
 from .backend_hip import DeviceAudio
 from .decoding import DecodingResult, language_probs, next_seed
 from .timing import find_alignment_batch
@@ -158,17 +162,27 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     n_mels = model.dims.n_mels
     if isinstance(audios, (str, np.ndarray, DeviceAudio)):
         raise TypeError("audios must be a sequence of paths and/or 1-D arrays")
-    waves: List[np.ndarray] = []
+    # what audio_ingest takes per file, (pcm or waveform, rate, bits), and the 16 kHz length it gives
+    sources: List[Tuple[np.ndarray, int, int]] = []
+    lengths: List[int] = []
     for i, a in enumerate(audios):
         if isinstance(a, DeviceAudio):
             raise TypeError(f"audio {i}: DeviceAudio is one file resident in the context; pass paths or arrays")
         if isinstance(a, str):
-            a = load_audio(a)
+            pcm, rate, bits = read_pcm(a)
+            if device_filter_taps(rate) <= MAX_DEVICE_TAPS:
+                g = gcd(int(rate), SAMPLE_RATE)
+                up, down = SAMPLE_RATE // g, int(rate) // g
+                sources.append((pcm, rate, bits))
+                lengths.append((len(pcm) * up + down - 1) // down)
+                continue
+            a = pcm_to_waveform(pcm, rate, bits)  # the filter is too long to hold on the device
         a = np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32)
         if a.ndim != 1:
             raise ValueError(f"audio {i} is not 1-D (shape {a.shape})")
-        waves.append(a)
-    n = len(waves)
+        sources.append((a, SAMPLE_RATE, 32))
+        lengths.append(a.shape[0])
+    n = len(sources)
     languages = _per_file(language, n, "language", lambda v: v is None or isinstance(v, str))
     prompts = _per_file(initial_prompt, n, "initial_prompt",
                         lambda v: v is None or isinstance(v, str) or all(_is_number(x) for x in v))
@@ -178,7 +192,16 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     probe = get_tokenizer(model.is_multilingual, num_languages=model.num_languages) if model.is_multilingual else None
 
     def prepare_group(group: List[int]):
-        return ctx.log_mel_batch([waves[i] for i in group], n_mels, padding=N_SAMPLES)
+        # the group's files back to back in the resident buffer (PCM resampled there, arrays
+        # copied), then the log-mel of the resident segments
+        total = sum(lengths[i] for i in group)
+        offset = 0
+        for i in group:
+            seg = ctx.audio_ingest(*sources[i], dst_offset=offset, reserve=total)
+            if seg.n_samples != lengths[i]:
+                raise RuntimeError(f"audio {i}: {seg.n_samples} samples ingested, {lengths[i]} planned")
+            offset += seg.n_samples
+        return ctx.log_mel_batch_resident([lengths[i] for i in group], n_mels, padding=N_SAMPLES)
 
     def detect(group: List[int], bases) -> None:
         """Language of every file of the group that has none: the first window of up to
@@ -238,7 +261,7 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
         return find_alignment_batch(model, toks[0], [lane.text_tokens() for _, lane, _ in kept],
                                     [size for _, _, size in kept], [slot for slot, _, _ in kept], tokenizers=toks)
 
-    lanes = run_files([w.shape[0] for w in waves], max_windows=ctx.max_windows, mel_budget_frames=mel_budget_frames,
+    lanes = run_files(lengths, max_windows=ctx.max_windows, mel_budget_frames=mel_budget_frames,
                       prepare_group=prepare_group, make_lanes=make_lanes, decode_round=decode_round,
                       align_round=align_round if word_timestamps else None)
     results = []

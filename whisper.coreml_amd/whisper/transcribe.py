@@ -33,7 +33,7 @@ from typing import TYPE_CHECKING, List, Optional, Tuple, Union
 
 import numpy as np
 
-from .audio import FRAMES_PER_SECOND, HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, load_audio
+from .audio import FRAMES_PER_SECOND, HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, load_audio_device
 from .backend_hip import DeviceAudio
 from .decoding import DecodingOptions, DecodingResult, detect_language, next_seed, run_windows
 from .timing import WordTiming, apply_alignment, find_alignment, find_alignment_batch
@@ -226,6 +226,9 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
     _check_fp16(model, decode_options.pop("fp16", True))
     ctx = model.ctx
     n_mels = model.dims.n_mels
+    if isinstance(audio, str) and _mel_prepared is None:
+        # a path: its PCM is mixed down and resampled on the device and stays there
+        audio = load_audio_device(model, audio)
     if _mel_prepared is not None:
         # distributed.run_shard: this rank's frames are already in the context and
         # normalised with the all-reduced max; seeks stay absolute
@@ -238,13 +241,13 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
     elif isinstance(audio, DeviceAudio):
         if audio.ctx is not ctx:
             raise ValueError("DeviceAudio belongs to another model context")
+        if audio.offset:
+            raise ValueError("DeviceAudio is a segment behind other files: transcribe() takes the only resident one")
         resident = audio.n_samples
 
         def compute_mel():
             return ctx.log_mel_resident(resident, n_mels, padding=N_SAMPLES, normalize=mel_max_reduce is None)
     else:
-        if isinstance(audio, str):
-            audio = load_audio(audio)
         audio = np.ascontiguousarray(audio.detach().cpu().numpy() if hasattr(audio, "detach") else audio,
                                      dtype=np.float32)
 
