@@ -237,7 +237,11 @@ int wh_step_kernels(wh_ctx* ctx, int n_win, int group, char* buf, int cap);
 
 /* cumulative stage wall times in ms: [0] mel [1] encode [2] prefill [3] steps
    [4] step count [5] encode windows; device ms of wh_audio_ingest between HIP events:
-   [6] its host-to-device copies [7] its resampling kernel */
+   [6] its host-to-device copies [7] its resampling kernel; device ms of wh_flac_ingest /
+   wh_flac_decode_device on the device path: [8] upload of the stream and the candidate table
+   [9] k_flac_parse [10] k_flac_restore [11] k_flac_gather [12] the resampling kernel; [13] host
+   ms of the candidate index and the chain.  WH_N_STATS values in all. */
+enum { WH_N_STATS = 14 };
 int wh_stats(wh_ctx* ctx, double* out, int n);
 int wh_sync(wh_ctx* ctx);
 
@@ -273,6 +277,43 @@ int wh_flac_info(const uint8_t* data, int64_t n, int* sample_rate, int* channels
                  int64_t* total_samples);
 int wh_flac_decode(const uint8_t* data, int64_t n, int32_t* out, int64_t cap_frames, int64_t* n_frames);
 const char* wh_flac_last_error(void);
+
+/* ---- FLAC decoded frame-parallel.  FLAC frames decode independently, so the stream is cut
+   at frame-header candidates and every candidate is decoded by its own lane (csrc/wh_flacdev.h,
+   one code for the host and the device); the frames that tile the stream from the first one
+   to its end (each ends where the next begins, block sizes summing to STREAMINFO's total) are
+   then gathered into interleaved PCM.  The contract: for every stream this path either gives
+   exactly the PCM wh_flac_decode gives, or it does not run and the call goes through
+   wh_flac_decode: the samples, or the error, are that decoder's.  It runs for 1-8 channels,
+   4-24 bits per sample (frames included) and a known total; a broken chain, a frame past its
+   byte budget (STREAMINFO's maximum frame size, or twice the verbatim size when that is 0), a
+   sample leaving int32, or staging beyond 4 x the PCM size send the stream to the host decoder.
+   Like wh_flac_decode it verifies neither the frame CRC-16 nor the STREAMINFO MD5.
+
+   wh_flac_index: the candidates after the metadata, sorted by byte offset: a sync code
+   (0xFF, then 0xF8 or 0xF9), no reserved block-size / sample-rate / sample-size code, a
+   channel code <= 10 that matches STREAMINFO's channel count, a well-formed UTF-8-style
+   number and a matching header CRC-8.  False candidates inside frame bodies may be among them.
+   offsets [cap], fields [cap][4] = header length, block size, channel assignment, bits per
+   sample; *n_cand = candidates found (all of them, also beyond cap).
+   wh_flac_decode_indexed: wh_flac_decode through the index on the host (no context, no GPU):
+   the CPU twin of the device path.  wh_flac_last_path: 0 if this thread's last
+   wh_flac_decode_indexed ran the indexed path, 1 if it went through wh_flac_decode.
+   wh_flac_decode_device: the device decode alone (upload, parse / restore / gather kernels),
+   PCM copied back as int32 [frames][channels]; *path_out = 0 device, 1 host.
+   wh_flac_ingest: a FLAC stream -> the resident 16 kHz waveform, with wh_audio_ingest's
+   segment semantics (dst_offset, reserve, n_out, the same refusals before the first HIP
+   call) and its arithmetic (the device PCM is int16 for bits <= 16, else int32, and goes
+   through the same resampling kernel).  up, down, taps as for wh_audio_ingest, from the
+   stream's rate (wh_flac_info).  On the host path it calls wh_flac_decode and wh_audio_ingest;
+   an error is reported unchanged and the resident segments and the mel stay as they were. */
+int wh_flac_index(const uint8_t* data, int64_t n, int64_t* offsets, int32_t* fields, int64_t cap, int64_t* n_cand);
+int wh_flac_decode_indexed(const uint8_t* data, int64_t n, int32_t* out, int64_t cap_frames, int64_t* n_frames);
+int wh_flac_last_path(void);
+int wh_flac_decode_device(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int32_t* out, int64_t cap_frames,
+                          int64_t* n_frames, int* path_out);
+int wh_flac_ingest(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int down, const double* taps,
+                   int n_taps, int64_t dst_offset, int64_t reserve, int64_t* n_out, int* path_out);
 
 #ifdef __cplusplus
 }

@@ -5,12 +5,22 @@
 // decorrelation modes) directly; the decoded samples are bit-exact, checked against
 // the MD5 of the unencoded audio that every FLAC stream carries in STREAMINFO
 // (tests/test_audio_io.py).  Down-mixing / resampling happen in Python (audio.py).
+//
+// The second half is the frame-parallel form of the same decoder (wh_flac_index,
+// wh_flac_decode_indexed): an index of frame-header candidates, the per-frame code of
+// wh_flacdev.h run on every candidate, the chain of frames that tile the stream, and the
+// gather into interleaved PCM.  On the host it is the twin of the device path
+// (wh_flacdev.hip, wh_flac_ingest); whenever it cannot vouch for a stream it steps aside
+// for wh_flac_decode, so its samples and errors are that decoder's.  Neither form verifies
+// the frame CRC-16 or the STREAMINFO MD5.  Built with -fwrapv: a damaged stream's
+// predictor may overflow int64, and that wraps instead of being undefined.
 #include <stdint.h>
 #include <string.h>
 
 #include <string>
 #include <vector>
 
+#include "wh_flacdev.h"
 #include "whisper_hip.h"
 
 namespace {
@@ -61,11 +71,7 @@ struct Bits {
   void align() { pos = (pos + 7) & ~int64_t(7); }
 };
 
-struct StreamInfo {
-  int rate = 0, channels = 0, bps = 0;
-  int64_t total = 0;
-  int64_t frames_at = 0;  // byte offset of the first frame
-};
+using StreamInfo = whflac::Info;
 
 std::string g_flac_err;
 
@@ -86,9 +92,9 @@ int parse_header(const uint8_t* d, int64_t n, StreamInfo* si) {
     if (type == 0) {
       Bits b(d + i + 4, len);
       b.u(16);  // min block size
-      b.u(16);  // max block size
+      si->max_block = (int)b.u(16);
       b.u(24);  // min frame size
-      b.u(24);  // max frame size
+      si->max_frame = (int)b.u(24);
       si->rate = (int)b.u(20);
       si->channels = (int)b.u(3) + 1;
       si->bps = (int)b.u(5) + 1;
@@ -144,6 +150,7 @@ bool subframe(Bits& b, int bs, int bps, int64_t* s, std::vector<int32_t>& res) {
     for (int i = 0; i < bs; ++i) s[i] = b.s(bps);
   } else if (type >= 8 && type <= 12) {
     const int order = type - 8;
+    if (order > bs) return false;  // residual() would refuse it; the warm-up must not run first
     for (int i = 0; i < order; ++i) s[i] = b.s(bps);
     res.resize(bs);
     if (!residual(b, bs, order, res.data())) return false;
@@ -160,6 +167,7 @@ bool subframe(Bits& b, int bs, int bps, int64_t* s, std::vector<int32_t>& res) {
     }
   } else if (type >= 32) {
     const int order = type - 31;
+    if (order > bs) return false;
     for (int i = 0; i < order; ++i) s[i] = b.s(bps);
     const int prec = (int)b.u(4) + 1;
     if (prec == 16) return false;
@@ -266,5 +274,129 @@ int wh_flac_decode(const uint8_t* data, int64_t n, int32_t* out, int64_t cap_fra
   *n_frames = done;
   return 0;
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- frame-parallel form
+namespace whflac {
+
+// the next 0xFF byte from i on that a frame header could start at, or -1
+static int64_t next_ff(const uint8_t* data, int64_t n, int64_t i) {
+  if (i + 5 > n) return -1;
+  const void* p = memchr(data + i, 0xFF, (size_t)(n - 4 - i));
+  return p ? (const uint8_t*)p - data : -1;
+}
+
+int flac_plan(const uint8_t* data, int64_t n, Plan* plan) {
+  const int rc = parse_header(data, n, &plan->si);
+  if (rc) return rc;
+  const Info& si = plan->si;
+  plan->cands.clear();
+  plan->stage = 0;
+  if (si.bps < 4 || si.bps > MAX_BITS || si.total < 1) return 1;
+  Cand c;
+  for (int64_t i = next_ff(data, n, si.frames_at); i >= 0; i = next_ff(data, n, i + 1))
+    if (fd_header(data, n, i, si.channels, si.bps, &c)) plan->cands.push_back(c);
+  if (plan->cands.empty() || plan->cands[0].off != si.frames_at) return 1;
+  const int64_t most = STAGE_MULTIPLE * si.total * si.channels;
+  for (Cand& k : plan->cands) {
+    k.slot = plan->stage;
+    plan->stage += (int64_t)k.bs * si.channels;
+    if (plan->stage > most) return 1;
+  }
+  return 0;
+}
+
+bool flac_chain(const Plan& plan, int64_t n, const int64_t* ends, std::vector<int32_t>* frames,
+                std::vector<int64_t>* starts) {
+  frames->clear();
+  starts->clear();
+  int64_t cur = plan.si.frames_at, done = 0;
+  size_t i = 0;
+  while (cur + 2 < n) {  // wh_flac_decode's loop condition
+    while (i < plan.cands.size() && plan.cands[i].off < cur) ++i;
+    if (i == plan.cands.size() || plan.cands[i].off != cur) return false;
+    if (ends[i] <= cur || ends[i] > n) return false;
+    frames->push_back((int32_t)i);
+    starts->push_back(done);
+    done += plan.cands[i].bs;
+    if (done > plan.si.total) return false;
+    cur = ends[i];
+  }
+  starts->push_back(done);
+  return done == plan.si.total;
+}
+
+}  // namespace whflac
+
+namespace {
+thread_local int g_indexed_path = 1;
+}
+
+extern "C" {
+
+int wh_flac_index(const uint8_t* data, int64_t n, int64_t* offsets, int32_t* fields, int64_t cap, int64_t* n_cand) {
+  if (!data || !n_cand || (cap > 0 && (!offsets || !fields))) return ferr(-1, "null argument");
+  StreamInfo si;
+  const int rc = parse_header(data, n, &si);
+  if (rc) return rc;
+  int64_t k = 0;
+  whflac::Cand c;
+  for (int64_t i = whflac::next_ff(data, n, si.frames_at); i >= 0; i = whflac::next_ff(data, n, i + 1)) {
+    if (!whflac::fd_header(data, n, i, si.channels, si.bps, &c)) continue;
+    if (k < cap) {
+      offsets[k] = c.off;
+      fields[4 * k + 0] = c.hdr_len;
+      fields[4 * k + 1] = c.bs;
+      fields[4 * k + 2] = c.chc;
+      fields[4 * k + 3] = c.bps;
+    }
+    ++k;
+  }
+  *n_cand = k;
+  return 0;
+}
+
+int wh_flac_decode_indexed(const uint8_t* data, int64_t n, int32_t* out, int64_t cap_frames, int64_t* n_frames) {
+  using namespace whflac;
+  if (!data || !out || !n_frames) return ferr(-1, "null argument");
+  g_indexed_path = 1;
+  Plan plan;
+  const int rc = flac_plan(data, n, &plan);
+  if (rc < 0) return rc;
+  if (rc == 0 && plan.si.total <= cap_frames) {
+    const int C = plan.si.channels;
+    std::vector<int32_t> stage((size_t)plan.stage);
+    std::vector<Sub> subs(plan.cands.size() * C);
+    std::vector<int64_t> ends(plan.cands.size());
+    for (size_t i = 0; i < plan.cands.size(); ++i)
+      ends[i] = fd_parse_frame(data, n, plan.cands[i], plan.si.max_frame, stage.data() + plan.cands[i].slot,
+                               subs.data() + i * C);
+    std::vector<int32_t> frames;
+    std::vector<int64_t> starts;
+    bool ok = flac_chain(plan, n, ends.data(), &frames, &starts);
+    for (size_t f = 0; ok && f < frames.size(); ++f) {
+      const Cand& c = plan.cands[frames[f]];
+      for (int ch = 0; ch < C; ++ch)
+        ok = fd_restore(stage.data() + c.slot + (int64_t)ch * c.bs, c.bs, subs[(size_t)frames[f] * C + ch]) && ok;
+    }
+    if (ok) {
+      for (size_t f = 0; f < frames.size(); ++f) {
+        const Cand& c = plan.cands[frames[f]];
+        int64_t v[8];
+        for (int i = 0; i < c.bs; ++i) {
+          fd_gather(stage.data() + c.slot, c.bs, c.chc, i, v);
+          for (int ch = 0; ch < C; ++ch) out[(starts[f] + i) * C + ch] = (int32_t)v[ch];
+        }
+      }
+      *n_frames = plan.si.total;
+      g_indexed_path = 0;
+      return 0;
+    }
+  }
+  return wh_flac_decode(data, n, out, cap_frames, n_frames);
+}
+
+int wh_flac_last_path(void) { return g_indexed_path; }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 
 #include "whisper_hip.h"
 #include "wh_align.h"
+#include "wh_flacdev.h"
 #include "wh_gemm.h"
 #include "wh_kernels.h"
 
@@ -129,6 +130,10 @@ struct wh_ctx {
   virtual int audio_ingest(const void* pcm, int format, int64_t n, int channels, int bits, int up, int down,
                            const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) = 0;
   virtual int audio_read(float* out, int64_t offset, int64_t n) = 0;
+  virtual int flac_decode_device(const uint8_t* data, int64_t n, int32_t* out, int64_t cap, int64_t* n_frames,
+                                 int* path) = 0;
+  virtual int flac_ingest(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps,
+                          int64_t dst, int64_t reserve, int64_t* n_out, int* path) = 0;
   virtual int mel_max(float* g) = 0;
   virtual int log_mel_batch(const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
                             int64_t* frame_base) = 0;
@@ -164,7 +169,7 @@ struct wh_ctx {
   int sharers = 0;
   wh_ctx* shares_from = nullptr;
   std::vector<float> token_ms;  // per-token wall ms of each decode_steps chunk
-  double stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double stats[WH_N_STATS] = {0};
   int maxc = 5;
   int maxc_stride = 1;
   int device = 0;
@@ -201,6 +206,18 @@ struct Ctx : public wh_ctx {
   void* d_pcm = nullptr;  // wh_audio_ingest: the file's PCM as uploaded
   size_t pcm_cap = 0;
   std::map<std::pair<int, int>, double*> d_taps;  // resampling filters by (up, down)
+  // wh_flac_ingest / wh_flac_decode_device: the stream, its candidates, their subframe records,
+  // frame ends and staging slots, the chain and its first samples (the restore's flag behind them)
+  uint8_t* fl_bytes = nullptr;
+  whflac::Cand* fl_cands = nullptr;
+  whflac::Sub* fl_subs = nullptr;
+  int64_t* fl_ends = nullptr;
+  int32_t* fl_stage = nullptr;
+  int32_t* fl_chain = nullptr;
+  int64_t* fl_starts = nullptr;
+  size_t fl_bytes_cap = 0, fl_cands_cap = 0, fl_subs_cap = 0, fl_ends_cap = 0, fl_stage_cap = 0, fl_chain_cap = 0,
+         fl_starts_cap = 0;
+  hipEvent_t fl_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   Timer tm_in;
   float* d_mel = nullptr;
   size_t mel_cap = 0;
@@ -300,6 +317,11 @@ struct Ctx : public wh_ctx {
     if (abase) rel(hipFree(abase), "hipFree(activations)");
     if (d_audio) rel(hipFree(d_audio), "hipFree(audio)");
     if (d_pcm) rel(hipFree(d_pcm), "hipFree(pcm)");
+    for (void* p : {(void*)fl_bytes, (void*)fl_cands, (void*)fl_subs, (void*)fl_ends, (void*)fl_stage, (void*)fl_chain,
+                    (void*)fl_starts})
+      if (p) rel(hipFree(p), "hipFree(flac)");
+    for (auto& e : fl_ev)
+      if (e) rel(hipEventDestroy(e), "hipEventDestroy(flac)");
     for (auto& kv : d_taps) rel(hipFree(kv.second), "hipFree(resampling taps)");
     if (d_mel) rel(hipFree(d_mel), "hipFree(mel)");
     for (auto& kv : d_filters) rel(hipFree(kv.second), "hipFree(mel filters)");
@@ -657,6 +679,12 @@ struct Ctx : public wh_ctx {
                    const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) override {
     const std::string who = "audio_ingest: ";
     if (!pcm) return fail(-1, who + "null pcm");
+    TRY(ingest_check(who, format, n, channels, bits, up, down, taps, n_taps, dst, reserve, n_out));
+    return ingest_run(who, pcm, format, n, channels, bits, up, down, taps, n_taps, dst, reserve, n_out);
+  }
+  // what wh_audio_ingest refuses, before any HIP call
+  int ingest_check(const std::string& who, int format, int64_t n, int channels, int bits, int up, int down,
+                   const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) {
     if (!n_out) return fail(-1, who + "null n_out");
     if (format != WH_PCM_S16 && format != WH_PCM_S32 && format != WH_PCM_F32)
       return fail(-7, who + "unknown format " + std::to_string(format));
@@ -682,6 +710,14 @@ struct Ctx : public wh_ctx {
       return fail(-7, who + "dst_offset = " + std::to_string(dst) + " is neither 0 nor the end of the resident segments (" +
                           std::to_string(end) + ")");
     if (reserve < 0) return fail(-7, who + "negative reserve");
+    return 0;
+  }
+  // pcm: the host PCM to upload, or null when the device PCM buffer (d_pcm) already holds it
+  // (wh_flac_ingest's device path; its resampling time goes to stats[12])
+  int ingest_run(const std::string& who, const void* pcm, int format, int64_t n, int channels, int bits, int up,
+                 int down, const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) {
+    const bool f32 = format == WH_PCM_F32;
+    const bool filt = !f32 && up != down;
     const int64_t no = filt ? (n * up + down - 1) / down : n;
     double* dt = nullptr;
     if (filt) {
@@ -708,30 +744,167 @@ struct Ctx : public wh_ctx {
       HIPCHK(hipEventElapsedTime(&copy_ms, tm_in.a, tm_in.b));
     } else {
       const size_t bytes = (size_t)n * channels * (format == WH_PCM_S32 ? 4 : 2);
-      if (bytes > pcm_cap) {
-        if (d_pcm) HIPCHK(hipFree(d_pcm));
-        d_pcm = nullptr;
-        pcm_cap = 0;
-        HIPCHK(hipMalloc(&d_pcm, bytes));
-        pcm_cap = bytes;
-      }
+      if (pcm) TRY(pcm_room(bytes));
       HIPCHK(hipEventRecord(tm_in.a, st));
-      HIPCHK(hipMemcpyAsync(d_pcm, pcm, bytes, hipMemcpyHostToDevice, st));
+      if (pcm) HIPCHK(hipMemcpyAsync(d_pcm, pcm, bytes, hipMemcpyHostToDevice, st));
       HIPCHK(hipEventRecord(tm_in.b, st));
       launch_pcm_resample(d_pcm, format == WH_PCM_S32, n, channels, bits, up, down, dt, d_audio + dst, no, st);
       HIPCHK(hipEventRecord(tm.b, st));
       HIPCHK(hipStreamSynchronize(st));
-      TRY(launch_status(__func__));
+      TRY(launch_status("audio_ingest"));
       HIPCHK(hipEventElapsedTime(&copy_ms, tm_in.a, tm_in.b));
       HIPCHK(hipEventElapsedTime(&kernel_ms, tm_in.b, tm.b));
     }
     stats[6] += copy_ms;
-    stats[7] += kernel_ms;
+    stats[pcm ? 7 : 12] += kernel_ms;
     if (dst == 0) audio_segs.clear();
     audio_segs.emplace_back(dst, no);
     audio_n = audio_segs.size() == 1 ? no : -1;
     *n_out = no;
     return 0;
+  }
+  int pcm_room(size_t bytes) {
+    if (bytes > pcm_cap) {
+      if (d_pcm) HIPCHK(hipFree(d_pcm));
+      d_pcm = nullptr;
+      pcm_cap = 0;
+      HIPCHK(hipMalloc(&d_pcm, bytes));
+      pcm_cap = bytes;
+    }
+    return 0;
+  }
+
+  // ------------------------------------------------------------ FLAC on the device
+  // (include/whisper_hip.h, csrc/wh_flacdev.h).  Device buffers grow to the largest stream seen.
+  template <typename P>
+  int flac_room(P*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return 0;
+    if (p) HIPCHK(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    HIPCHK(hipMalloc(&p, bytes));
+    cap = bytes;
+    return 0;
+  }
+  // The stream of `plan` decoded into d_pcm as interleaved int32 (s32) or int16.  *ran = false:
+  // the chain did not hold or a sample left int32, the device path does not run (d_pcm is
+  // scratch; nothing else of the context was touched).
+  int flac_device(const uint8_t* data, int64_t n, const whflac::Plan& plan, bool s32, bool* ran) {
+    using namespace whflac;
+    *ran = false;
+    const int C = plan.si.channels;
+    const size_t nc = plan.cands.size();
+    if (nc > (size_t)(1 << 24)) return 0;  // lanes are counted in int
+    if (!fl_ev[0])
+      for (auto& e : fl_ev) HIPCHK(hipEventCreate(&e));
+    TRY(flac_room(fl_bytes, fl_bytes_cap, (size_t)n));
+    TRY(flac_room(fl_cands, fl_cands_cap, nc * sizeof(Cand)));
+    TRY(flac_room(fl_subs, fl_subs_cap, nc * C * sizeof(Sub)));
+    TRY(flac_room(fl_ends, fl_ends_cap, nc * 8));
+    TRY(flac_room(fl_stage, fl_stage_cap, (size_t)plan.stage * 4));
+    TRY(flac_room(fl_chain, fl_chain_cap, nc * 4));
+    TRY(flac_room(fl_starts, fl_starts_cap, (nc + 1) * 8 + 8));  // the flag lies behind the starts
+    TRY(pcm_room((size_t)plan.si.total * C * (s32 ? 4 : 2)));
+    HIPCHK(hipEventRecord(fl_ev[0], st));
+    HIPCHK(hipMemcpyAsync(fl_bytes, data, (size_t)n, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(fl_cands, plan.cands.data(), nc * sizeof(Cand), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(fl_ev[1], st));
+    launch_flac_parse(fl_bytes, n, fl_cands, (int)nc, C, plan.si.max_frame, fl_stage, fl_subs, fl_ends, st);
+    HIPCHK(hipEventRecord(fl_ev[2], st));
+    std::vector<int64_t> ends(nc);
+    HIPCHK(hipMemcpyAsync(ends.data(), fl_ends, nc * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(launch_status("flac_decode"));
+    float up_ms = 0, parse_ms = 0, restore_ms = 0, gather_ms = 0;
+    HIPCHK(hipEventElapsedTime(&up_ms, fl_ev[0], fl_ev[1]));
+    HIPCHK(hipEventElapsedTime(&parse_ms, fl_ev[1], fl_ev[2]));
+    stats[8] += up_ms;
+    stats[9] += parse_ms;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> frames;
+    std::vector<int64_t> starts;
+    const bool chained = flac_chain(plan, n, ends.data(), &frames, &starts);
+    stats[13] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (!chained) return 0;
+    const int nf = (int)frames.size();
+    int* d_bad = (int*)(fl_starts + nf + 1);
+    starts.push_back(0);  // the flag, cleared with the same copy
+    HIPCHK(hipMemcpyAsync(fl_chain, frames.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(fl_starts, starts.data(), (size_t)(nf + 2) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(fl_ev[3], st));
+    launch_flac_restore(fl_cands, fl_chain, nf, C, fl_stage, fl_subs, d_bad, st);
+    HIPCHK(hipEventRecord(fl_ev[4], st));
+    launch_flac_gather(fl_cands, fl_chain, fl_starts, nf, C, fl_stage, d_pcm, s32 ? 1 : 0, plan.si.total, st);
+    HIPCHK(hipEventRecord(fl_ev[5], st));
+    int bad = 1;
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(launch_status("flac_decode"));
+    HIPCHK(hipEventElapsedTime(&restore_ms, fl_ev[3], fl_ev[4]));
+    HIPCHK(hipEventElapsedTime(&gather_ms, fl_ev[4], fl_ev[5]));
+    stats[10] += restore_ms;
+    stats[11] += gather_ms;
+    *ran = bad == 0;
+    return 0;
+  }
+  // STREAMINFO and the index, timed into stats[13].  < 0: not a FLAC stream (the host decoder's error)
+  int flac_plan_timed(const uint8_t* data, int64_t n, whflac::Plan* plan) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = whflac::flac_plan(data, n, plan);
+    stats[13] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc < 0) return fail(rc, wh_flac_last_error());
+    return rc;
+  }
+  int flac_decode_device(const uint8_t* data, int64_t n, int32_t* out, int64_t cap, int64_t* n_frames,
+                         int* path) override {
+    if (!data || !out || !n_frames || !path) return fail(-1, "flac_decode_device: null argument");
+    whflac::Plan plan;
+    const int rc = flac_plan_timed(data, n, &plan);
+    if (rc < 0) return rc;
+    if (rc == 0 && plan.si.total <= cap) {
+      bool ran = false;
+      TRY(flac_device(data, n, plan, true, &ran));
+      if (ran) {
+        HIPCHK(hipMemcpy(out, d_pcm, (size_t)plan.si.total * plan.si.channels * 4, hipMemcpyDeviceToHost));
+        *n_frames = plan.si.total;
+        *path = 0;
+        return 0;
+      }
+    }
+    *path = 1;
+    const int hrc = wh_flac_decode(data, n, out, cap, n_frames);
+    return hrc ? fail(hrc, wh_flac_last_error()) : 0;
+  }
+  int flac_ingest(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps, int64_t dst,
+                  int64_t reserve, int64_t* n_out, int* path) override {
+    const std::string who = "flac_ingest: ";
+    if (!data) return fail(-1, who + "null data");
+    if (!path) return fail(-1, who + "null path_out");
+    whflac::Plan plan;
+    const int rc = flac_plan_timed(data, n, &plan);
+    if (rc < 0) return rc;
+    const whflac::Info& si = plan.si;
+    const int format = si.bps <= 16 ? WH_PCM_S16 : WH_PCM_S32;
+    if (rc == 0) {
+      TRY(ingest_check(who, format, si.total, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out));
+      bool ran = false;
+      TRY(flac_device(data, n, plan, format == WH_PCM_S32, &ran));
+      if (ran) {
+        *path = 0;
+        return ingest_run(who, nullptr, format, si.total, si.channels, si.bps, up, down, taps, n_taps, dst, reserve,
+                          n_out);
+      }
+    }
+    // the host decoder and the PCM ingest, as a caller without this entry point would run them
+    *path = 1;
+    const int64_t cap = si.total > 0 ? si.total : n * 8;
+    std::vector<int32_t> pcm((size_t)cap * si.channels);
+    int64_t got = 0;
+    const int hrc = wh_flac_decode(data, n, pcm.data(), cap, &got);
+    if (hrc) return fail(hrc, wh_flac_last_error());
+    if (format == WH_PCM_S32) return audio_ingest(pcm.data(), format, got, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out);
+    std::vector<int16_t> pcm16(pcm.begin(), pcm.begin() + (size_t)got * si.channels);
+    return audio_ingest(pcm16.data(), format, got, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out);
   }
   int audio_read(float* out, int64_t offset, int64_t n) override {
     if (!out) return fail(-1, "audio_read: null out");
@@ -2249,6 +2422,14 @@ int wh_audio_ingest(wh_ctx* ctx, const void* pcm, int format, int64_t n_frames, 
   CTXCALL(ctx->audio_ingest(pcm, format, n_frames, channels, bits, up, down, taps, n_taps, dst_offset, reserve, n_out));
 }
 int wh_audio_read(wh_ctx* ctx, float* out, int64_t offset, int64_t n) { CTXCALL(ctx->audio_read(out, offset, n)); }
+int wh_flac_decode_device(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int32_t* out, int64_t cap_frames,
+                          int64_t* n_frames, int* path_out) {
+  CTXCALL(ctx->flac_decode_device(data, n_bytes, out, cap_frames, n_frames, path_out));
+}
+int wh_flac_ingest(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int down, const double* taps, int n_taps,
+                   int64_t dst_offset, int64_t reserve, int64_t* n_out, int* path_out) {
+  CTXCALL(ctx->flac_ingest(data, n_bytes, up, down, taps, n_taps, dst_offset, reserve, n_out, path_out));
+}
 int wh_mel_max(wh_ctx* ctx, float* g) { CTXCALL(ctx->mel_max(g)); }
 int wh_log_mel_batch(wh_ctx* ctx, const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
                      int64_t* frame_base) {
@@ -2309,7 +2490,7 @@ int wh_dtw(wh_ctx* ctx, const float* x, int n_rows, int n_cols, int* path, int* 
 }
 int wh_stats(wh_ctx* ctx, double* out, int n) {
   if (!ctx || !out) return fail(-1, "null argument");
-  for (int i = 0; i < n && i < 8; ++i) out[i] = ctx->stats[i];
+  for (int i = 0; i < n && i < WH_N_STATS; ++i) out[i] = ctx->stats[i];
   return 0;
 }
 int wh_step_kernels(wh_ctx* ctx, int n_win, int group, char* buf, int cap) {

@@ -178,11 +178,20 @@ def load_audio_device(model, file: str):
     resident audio buffer (``HipContext.audio_ingest``), the same samples bit for bit.
     Returns the ``DeviceAudio`` that ``transcribe`` accepts.  ``model``: a ``Whisper``, a
     ``HipContext``, or a device (the free-function context of ``log_mel_spectrogram``).
+    A ``.flac`` file is not decoded on the host at all: its bytes are uploaded and its frames
+    are decoded in parallel on the device (``HipContext.flac_ingest``; ``decoded_on`` of the
+    result says "host" when the stream was outside that path and the host decoder ran).
     A rate whose filter would exceed ``MAX_DEVICE_TAPS`` is resampled on the host and
     uploaded instead."""
     ctx = getattr(model, "ctx", model)
     if ctx is None or isinstance(ctx, (int, str)):
         ctx = _mel_context(_device_index(ctx))
+    if file.lower().endswith(".flac"):
+        from .backend_hip import flac_info
+        with open(file, "rb") as f:
+            data = f.read()
+        if device_filter_taps(flac_info(data)[0]) <= MAX_DEVICE_TAPS:
+            return ctx.flac_ingest(data)
     pcm, rate, bits = read_pcm(file)
     if device_filter_taps(rate) > MAX_DEVICE_TAPS:
         return ctx.audio_upload(pcm_to_waveform(pcm, rate, bits))

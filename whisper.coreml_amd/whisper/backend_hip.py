@@ -91,7 +91,16 @@ _EXPORTS = {
     "wh_flac_info": (c_int, [c_void_p, c_int64, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int64)]),
     "wh_flac_decode": (c_int, [c_void_p, c_int64, c_void_p, c_int64, POINTER(c_int64)]),
     "wh_flac_last_error": (c_char_p, []),
+    "wh_flac_index": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
+    "wh_flac_decode_indexed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, POINTER(c_int64)]),
+    "wh_flac_last_path": (c_int, []),
+    "wh_flac_decode_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_int64),
+                                      POINTER(c_int)]),
+    "wh_flac_ingest": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_int64,
+                               POINTER(c_int64), POINTER(c_int)]),
 }
+N_STATS = 14  # WH_N_STATS
+FLAC_PATHS = ("device", "host")
 
 
 def lib_path() -> str:
@@ -141,16 +150,62 @@ def decode_flac(data: bytes):
     return out[: n.value], rate.value, bps.value
 
 
+def flac_info(data: bytes):
+    """(sample rate, channels, bits per sample, total samples per channel) from STREAMINFO."""
+    lib = load_library()
+    buf = np.frombuffer(data, np.uint8)
+    rate, ch, bps, total = c_int(), c_int(), c_int(), c_int64()
+    rc = lib.wh_flac_info(_ptr(buf), len(buf), ctypes.byref(rate), ctypes.byref(ch), ctypes.byref(bps),
+                          ctypes.byref(total))
+    if rc != 0:
+        raise HipBackendError(f"wh_flac_info failed ({rc}): {lib.wh_flac_last_error().decode(errors='replace')}")
+    return rate.value, ch.value, bps.value, total.value
+
+
+def flac_index(data: bytes):
+    """The frame-header candidates of a FLAC stream (wh_flac_index), sorted by offset:
+    (offsets int64 [n], fields int32 [n][4] = header length, block size, channel assignment,
+    bits per sample).  False candidates inside frame bodies may be among them."""
+    lib = load_library()
+    buf = np.frombuffer(data, np.uint8)
+    n = c_int64()
+    rc = lib.wh_flac_index(_ptr(buf), len(buf), None, None, 0, ctypes.byref(n))
+    if rc != 0:
+        raise HipBackendError(f"wh_flac_index failed ({rc}): {lib.wh_flac_last_error().decode(errors='replace')}")
+    offsets, fields = np.empty(n.value, np.int64), np.empty((n.value, 4), np.int32)
+    lib.wh_flac_index(_ptr(buf), len(buf), _ptr(offsets), _ptr(fields), n.value, ctypes.byref(n))
+    return offsets, fields
+
+
+def decode_flac_indexed(data: bytes):
+    """``decode_flac`` through the frame index on the host (wh_flac_decode_indexed, the CPU
+    twin of the device decoder): (samples, sample_rate, bits_per_sample, path), path "device"
+    when the indexed path ran and "host" when the stream went through wh_flac_decode."""
+    lib = load_library()
+    buf = np.frombuffer(data, np.uint8)
+    rate, ch, bps, total = flac_info(data)
+    cap = total if total > 0 else len(buf) * 8
+    out = np.empty((cap, ch), np.int32)
+    n = c_int64()
+    rc = lib.wh_flac_decode_indexed(_ptr(buf), len(buf), _ptr(out), cap, ctypes.byref(n))
+    if rc != 0:
+        raise HipBackendError(f"wh_flac_decode_indexed failed ({rc}): "
+                              f"{lib.wh_flac_last_error().decode(errors='replace')}")
+    return out[: n.value], rate, bps, FLAC_PATHS[lib.wh_flac_last_path()]
+
+
 class DeviceAudio:
     """Audio already resident in a context's HBM (``HipContext.audio_upload`` /
-    ``audio_ingest``); ``transcribe`` then starts from device memory (no host-to-device
-    copy).  ``offset``: where the segment starts in the resident buffer (0 unless it was
-    ingested behind other files)."""
+    ``audio_ingest`` / ``flac_ingest``); ``transcribe`` then starts from device memory (no
+    host-to-device copy).  ``offset``: where the segment starts in the resident buffer (0
+    unless it was ingested behind other files).  ``decoded_on``: "device" or "host" for a
+    FLAC stream given to ``flac_ingest``, None for anything else."""
 
-    def __init__(self, ctx, n_samples: int, offset: int = 0):
+    def __init__(self, ctx, n_samples: int, offset: int = 0, decoded_on: Optional[str] = None):
         self.ctx = ctx
         self.n_samples = n_samples
         self.offset = offset
+        self.decoded_on = decoded_on
 
 
 def max_windows_limit(dims: dict, dtype: str, max_group: int) -> int:
@@ -264,6 +319,33 @@ class HipContext:
         self._check(self.lib.wh_audio_ingest(self.h, *args, int(dst_offset), int(reserve), ctypes.byref(n_out)),
                     "wh_audio_ingest")
         return DeviceAudio(self, n_out.value, int(dst_offset))
+
+    def flac_ingest(self, data: bytes, dst_offset: int = 0, reserve: int = 0) -> "DeviceAudio":
+        """A FLAC stream -> the waveform of ``audio.load_audio`` in the resident buffer, decoded
+        on the device (wh_flac_ingest: frames in parallel, the PCM never on the host) with
+        ``audio_ingest``'s segment semantics.  ``decoded_on`` of the result tells which decoder
+        ran: "host" means the stream was outside the device path and went through
+        ``decode_flac`` and ``audio_ingest``, with the same samples or the same error."""
+        from .audio import resample_filter
+        buf = np.frombuffer(data, np.uint8)
+        up, down, taps = resample_filter(flac_info(data)[0])
+        n_out, path = c_int64(), c_int(-1)
+        self._check(self.lib.wh_flac_ingest(self.h, _ptr(buf), len(buf), up, down, None if taps is None else _ptr(taps),
+                                            0 if taps is None else taps.shape[0], int(dst_offset), int(reserve),
+                                            ctypes.byref(n_out), ctypes.byref(path)), "wh_flac_ingest")
+        return DeviceAudio(self, n_out.value, int(dst_offset), FLAC_PATHS[path.value])
+
+    def flac_decode_device(self, data: bytes):
+        """``decode_flac`` on the device (wh_flac_decode_device): (samples int32
+        [frames][channels], sample_rate, bits_per_sample, path), path "device" or "host"."""
+        buf = np.frombuffer(data, np.uint8)
+        rate, ch, bps, total = flac_info(data)
+        cap = total if total > 0 else len(buf) * 8
+        out = np.empty((cap, ch), np.int32)
+        n, path = c_int64(), c_int(-1)
+        self._check(self.lib.wh_flac_decode_device(self.h, _ptr(buf), len(buf), _ptr(out), cap, ctypes.byref(n),
+                                                   ctypes.byref(path)), "wh_flac_decode_device")
+        return out[: n.value], rate, bps, FLAC_PATHS[path.value]
 
     def audio_read(self, offset: int, n: int) -> np.ndarray:
         """Resident samples [offset, offset + n) as a host array."""
@@ -477,10 +559,11 @@ class HipContext:
         return path[:, :n.value].copy()
 
     def stats(self) -> dict:
-        out = (c_double * 8)()
-        self._check(self.lib.wh_stats(self.h, out, 8), "wh_stats")
+        out = (c_double * N_STATS)()
+        self._check(self.lib.wh_stats(self.h, out, N_STATS), "wh_stats")
         keys = ["mel_ms", "encode_ms", "prefill_ms", "steps_ms", "steps", "encode_windows", "ingest_copy_ms",
-                "ingest_kernel_ms"]
+                "ingest_kernel_ms", "flac_upload_ms", "flac_parse_ms", "flac_restore_ms", "flac_gather_ms",
+                "flac_resample_ms", "flac_index_ms"]
         return {k: out[i] for i, k in enumerate(keys)}
 
     def sync(self):

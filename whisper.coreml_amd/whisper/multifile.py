@@ -9,7 +9,8 @@ the batched encoder, the batched step graph and ``find_alignment_batch``.
 
 Files are taken in groups whose log-mel fits ``mel_budget_frames``.  A group's files
 are ingested back to back into the context's resident audio (a path's PCM is mixed
-down and resampled there, ``HipContext.audio_ingest``; an array is copied), and one
+down and resampled there, ``HipContext.audio_ingest``; a ``.flac`` path's frames are also
+decoded there, ``HipContext.flac_ingest``; an array is copied), and one
 ``log_mel_batch_resident`` call computes the group's mel (each file normalised with
 its own max), the files' frames lying back to back in the context mel.  At most
 ``ctx.max_windows`` lanes are live; a lane that ends hands its slot to the next
@@ -24,7 +25,7 @@ import numpy as np
 
 from .audio import (HOP_LENGTH, MAX_DEVICE_TAPS, N_FRAMES, N_SAMPLES, SAMPLE_RATE, device_filter_taps, pcm_to_waveform,
                     read_pcm)
-from .backend_hip import DeviceAudio
+from .backend_hip import DeviceAudio, flac_info
 from .decoding import DecodingResult, language_probs, next_seed
 from .timing import find_alignment_batch
 from .tokenizer import LANGUAGES, get_tokenizer
@@ -162,13 +163,25 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     n_mels = model.dims.n_mels
     if isinstance(audios, (str, np.ndarray, DeviceAudio)):
         raise TypeError("audios must be a sequence of paths and/or 1-D arrays")
-    # what audio_ingest takes per file, (pcm or waveform, rate, bits), and the 16 kHz length it gives
-    sources: List[Tuple[np.ndarray, int, int]] = []
+    # what audio_ingest takes per file, (pcm or waveform, rate, bits), or (FLAC bytes,) for
+    # flac_ingest, and the 16 kHz length it gives
+    sources: List[tuple] = []
     lengths: List[int] = []
     for i, a in enumerate(audios):
         if isinstance(a, DeviceAudio):
             raise TypeError(f"audio {i}: DeviceAudio is one file resident in the context; pass paths or arrays")
         if isinstance(a, str):
+            if a.lower().endswith(".flac"):
+                # the compressed bytes wait for the group's turn: flac_ingest decodes them on the device
+                with open(a, "rb") as f:
+                    data = f.read()
+                rate, _, _, frames = flac_info(data)
+                if frames > 0 and device_filter_taps(rate) <= MAX_DEVICE_TAPS:
+                    g = gcd(int(rate), SAMPLE_RATE)
+                    up, down = SAMPLE_RATE // g, int(rate) // g
+                    sources.append((data,))
+                    lengths.append((frames * up + down - 1) // down)
+                    continue
             pcm, rate, bits = read_pcm(a)
             if device_filter_taps(rate) <= MAX_DEVICE_TAPS:
                 g = gcd(int(rate), SAMPLE_RATE)
@@ -197,7 +210,8 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
         total = sum(lengths[i] for i in group)
         offset = 0
         for i in group:
-            seg = ctx.audio_ingest(*sources[i], dst_offset=offset, reserve=total)
+            ingest = ctx.flac_ingest if len(sources[i]) == 1 else ctx.audio_ingest
+            seg = ingest(*sources[i], dst_offset=offset, reserve=total)
             if seg.n_samples != lengths[i]:
                 raise RuntimeError(f"audio {i}: {seg.n_samples} samples ingested, {lengths[i]} planned")
             offset += seg.n_samples
