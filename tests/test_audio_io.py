@@ -79,6 +79,74 @@ def test_load_audio_unsupported(tmp_path):
         load_audio(str(p))
 
 
+def _write_wav(path, rate, frames, channels=2, seed=0):
+    pcm = np.random.default_rng(seed).integers(-20000, 20000, size=(frames, channels), dtype=np.int16)
+    with wave.open(str(path), "wb") as w:
+        w.setnchannels(channels)
+        w.setsampwidth(2)
+        w.setframerate(rate)
+        w.writeframes(pcm.tobytes())
+    return pcm
+
+
+@pytest.mark.parametrize("rate,frames", [(44100, 4411), (48000, 4801), (16000, 1601)])
+def test_ingest_source_pcm_plans_the_resampled_length(tmp_path, rate, frames):
+    from whisper.audio import ingest_source, pcm_to_waveform
+    pcm = _write_wav(tmp_path / "x.wav", rate, frames)
+    for need_length in (False, True):
+        source, length = ingest_source(str(tmp_path / "x.wav"), need_length=need_length)
+        assert isinstance(source, tuple) and len(source) == 3 and source[1:] == (rate, 16)
+        np.testing.assert_array_equal(source[0], pcm)
+        assert length == len(pcm_to_waveform(pcm, rate, 16))
+
+
+def test_ingest_source_flac_stays_compressed():
+    from whisper.audio import ingest_source, load_audio
+    data = open(JFK, "rb").read()
+    for need_length in (False, True):
+        source, length = ingest_source(JFK, need_length=need_length)
+        assert source == (data,)
+        assert length == len(load_audio(JFK))  # 44.1 kHz -> 16 kHz
+
+
+def test_ingest_source_flac_without_total(tmp_path):
+    """STREAMINFO may leave the total unknown: the bytes still go to the device decoder,
+    but a caller that needs the length in advance gets the host-decoded PCM."""
+    from whisper.audio import ingest_source, load_audio
+    from whisper.backend_hip import flac_info
+    data = bytearray(open(JFK, "rb").read())
+    data[8 + 13] &= 0xF0  # the 36-bit total: low nibble of byte 13 and bytes 14-17 of STREAMINFO
+    data[8 + 14:8 + 18] = bytes(4)
+    data = bytes(data)
+    assert flac_info(data) == (44100, 2, 24, 0)
+    p = str(tmp_path / "nototal.flac")
+    open(p, "wb").write(data)
+    assert ingest_source(p) == ((data,), None)
+    source, length = ingest_source(p, need_length=True)
+    assert source[1:] == (44100, 24) and source[0].shape == (485100, 2)
+    assert length == len(load_audio(JFK))
+
+
+def test_ingest_source_resamples_on_the_host_past_the_device_filter(tmp_path):
+    from whisper.audio import MAX_DEVICE_TAPS, device_filter_taps, ingest_source, pcm_to_waveform
+    rate = 16001  # coprime with 16000: a filter of 320 021 taps
+    assert device_filter_taps(rate) > MAX_DEVICE_TAPS
+    pcm = _write_wav(tmp_path / "x.wav", rate, 1601, channels=1)
+    for need_length in (False, True):
+        source, length = ingest_source(str(tmp_path / "x.wav"), need_length=need_length)
+        assert isinstance(source, np.ndarray) and source.dtype == np.float32
+        np.testing.assert_array_equal(source, pcm_to_waveform(pcm, rate, 16))
+        assert length == len(source)
+
+
+def test_ratio():
+    from whisper.audio import _ratio, device_filter_taps, resample_filter
+    assert [_ratio(r) for r in (16000, 44100, 48000, 8000, 16001)] == [
+        (1, 1), (160, 441), (1, 3), (2, 1), (16000, 16001)]
+    assert _ratio(16000, 44100) == (441, 160)
+    assert resample_filter(48000)[:2] == (1, 3) and len(resample_filter(48000)[2]) == device_filter_taps(48000) == 61
+
+
 @pytest.mark.gpu
 def test_mel_from_file_matches_array():
     # reference tests/test_audio.py:15-19, on the GPU log-mel

@@ -10,6 +10,7 @@ libwhisper_hip; the returned array is a host copy.  There is no CPU path.
 import os
 import wave
 from functools import lru_cache
+from math import gcd
 from typing import Optional, Union
 
 import numpy as np
@@ -55,6 +56,12 @@ def read_pcm(file: str):
     raise RuntimeError(f"Failed to load audio: {file}: only .flac and 16-bit PCM .wav are supported without ffmpeg")
 
 
+def _ratio(rate: int, sr: int = SAMPLE_RATE):
+    """(up, down) of the conversion from ``rate`` to ``sr``; n samples give ceil(n * up / down)."""
+    g = gcd(int(rate), int(sr))
+    return int(sr) // g, int(rate) // g
+
+
 def pcm_to_waveform(pcm: np.ndarray, rate: int, bits: int, sr: int = SAMPLE_RATE) -> np.ndarray:
     """Integer PCM [frames][channels] -> mono float32 at ``sr`` on the host, in float64:
     channel mean, polyphase FIR, 16-bit quantisation, scaling by 1/32768.  The device path
@@ -62,10 +69,8 @@ def pcm_to_waveform(pcm: np.ndarray, rate: int, bits: int, sr: int = SAMPLE_RATE
     x = np.asarray(pcm).reshape(len(pcm), -1).astype(np.float64) / float(1 << (bits - 1))
     x = x.mean(axis=1)
     if rate != sr:
-        from math import gcd
         from scipy.signal import resample_poly
-        g = gcd(int(rate), int(sr))
-        x = resample_poly(x, sr // g, rate // g)
+        x = resample_poly(x, *_ratio(rate, sr))
     pcm16 = np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)
     return pcm16.astype(np.float32) / 32768.0
 
@@ -75,9 +80,7 @@ def resample_filter(rate: int, sr: int = SAMPLE_RATE):
     """(up, down, taps) of the rate conversion ``pcm_to_waveform`` does: the float64 FIR
     ``scipy.signal.resample_poly(x, up, down)`` designs by default, ``2 * 10 * max(up, down) + 1``
     taps (read-only).  ``rate == sr``: (1, 1, None), there is no filter."""
-    from math import gcd
-    g = gcd(int(rate), int(sr))
-    up, down = int(sr) // g, int(rate) // g
+    up, down = _ratio(rate, sr)
     if up == down:
         return 1, 1, None
     from scipy.signal import firwin
@@ -166,10 +169,32 @@ def _device_index(device) -> int:
 
 def device_filter_taps(rate: int, sr: int = SAMPLE_RATE) -> int:
     """Taps of the filter ``resample_filter(rate)`` would design (0: none), without designing it."""
-    from math import gcd
-    g = gcd(int(rate), int(sr))
-    up, down = int(sr) // g, int(rate) // g
+    up, down = _ratio(rate, sr)
     return 0 if up == down else 2 * 10 * max(up, down) + 1
+
+
+def ingest_source(file: str, need_length: bool = False):
+    """How a file's audio reaches the device, decided in one place: (source, length).
+    ``source`` is ``(flac bytes,)`` for ``HipContext.flac_ingest`` (the frames are decoded
+    on the device), ``(pcm, rate, bits)`` for ``HipContext.audio_ingest`` (mixed down and
+    resampled on the device), or the 16 kHz waveform as an array when the rate's filter
+    would exceed ``MAX_DEVICE_TAPS`` and the host resampled it.  ``length`` is the 16 kHz
+    sample count the source gives; None for a FLAC whose STREAMINFO has no total, unless
+    ``need_length``: then such a file is decoded on the host instead."""
+    if file.lower().endswith(".flac"):
+        from .backend_hip import flac_info
+        with open(file, "rb") as f:
+            data = f.read()
+        rate, _, _, frames = flac_info(data)
+        if device_filter_taps(rate) <= MAX_DEVICE_TAPS and (frames > 0 or not need_length):
+            up, down = _ratio(rate)
+            return (data,), (frames * up + down - 1) // down if frames > 0 else None
+    pcm, rate, bits = read_pcm(file)
+    if device_filter_taps(rate) > MAX_DEVICE_TAPS:
+        waveform = pcm_to_waveform(pcm, rate, bits)
+        return waveform, len(waveform)
+    up, down = _ratio(rate)
+    return (pcm, rate, bits), (len(pcm) * up + down - 1) // down
 
 
 def load_audio_device(model, file: str):
@@ -182,20 +207,14 @@ def load_audio_device(model, file: str):
     are decoded in parallel on the device (``HipContext.flac_ingest``; ``decoded_on`` of the
     result says "host" when the stream was outside that path and the host decoder ran).
     A rate whose filter would exceed ``MAX_DEVICE_TAPS`` is resampled on the host and
-    uploaded instead."""
+    uploaded instead (``ingest_source`` decides)."""
     ctx = getattr(model, "ctx", model)
     if ctx is None or isinstance(ctx, (int, str)):
         ctx = _mel_context(_device_index(ctx))
-    if file.lower().endswith(".flac"):
-        from .backend_hip import flac_info
-        with open(file, "rb") as f:
-            data = f.read()
-        if device_filter_taps(flac_info(data)[0]) <= MAX_DEVICE_TAPS:
-            return ctx.flac_ingest(data)
-    pcm, rate, bits = read_pcm(file)
-    if device_filter_taps(rate) > MAX_DEVICE_TAPS:
-        return ctx.audio_upload(pcm_to_waveform(pcm, rate, bits))
-    return ctx.audio_ingest(pcm, rate, bits)
+    source, _ = ingest_source(file)
+    if isinstance(source, np.ndarray):
+        return ctx.audio_upload(source)
+    return ctx.flac_ingest(*source) if len(source) == 1 else ctx.audio_ingest(*source)
 
 
 def log_mel_spectrogram(audio: Union[str, np.ndarray], n_mels: int = 80, padding: int = 0,

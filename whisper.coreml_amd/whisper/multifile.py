@@ -4,13 +4,16 @@ Inside a file every window depends on the previous one (seek, prompt carry-over,
 running last-speech time), so ``transcribe()`` with the default options walks it one
 window at a time.  Different files are independent whatever the options are: here
 each file is a lane (``transcribe._Lane``, the reference loop's state for one file)
-and every round encodes and decodes the next window of all live lanes together —
-the batched encoder, the batched step graph and ``find_alignment_batch``.
+and every round takes the next window of all live lanes.  The round itself — encode,
+decode with fallback, apply, one alignment call, finish — is ``transcribe._run_round``,
+the body that the sequential and the clip schedule run too; this module is the third
+driver of it and adds only which lanes are live.
 
 Files are taken in groups whose log-mel fits ``mel_budget_frames``.  A group's files
-are ingested back to back into the context's resident audio (a path's PCM is mixed
-down and resampled there, ``HipContext.audio_ingest``; a ``.flac`` path's frames are also
-decoded there, ``HipContext.flac_ingest``; an array is copied), and one
+are ingested back to back into the context's resident audio (``audio.ingest_source``
+decides how: a path's PCM is mixed down and resampled there, ``HipContext.audio_ingest``;
+a ``.flac`` path's frames are also decoded there, ``HipContext.flac_ingest``; an array is
+copied), and one
 ``log_mel_batch_resident`` call computes the group's mel (each file normalised with
 its own max), the files' frames lying back to back in the context mel.  At most
 ``ctx.max_windows`` lanes are live; a lane that ends hands its slot to the next
@@ -18,18 +21,15 @@ pending file of the group.  ``run_files`` is the scheduler alone, with the GPU w
 behind callables, so it can be driven without a device.
 """
 
-from math import gcd
 from typing import TYPE_CHECKING, Callable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .audio import (HOP_LENGTH, MAX_DEVICE_TAPS, N_FRAMES, N_SAMPLES, SAMPLE_RATE, device_filter_taps, pcm_to_waveform,
-                    read_pcm)
-from .backend_hip import DeviceAudio, flac_info
+from .audio import HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, ingest_source
+from .backend_hip import DeviceAudio
 from .decoding import DecodingResult, language_probs, next_seed
-from .timing import find_alignment_batch
 from .tokenizer import LANGUAGES, get_tokenizer
-from .transcribe import _Lane, _check_fp16, _decode_with_fallback, _plan_file
+from .transcribe import Window, _Lane, _check_fp16, _device_round, _plan_file, _run_round
 
 if TYPE_CHECKING:
     from .model import Whisper
@@ -37,8 +37,6 @@ if TYPE_CHECKING:
 # frames of log-mel one group may hold.  A frame is n_mels floats: at 128 mels this is
 # 2 GiB of mel (plus 2.4 GiB of concatenated audio), about 11 hours of audio per group.
 DEFAULT_MEL_BUDGET_FRAMES = 4_000_000
-
-Window = Tuple["_Lane", int, int, Optional[List[int]]]  # (lane, absolute frame, segment size, prompt)
 
 
 def file_frames(n_samples: int) -> int:
@@ -88,13 +86,7 @@ def run_lanes(lanes: Sequence["_Lane"], max_windows: int, decode_round: Callable
         live = still
         if not windows:
             return
-        results = decode_round(windows)
-        if len(results) != len(windows):
-            raise RuntimeError("decode_round returned %d results for %d windows" % (len(results), len(windows)))
-        kept = [(slot, w[0], w[2]) for slot, (w, r) in enumerate(zip(windows, results)) if w[0].apply(r)]
-        aligns = align_round(kept) if align_round is not None else [None] * len(kept)
-        for (_, lane, _), alignment in zip(kept, aligns):
-            lane.finish(alignment)
+        _run_round(windows, decode_round, align_round)
 
 
 def run_files(n_samples: Sequence[int], *, max_windows: int, mel_budget_frames: int,
@@ -171,25 +163,12 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
         if isinstance(a, DeviceAudio):
             raise TypeError(f"audio {i}: DeviceAudio is one file resident in the context; pass paths or arrays")
         if isinstance(a, str):
-            if a.lower().endswith(".flac"):
-                # the compressed bytes wait for the group's turn: flac_ingest decodes them on the device
-                with open(a, "rb") as f:
-                    data = f.read()
-                rate, _, _, frames = flac_info(data)
-                if frames > 0 and device_filter_taps(rate) <= MAX_DEVICE_TAPS:
-                    g = gcd(int(rate), SAMPLE_RATE)
-                    up, down = SAMPLE_RATE // g, int(rate) // g
-                    sources.append((data,))
-                    lengths.append((frames * up + down - 1) // down)
-                    continue
-            pcm, rate, bits = read_pcm(a)
-            if device_filter_taps(rate) <= MAX_DEVICE_TAPS:
-                g = gcd(int(rate), SAMPLE_RATE)
-                up, down = SAMPLE_RATE // g, int(rate) // g
-                sources.append((pcm, rate, bits))
-                lengths.append((len(pcm) * up + down - 1) // down)
+            # FLAC bytes and PCM wait for the group's turn; the length has to be known before
+            a, length = ingest_source(a, need_length=True)
+            if isinstance(a, tuple):
+                sources.append(a)
+                lengths.append(length)
                 continue
-            a = pcm_to_waveform(pcm, rate, bits)  # the filter is too long to hold on the device
         a = np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32)
         if a.ndim != 1:
             raise ValueError(f"audio {i} is not 1-D (shape {a.shape})")
@@ -258,23 +237,7 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
                                carry_initial_prompt, st, base=int(bases[k]), file_seed=file_seeds[i]))
         return lanes
 
-    def decode_round(windows: List[Window]) -> List[DecodingResult]:
-        seeks = [w[1] for w in windows]
-        sizes = [w[2] for w in windows]
-        ctx.encode(seeks, sizes)
-        model._last_windows = (seeks, sizes)
-        st = windows[0][0].st  # the decoding options and thresholds are the same for every file
-        return _decode_with_fallback(model, st["base"], st["temperatures"], [w[3] for w in windows], st["thresholds"],
-                                     languages=[w[0].language for w in windows],
-                                     seed_keys=[(w[0].file_seed, w[0].window[0]) for w in windows])
-
-    def align_round(kept):
-        if not kept:
-            return []
-        toks = [lane.st["tokenizer"] for _, lane, _ in kept]
-        return find_alignment_batch(model, toks[0], [lane.text_tokens() for _, lane, _ in kept],
-                                    [size for _, _, size in kept], [slot for slot, _, _ in kept], tokenizers=toks)
-
+    decode_round, align_round = _device_round(model, per_file=True)
     lanes = run_files(lengths, max_windows=ctx.max_windows, mel_budget_frames=mel_budget_frames,
                       prepare_group=prepare_group, make_lanes=make_lanes, decode_round=decode_round,
                       align_round=align_round if word_timestamps else None)

@@ -2,25 +2,30 @@
 
 Same options and segment semantics as the reference loop (30 s windows, data-
 dependent ``seek``, temperature fallback, prompt carry-over, no-speech skip,
-empty-segment clearing).  Two schedules:
+empty-segment clearing).
 
-* sequential — the reference order, one window at a time; required whenever a
-  window depends on the previous one (``condition_on_previous_text=True``,
-  ``carry_initial_prompt``, ``hallucination_silence_threshold``);
-* batched — with ``condition_on_previous_text=False`` and several clips
-  (``clip_timestamps`` on a grid), windows of different clips are independent
+There is one loop body and three drivers of it.  The body is ``_Lane`` (the loop's
+state, cut where the GPU work sits: ``next_window`` / ``apply`` / ``finish``) and
+``_run_round`` (windows that share one encode: decode with fallback, apply, one
+alignment call for the windows that were kept, finish); ``_device_round`` is the GPU
+work of a round.  The drivers differ only in which windows they put into a round:
+
+* sequential (``_run_sequential``) — the reference order, one lane, one window at a
+  time; required whenever a window depends on the previous one
+  (``condition_on_previous_text=True``, ``carry_initial_prompt``,
+  ``hallucination_silence_threshold``);
+* batched (``_run_batched``) — with ``condition_on_previous_text=False`` and several
+  clips (``clip_timestamps`` on a grid), windows of different clips are independent
   (each clip's seek is clip-local, the prompt resets every window:
-  transcribe.py:277-287, 513-515), so every round encodes and decodes the next
-  window of *all* unfinished clips together on the GPU.  Segments are assembled
-  in clip order afterwards, which reproduces the reference's output exactly.
-  With word timestamps the alignment of every window runs in the round (GPU);
-  the words are then re-derived in clip order with the reference's running
-  ``last_speech_timestamp``; if that would move any window's seek (it can only
-  through a one-word last segment) the file is re-run sequentially.
-
-The sequential loop's per-file state and body live in ``_Lane``; the sequential
-schedule drives one lane alone, ``multifile.transcribe_batch`` one lane per file with
-the next window of every unfinished file decoded together.
+  transcribe.py:277-287, 513-515), so each clip is a lane and every round takes the
+  next window of *all* unfinished clips.  Segments are assembled in clip order
+  afterwards, which reproduces the reference's output exactly.  With word timestamps
+  the lanes time their words in the round; the words are then re-derived in clip
+  order with the reference's running ``last_speech_timestamp``; if that would move
+  any window's seek (it can only through a one-word last segment) the file is
+  re-run sequentially;
+* many files (``multifile.transcribe_batch``) — a lane per file, the next window of
+  every live file in a round, a freed place refilled from the pending files.
 
 The log-mel of the whole file is computed on the GPU and stays there; windows
 are cut from it on the device.
@@ -36,7 +41,7 @@ import numpy as np
 from .audio import FRAMES_PER_SECOND, HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, load_audio_device
 from .backend_hip import DeviceAudio
 from .decoding import DecodingOptions, DecodingResult, detect_language, next_seed, run_windows
-from .timing import WordTiming, apply_alignment, find_alignment, find_alignment_batch
+from .timing import WordTiming, apply_alignment, find_alignment_batch
 from .tokenizer import LANGUAGES, get_tokenizer
 
 if TYPE_CHECKING:
@@ -70,14 +75,8 @@ def _decode_with_fallback(model, base_opts: DecodingOptions, temperatures, promp
     results: List[Optional[DecodingResult]] = [None] * n
     pending = list(range(n))
     for ti, t in enumerate(temperatures):
-        kw = {}
-        if t > 0:
-            kw = dict(beam_size=None, patience=None)
-        else:
-            kw = dict(best_of=None)
+        kw = dict(beam_size=None, patience=None) if t > 0 else dict(best_of=None)
         opts = replace(base_opts, temperature=t, **kw)
-        if t > 0 and opts.best_of is None:
-            opts = replace(opts, best_of=None)
         calls = [pending]
         if t > 0 and seed_keys is not None:
             calls = [[i] for i in pending]
@@ -311,7 +310,7 @@ def _window_at(seek: int, clip: Tuple[int, int], content_frames: int):
     return segment_size, segment_size * HOP_LENGTH / SAMPLE_RATE
 
 
-def _apply_result(model, result, seek, segment_size, st) -> Tuple[List[dict], int, bool, bool]:
+def _apply_result(result, seek, segment_size, st) -> Tuple[List[dict], int, bool, bool]:
     """no-speech skip (transcribe.py:308-321) then segment split; returns
     (segments, new seek, skipped, single_timestamp_ending).  Empty segments are not
     cleared yet (word timestamps see them first, transcribe.py:412-499)."""
@@ -366,13 +365,6 @@ def _next_words_segment(segments: List[dict]) -> Optional[dict]:
     return next((s for s in segments if s["words"]), None)
 
 
-def _window_alignment(model, st, segs: List[dict], segment_size: int, slot: int):
-    """find_alignment of one window's segments (its audio features in `slot`)."""
-    tok = st["tokenizer"]
-    text_tokens = [t for s in segs for t in s["tokens"] if t < tok.eot]
-    return find_alignment(model, tok, text_tokens, segment_size, slot=slot)
-
-
 def _words_and_seek(st, segs, alignment, seek, previous_seek, segment_size, single_end, last_speech):
     """transcribe.py:412-426 on a precomputed alignment: words of every segment, the
     seek refinement from the last word; returns (seek, last_speech_timestamp)."""
@@ -393,9 +385,9 @@ class _Lane:
     and its prompt, ``apply`` takes the decoded result (no-speech skip, segment
     split), ``finish`` takes the window's word alignment (word timings with the seek
     refinement, hallucination-silence rules, empty-segment clearing, prompt reset).
-    ``_run_sequential`` drives one lane alone; ``transcribe_batch`` drives one lane
-    per file, many at a time.  Seeks are the file's own frames; ``base`` is where the
-    file's frames start in the context mel."""
+    ``_run_sequential`` drives one lane alone, ``_run_batched`` one lane per clip,
+    ``transcribe_batch`` one lane per file.  Seeks are the file's own frames; ``base``
+    is where the file's frames start in the context mel."""
 
     def __init__(self, n_text_ctx: int, clips, initial_prompt_tokens, condition_on_previous_text: bool,
                  carry_initial_prompt: bool, st: dict, base: int = 0, file_seed: int = 0):
@@ -447,7 +439,7 @@ class _Lane:
         seek, segment_size = self.window
         self.result = result
         self.previous_seek = seek
-        self.segs, self.seek, skipped, self.single_end = _apply_result(None, result, seek, segment_size, self.st)
+        self.segs, self.seek, skipped, self.single_end = _apply_result(result, seek, segment_size, self.st)
         return not skipped
 
     def text_tokens(self) -> List[int]:
@@ -517,102 +509,102 @@ class _Lane:
             self.prompt_reset_since = len(self.all_tokens)
 
 
+Window = Tuple[_Lane, int, int, Optional[List[int]]]  # (lane, absolute first frame, segment size, prompt)
+
+
+def _run_round(windows: List[Window], decode_round, align_round=None) -> list:
+    """The loop body of every schedule for windows that share one encode (window i in
+    slot i): ``decode_round(windows)`` gives their results, each lane applies its own,
+    ``align_round`` aligns the windows that were not skipped together ((slot, lane,
+    segment size) each; None: no word timestamps), each lane finishes.  Returns the
+    (lane, alignment) pairs of the windows that were not skipped."""
+    results = decode_round(windows)
+    if len(results) != len(windows):
+        raise RuntimeError("decode_round returned %d results for %d windows" % (len(results), len(windows)))
+    kept = [(slot, w[0], w[2]) for slot, (w, r) in enumerate(zip(windows, results)) if w[0].apply(r)]
+    aligns = align_round(kept) if align_round is not None else [None] * len(kept)
+    done = [(lane, alignment) for (_, lane, _), alignment in zip(kept, aligns)]
+    for lane, alignment in done:
+        lane.finish(alignment)
+    return done
+
+
+def _device_round(model, per_window: bool = True, per_file: bool = False):
+    """(decode_round, align_round) of ``_run_round`` on the model's context.  The lanes
+    share the decoding options, temperatures and thresholds.  ``per_window``: T > 0
+    retries are seeded per window (``_window_seed``), not by the process counter;
+    ``per_file``: every window decodes in its lane's language."""
+    ctx = model.ctx
+
+    def decode_round(windows: List[Window]) -> List[DecodingResult]:
+        seeks = [w[1] for w in windows]
+        sizes = [w[2] for w in windows]
+        ctx.encode(seeks, sizes)
+        model._last_windows = (seeks, sizes)
+        st = windows[0][0].st
+        return _decode_with_fallback(
+            model, st["base"], st["temperatures"], [w[3] for w in windows], st["thresholds"],
+            languages=[w[0].language for w in windows] if per_file else None,
+            seed_keys=[(w[0].file_seed, w[0].window[0]) for w in windows] if per_window else None)
+
+    def align_round(kept):
+        if not kept:
+            return []
+        toks = [lane.st["tokenizer"] for _, lane, _ in kept]
+        return find_alignment_batch(model, toks[0], [lane.text_tokens() for _, lane, _ in kept],
+                                    [size for _, _, size in kept], [slot for slot, _, _ in kept], tokenizers=toks)
+
+    return decode_round, align_round
+
+
 def _run_sequential(model, clips, initial_prompt_tokens, condition_on_previous_text, carry_initial_prompt, st):
     """The reference's order: one lane, one window at a time."""
-    ctx = model.ctx
     lane = _Lane(model.dims.n_text_ctx, clips, initial_prompt_tokens, condition_on_previous_text,
                  carry_initial_prompt, st, file_seed=next_seed())
+    decode_round, align_round = _device_round(model)
     while True:
         window = lane.next_window()
         if window is None:
-            break
-        seek, segment_size, prompt = window
-        ctx.encode([seek], [segment_size])
-        model._last_windows = ([seek], [segment_size])
-        result = _decode_with_fallback(model, st["base"], st["temperatures"], [prompt], st["thresholds"],
-                                       seed_keys=[(lane.file_seed, lane.window[0])])[0]
-        if not lane.apply(result):
-            continue
-        alignment = None
-        if st["word_timestamps"]:
-            alignment = _window_alignment(model, st, lane.segs, segment_size, 0) if lane.segs else []
-        lane.finish(alignment)
-    return lane.segments
+            return lane.segments
+        _run_round([(lane, *window)], decode_round, align_round if st["word_timestamps"] else None)
 
 
 def _run_batched(model, clips, initial_prompt_tokens, st):
-    """Rounds over clips: every unfinished clip contributes its next window."""
-    ctx = model.ctx
-    content_frames = st["content_frames"]
-    seeks = [c[0] for c in clips]
-    live = [True] * len(clips)
-    per_clip: List[List[dict]] = [[] for _ in clips]
-    windows: List[List[tuple]] = [[] for _ in clips]  # word timestamps: per-window records
-    clip_speech = [0.0] * len(clips)
-    first_window = True
-    while any(live):
-        batch = []  # (clip, seek, segment_size)
-        for ci, (cs, ce) in enumerate(clips):
-            if not live[ci]:
-                continue
-            if seeks[ci] < cs:
-                seeks[ci] = cs
-            if seeks[ci] >= ce:
-                live[ci] = False
-                continue
-            segment_size, segment_duration = _window_at(seeks[ci], clips[ci], content_frames)
-            if segment_duration < 1.0:
-                live[ci] = False
-                continue
-            batch.append((ci, seeks[ci], segment_size))
-        if not batch:
-            break
+    """The clip grid: a lane per clip (no prompt of its own, nothing carried over); every
+    round offers the next window of every unfinished clip, in clip order, cut into chunks
+    of ``max_windows``.  A place freed inside a round is not refilled: which windows share
+    a call is part of the result (a lone window takes the single-window step path)."""
+    words = st["word_timestamps"]
+    lanes = [_Lane(model.dims.n_text_ctx, [clip], (), False, False, st) for clip in clips]
+    decode_round, align_round = _device_round(model, per_window=False)
+    # word timestamps: per lane, what the ordered pass needs of every window that was kept
+    records = {lane: [] for lane in lanes}
+    # only the very first window offered sees the initial prompt, and only if it is clip 0's
+    first_prompt = list(initial_prompt_tokens) or None
+    live = lanes
+    while live:
+        batch = [(lane, lane.next_window()) for lane in live]
+        batch = [(lane, *w) for lane, w in batch if w is not None]
+        if batch and batch[0][0] is lanes[0] and first_prompt:
+            batch[0] = (*batch[0][:3], first_prompt)
+        first_prompt = None
+        live = [w[0] for w in batch]
         for b0 in range(0, len(batch), model.ctx.max_windows):
-            chunk = batch[b0:b0 + model.ctx.max_windows]
-            prompts = []
-            for ci, _, _ in chunk:
-                # only the very first window of the file sees the initial prompt
-                prompts.append(initial_prompt_tokens if (first_window and ci == 0 and initial_prompt_tokens) else None)
-            first_window = False
-            ctx.encode([s for _, s, _ in chunk], [z for _, _, z in chunk])
-            model._last_windows = ([s for _, s, _ in chunk], [z for _, _, z in chunk])
-            results = _decode_with_fallback(model, st["base"], st["temperatures"], prompts, st["thresholds"])
-            applied = [_apply_result(model, r, seek, segment_size, st) for (ci, seek, segment_size), r in
-                       zip(chunk, results)]
-            if st["word_timestamps"]:
-                # every window's alignment of this chunk in one batched device call
-                tok = st["tokenizer"]
-                texts = [[t for s_ in a[0] for t in s_["tokens"] if t < tok.eot] for a in applied]
-                aligns = find_alignment_batch(model, tok, texts, [z for _, _, z in chunk], list(range(len(chunk))))
-            for slot, ((ci, seek, segment_size), r) in enumerate(zip(chunk, results)):
-                segs, new_seek, skipped, single_end = applied[slot]
-                if st["word_timestamps"] and not skipped:
-                    alignment = aligns[slot]
-                    # provisional: the clip-local running last-speech time (the true one,
-                    # from the preceding clips, is applied in the ordered pass below)
-                    new_seek = _words_and_seek(st, segs, alignment, new_seek, seek, segment_size, single_end,
-                                               clip_speech[ci])
-                    end = get_end(segs)
-                    if end is not None:
-                        clip_speech[ci] = end
-                    windows[ci].append((seek, segment_size, r, alignment, new_seek))
-                    segs = []
-                elif st["word_timestamps"]:
-                    windows[ci].append((seek, segment_size, r, None, new_seek))
-                _clear_empty(st["tokenizer"], segs)
-                per_clip[ci].extend(segs)
-                seeks[ci] = new_seek
-    if not st["word_timestamps"]:
-        return [s for clip in per_clip for s in clip]
-    # ordered pass: word timings with the running last_speech_timestamp of the
+            kept = _run_round(batch[b0:b0 + model.ctx.max_windows], decode_round, align_round if words else None)
+            if words:
+                for lane, alignment in kept:
+                    records[lane].append((*lane.window, lane.result, alignment, lane.seek))
+    if not words:
+        return [s for lane in lanes for s in lane.segments]
+    # ordered pass: the lanes timed their words with the clip's own running last-speech
+    # time, which gave the seeks above.  Here every kept window's segments and words are
+    # derived again, in clip order, with the running last_speech_timestamp of the
     # reference's sequential loop (transcribe.py:271, 412-426, 485-486); a window whose
     # seek would change under it makes the caller re-run the sequential schedule
     out, last_speech = [], 0.0
-    for ci in range(len(clips)):
-        for seek, segment_size, r, alignment, prov_seek in windows[ci]:
-            if alignment is None:
-                continue
-            segs, new_seek, _, single_end = _apply_result(model, r, seek, segment_size, st)
+    for windows in records.values():
+        for seek, segment_size, r, alignment, prov_seek in windows:
+            segs, new_seek, _, single_end = _apply_result(r, seek, segment_size, st)
             new_seek = _words_and_seek(st, segs, alignment, new_seek, seek, segment_size, single_end, last_speech)
             if new_seek != prov_seek:
                 return None
