@@ -4,8 +4,9 @@ Two windows of one row each is the smallest batch that takes the split-K step: k
 writes partial slabs (fp16 in fp16 contexts) and k_resid_ln sums them into the residual
 and normalises it for the next projection (one window takes the k_proj1 layers instead).
 At widths 772..1024 k_resid_ln's block is 256 threads, the size that once also meant "the
-two-float4 form, fp32 slabs only": fp16 slabs were then read as fp32.  No other test runs a
-width in that range (the teacher-forced tests cover 128, 384 and 1280).
+two-float4 form, fp32 slabs only": fp16 slabs were then read as fp32.  This is the narrow
+regression test of that defect; tests/test_gpu_widths.py runs widths 512, 768 and 1024 over
+every step path (the golden-trajectory teacher-forced tests cover 128, 384 and 1280).
 
 Synthetic medium dimensions with 1 encoder and 2 decoder layers (both forms of the
 residual launch: the next layer's LayerNorm and the final one), seeded weights, two copies

@@ -24,8 +24,16 @@ namespace {
 
 struct Cfg { int nsub, kw, nstep; };
 constexpr Cfg CFGS[] = {{4, 1, 5}, {4, 1, 10}, {5, 1, 10}, {4, 1, 4}, {4, 1, 6},
-                        {4, 1, 20}, {5, 1, 20}, {8, 1, 5}, {8, 1, 10}};
+                        {4, 1, 20}, {5, 1, 20}, {8, 1, 5}, {8, 1, 10},
+                        // last resort, looked at only where none of the above fits: K = 4096 (the
+                        // medium models' fc2 in the step and the first pass: 128 k-steps, z = 16,
+                        // 256 workgroups).  Without it that projection fell to the k_gemv paths,
+                        // whose K split and kernel depend on the row count: a window's logits
+                        // changed between batches of <= 32 and >= 33 rows
+                        // (tests/test_gpu_widths.py::test_step_batch_invariance)
+                        {4, 1, 8}};
 constexpr int NCFG = sizeof(CFGS) / sizeof(CFGS[0]);
+constexpr int NRANKED = NCFG - 1;  // the configurations ranked against each other
 
 typedef void (*KFn)(GemmArgs);
 struct Ent { KFn f; int lds; };
@@ -39,6 +47,8 @@ template <typename T, int MT>
 void row(Ent* e) {
   e[0] = ent<T, MT, 0>(); e[1] = ent<T, MT, 1>(); e[2] = ent<T, MT, 2>(); e[3] = ent<T, MT, 3>(); e[4] = ent<T, MT, 4>();
   e[5] = ent<T, MT, 5>(); e[6] = ent<T, MT, 6>(); e[7] = ent<T, MT, 7>(); e[8] = ent<T, MT, 8>();
+  e[9] = ent<T, MT, 9>();
+  static_assert(NCFG == 10, "one entry per configuration");
 }
 template <typename T>
 struct Table {
@@ -83,6 +93,7 @@ int launch_proj_partial(const GemmArgs& a, int max_z, hipStream_t st, int* z_out
   int best = -1, best_wgs = 0, best_z = 0;
   for (int c = 0; c < NCFG; ++c) {
     const Cfg& k = CFGS[c];
+    if (c >= NRANKED && best >= 0 && forced < 0) break;  // the last resort: only where nothing else fits
     if (S % (k.kw * k.nstep)) continue;
     const int z = S / (k.kw * k.nstep);
     // feasibility at the largest row tile count (MT 7): a configuration whose LDS fits
