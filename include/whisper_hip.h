@@ -242,6 +242,11 @@ int wh_step_kernels(wh_ctx* ctx, int n_win, int group, char* buf, int cap);
    [9] k_flac_parse [10] k_flac_restore [11] k_flac_gather [12] the resampling kernel; [13] host
    ms of the candidate index and the chain.  WH_N_STATS values in all. */
 enum { WH_N_STATS = 14 };
+enum {
+  WH_STAT_MEL_MS = 0, WH_STAT_ENCODE_MS, WH_STAT_PREFILL_MS, WH_STAT_STEPS_MS, WH_STAT_STEPS, WH_STAT_ENCODE_WINDOWS,
+  WH_STAT_INGEST_COPY_MS, WH_STAT_INGEST_KERNEL_MS, WH_STAT_FLAC_UPLOAD_MS, WH_STAT_FLAC_PARSE_MS,
+  WH_STAT_FLAC_RESTORE_MS, WH_STAT_FLAC_GATHER_MS, WH_STAT_FLAC_RESAMPLE_MS, WH_STAT_FLAC_INDEX_MS
+};
 int wh_stats(wh_ctx* ctx, double* out, int n);
 int wh_sync(wh_ctx* ctx);
 

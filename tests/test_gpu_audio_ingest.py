@@ -226,6 +226,45 @@ def test_refused_calls_leave_the_context_alone(jfk_host):
         raw(dst=d.n_samples)
 
 
+# ---------------------------------------------------------------- stage counters
+def test_each_call_charges_its_own_stage_counters():
+    """Which ``wh_stats`` counters a front-end call moves (strictly greater) and that every
+    other one stays bit-equal, on a fresh context.  The FLAC device path starts its ingest
+    with the PCM already on the device, so the copy interval it times is empty:
+    ``ingest_copy_ms`` may stay or grow there, never shrink."""
+    ctx = _fresh_ctx()
+    flac = ("flac_upload_ms", "flac_parse_ms", "flac_restore_ms", "flac_gather_ms", "flac_resample_ms",
+            "flac_index_ms")
+
+    def charged(what, call, moves, may_grow=()):
+        before = ctx.stats()
+        out = call()
+        after = ctx.stats()
+        print(what, {k: (before[k], after[k]) for k in after if after[k] != before[k]})
+        for k in after:
+            if k in moves:
+                assert after[k] > before[k], (what, k, before[k], after[k])
+            elif k in may_grow:
+                assert after[k] >= before[k], (what, k, before[k], after[k])
+            else:
+                assert after[k] == before[k], (what, k, before[k], after[k])
+        return out
+
+    try:
+        rng = np.random.default_rng(5)
+        host = (rng.standard_normal(8000) * 0.1).astype(np.float32)
+        charged("log_mel", lambda: ctx.log_mel(host, 80, padding=PAD), {"mel_ms"})
+        charged("audio_ingest s16", lambda: ctx.audio_ingest(_pcm(rng, 9000, 2, 16), 48000, 16),
+                {"ingest_copy_ms", "ingest_kernel_ms"})
+        charged("audio_ingest f32", lambda: ctx.audio_ingest(host, 16000, 32), {"ingest_copy_ms"})
+        with open(JFK, "rb") as f:
+            data = f.read()
+        d = charged("flac_ingest", lambda: ctx.flac_ingest(data), set(flac), may_grow=("ingest_copy_ms",))
+        assert d.decoded_on == "device" and d.n_samples == 176000
+    finally:
+        ctx.close()
+
+
 # ---------------------------------------------------------------- end to end
 @pytest.fixture(scope="module")
 def micro32():

@@ -1,0 +1,93 @@
+// The audio front end of a context: resident waveforms (upload, PCM ingest, FLAC decoded on
+// the device) and the log-mel spectrogram the encoder reads.  None of it depends on the
+// model's element type, so it is a plain struct compiled once (csrc/wh_audio.hip); the
+// context lends it its stream and its stage counters and reads the mel through mel().
+#pragma once
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "wh_flacdev.h"
+#include "wh_host.h"
+#include "wh_kernels.h"
+
+// the stored log-mel as the encoder reads it: rows of `frames` floats, one per mel bin
+struct MelView {
+  const float* p;
+  int64_t frames, f0;  // f0: the absolute index of the first stored frame
+  int n_mels;
+};
+
+struct AudioFront {
+  int init(hipStream_t stream, double* counters);
+  // every buffer, map entry and event, each release checked
+  void release(Releases& rel);
+  MelView mel() const { return MelView{d_mel.p, mel_frames, mel_f0, mel_nm}; }
+
+  int set_mel_filters(int n_mels, const float* filters);
+  int audio_upload(const float* audio, int64_t n);
+  int audio_ingest(const void* pcm, int format, int64_t n, int channels, int bits, int up, int down,
+                   const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out);
+  int audio_read(float* out, int64_t offset, int64_t n);
+  int flac_decode_device(const uint8_t* data, int64_t n, int32_t* out, int64_t cap, int64_t* n_frames, int* path);
+  int flac_ingest(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps, int64_t dst,
+                  int64_t reserve, int64_t* n_out, int* path);
+  // audio == nullptr: use the resident buffer of wh_audio_upload (n must match)
+  int log_mel(const float* audio, int64_t n, int64_t pad, int n_mels, int normalize, int64_t* nf) {
+    return log_mel_frames(audio, n, pad, n_mels, 0, -1, normalize, nf);
+  }
+  int log_mel_frames(const float* audio, int64_t n, int64_t pad, int n_mels, int64_t frame0, int64_t count,
+                     int normalize, int64_t* total_frames);
+  int log_mel_batch(const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
+                    int64_t* frame_base);
+  int mel_max(float* g);
+  int mel_max_batch(float* g, int n_files);
+  int mel_normalize(float g);
+  int mel_read(float* out, int64_t f0, int64_t nf);
+  int mel_write(const float* mel, int64_t nf, int n_mels);
+
+ private:
+  hipStream_t st = nullptr;  // the context's
+  double* stats = nullptr;   // the context's stage counters (WH_STAT_*)
+  Timer tm;
+
+  DevBuf<float> d_audio;
+  int64_t audio_n = 0;
+  // resident audio: segments (offset, length) lying back to back in d_audio from sample 0
+  // (wh_audio_ingest appends; an upload leaves one; a host wh_log_mel_batch leaves none)
+  std::vector<std::pair<int64_t, int64_t>> audio_segs;
+  DevBuf<char> d_pcm;  // wh_audio_ingest: the file's PCM as uploaded
+  std::map<std::pair<int, int>, double*> d_taps;  // resampling filters by (up, down)
+  // wh_flac_ingest / wh_flac_decode_device: the stream, its candidates, their subframe records,
+  // frame ends and staging slots, the chain and its first samples (the restore's flag behind them)
+  DevBuf<uint8_t> fl_bytes;
+  DevBuf<whflac::Cand> fl_cands;
+  DevBuf<whflac::Sub> fl_subs;
+  DevBuf<int64_t> fl_ends;
+  DevBuf<int32_t> fl_stage;
+  DevBuf<int32_t> fl_chain;
+  DevBuf<int64_t> fl_starts;
+
+  DevBuf<float> d_mel;
+  int64_t mel_frames = 0;
+  int64_t mel_f0 = 0;  // absolute index of the first stored frame
+  int mel_nm = 0;
+  DevBuf<unsigned> gmax;  // the mel's ordered-uint maximum; mel_normalize's override at [4]
+  // wh_log_mel_batch: per-file descriptors and per-file ordered-uint maxima
+  DevBuf<wh::MelFile> mel_files;
+  DevBuf<unsigned> gmax_files;
+  int mel_batch_files = 0;  // files of the last wh_log_mel_batch (0: the mel is not from one)
+  std::map<int, float*> d_filters;
+  std::map<int, std::vector<float>> h_filters;
+
+  void one_segment(int64_t n);
+  int audio_room(size_t samples);
+  void mel_is(int64_t frames, int64_t f0, int n_mels, int batch_files);
+  int ingest_check(const std::string& who, int format, int64_t n, int channels, int bits, int up, int down,
+                   const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out);
+  int ingest_run(const std::string& who, const void* pcm, int format, int64_t n, int channels, int bits, int up,
+                 int down, const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out);
+  int flac_device(const uint8_t* data, int64_t n, const whflac::Plan& plan, bool s32, bool* ran);
+  int flac_plan_timed(const uint8_t* data, int64_t n, whflac::Plan* plan);
+};

@@ -1,0 +1,409 @@
+// The audio front end of a context (csrc/wh_audio.h): host code only, every kernel it
+// launches lives in wh_kernels.hip, wh_ingest.hip or wh_flacdev.hip.
+#include "wh_audio.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+
+#include "whisper_hip.h"
+
+using namespace wh;
+
+// host wall ms since t0, added to a stage counter
+static void charge_host(double& counter, std::chrono::steady_clock::time_point t0) {
+  counter += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int AudioFront::init(hipStream_t stream, double* counters) {
+  st = stream;
+  stats = counters;
+  TRY(tm.create());
+  return gmax.reserve(64);
+}
+
+void AudioFront::release(Releases& rel) {
+  d_audio.release(rel, "hipFree(audio)");
+  d_pcm.release(rel, "hipFree(pcm)");
+  auto flac = [&](auto&... b) { (b.release(rel, "hipFree(flac)"), ...); };
+  flac(fl_bytes, fl_cands, fl_subs, fl_ends, fl_stage, fl_chain, fl_starts);
+  for (auto& kv : d_taps) rel(hipFree(kv.second), "hipFree(resampling taps)");
+  d_mel.release(rel, "hipFree(mel)");
+  for (auto& kv : d_filters) rel(hipFree(kv.second), "hipFree(mel filters)");
+  gmax.release(rel, "hipFree(mel max)");
+  mel_files.release(rel, "hipFree(mel files)");
+  gmax_files.release(rel, "hipFree(mel file max)");
+  tm.release(rel);
+}
+
+int AudioFront::set_mel_filters(int n_mels, const float* filters) {
+  std::vector<float> f(filters, filters + (size_t)n_mels * 201);
+  float* d = nullptr;
+  if (d_filters.count(n_mels)) d = d_filters[n_mels];
+  else {
+    HIPCHK(hipMalloc(&d, f.size() * 4));
+    d_filters[n_mels] = d;
+  }
+  HIPCHK(hipMemcpy(d, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+  h_filters[n_mels] = f;
+  return 0;
+}
+
+// ------------------------------------------------------------ resident audio
+int AudioFront::audio_room(size_t samples) { return d_audio.reserve(std::max<size_t>(samples, 16000) * 4); }
+
+int AudioFront::audio_upload(const float* audio, int64_t n) {
+  TRY(audio_room((size_t)n));
+  HIPCHK(hipMemcpyAsync(d_audio.p, audio, n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  one_segment(n);
+  return 0;
+}
+void AudioFront::one_segment(int64_t n) {
+  audio_segs.assign(1, std::make_pair((int64_t)0, n));
+  audio_n = n;
+}
+// PCM of one file -> mono float32 at 16 kHz, appended to the resident segments at dst
+// (include/whisper_hip.h).  Everything is checked before the first HIP call.
+int AudioFront::audio_ingest(const void* pcm, int format, int64_t n, int channels, int bits, int up, int down,
+                             const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) {
+  const std::string who = "audio_ingest: ";
+  if (!pcm) return fail(-1, who + "null pcm");
+  TRY(ingest_check(who, format, n, channels, bits, up, down, taps, n_taps, dst, reserve, n_out));
+  return ingest_run(who, pcm, format, n, channels, bits, up, down, taps, n_taps, dst, reserve, n_out);
+}
+// what wh_audio_ingest refuses, before any HIP call
+int AudioFront::ingest_check(const std::string& who, int format, int64_t n, int channels, int bits, int up, int down,
+                             const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) {
+  if (!n_out) return fail(-1, who + "null n_out");
+  if (format != WH_PCM_S16 && format != WH_PCM_S32 && format != WH_PCM_F32)
+    return fail(-7, who + "unknown format " + std::to_string(format));
+  if (n < 1 || n > ((int64_t)1 << 40)) return fail(-7, who + "n_frames = " + std::to_string(n) + " out of range");
+  if (channels < 1 || channels > 256) return fail(-7, who + "channels = " + std::to_string(channels) + " out of range");
+  if (up < 1 || down < 1 || up > (1 << 20) || down > (1 << 20))
+    return fail(-7, who + "up = " + std::to_string(up) + ", down = " + std::to_string(down) + " out of range");
+  const bool f32 = format == WH_PCM_F32;
+  const bool filt = !f32 && up != down;
+  if (f32) {
+    if (channels != 1 || up != 1 || down != 1)
+      return fail(-7, who + "format WH_PCM_F32 is a mono waveform at 16 kHz: channels, up and down must be 1");
+  } else {
+    if (bits < 1 || bits > 32 || (format == WH_PCM_S16 && bits > 16))
+      return fail(-7, who + "bits = " + std::to_string(bits) + " out of range for the format");
+    const int64_t want = 2 * 10 * (int64_t)std::max(up, down) + 1;
+    if (filt && (!taps || n_taps != want))
+      return fail(-7, who + "n_taps = " + std::to_string(taps ? n_taps : 0) + ", the filter of up = " +
+                          std::to_string(up) + ", down = " + std::to_string(down) + " has " + std::to_string(want));
+  }
+  const int64_t end = audio_segs.empty() ? 0 : audio_segs.back().first + audio_segs.back().second;
+  if (dst != 0 && dst != end)
+    return fail(-7, who + "dst_offset = " + std::to_string(dst) + " is neither 0 nor the end of the resident segments (" +
+                        std::to_string(end) + ")");
+  if (reserve < 0) return fail(-7, who + "negative reserve");
+  return 0;
+}
+// pcm: the host PCM to upload, or null when the device PCM buffer (d_pcm) already holds it
+// (wh_flac_ingest's device path; its resampling time goes to WH_STAT_FLAC_RESAMPLE_MS)
+int AudioFront::ingest_run(const std::string& who, const void* pcm, int format, int64_t n, int channels, int bits,
+                           int up, int down, const double* taps, int n_taps, int64_t dst, int64_t reserve,
+                           int64_t* n_out) {
+  const bool f32 = format == WH_PCM_F32;
+  const bool filt = !f32 && up != down;
+  const int64_t no = filt ? (n * up + down - 1) / down : n;
+  double* dt = nullptr;
+  if (filt) {
+    const auto key = std::make_pair(up, down);
+    auto it = d_taps.find(key);
+    if (it == d_taps.end()) {
+      HIPCHK(hipMalloc(&dt, (size_t)n_taps * 8));
+      if (hipMemcpy(dt, taps, (size_t)n_taps * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dt);
+        return fail(-100, who + "copying the filter taps failed");
+      }
+      d_taps[key] = dt;
+    } else {
+      dt = it->second;
+    }
+  }
+  // room for the new end (or the caller's reserve); the segments before dst survive a move
+  TRY(d_audio.reserve(std::max<size_t>(std::max(dst + no, reserve), 16000) * 4, (size_t)dst * 4, st));
+  if (f32) {
+    TRY(tm.mark(0, st));
+    HIPCHK(hipMemcpyAsync(d_audio.p + dst, pcm, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    TRY(tm.finish(st, stats[WH_STAT_INGEST_COPY_MS]));
+  } else {
+    const size_t bytes = (size_t)n * channels * (format == WH_PCM_S32 ? 4 : 2);
+    if (pcm) TRY(d_pcm.reserve(bytes));
+    TRY(tm.mark(0, st));
+    if (pcm) HIPCHK(hipMemcpyAsync(d_pcm.p, pcm, bytes, hipMemcpyHostToDevice, st));
+    TRY(tm.mark(1, st));
+    launch_pcm_resample(d_pcm.p, format == WH_PCM_S32, n, channels, bits, up, down, dt, d_audio.p + dst, no, st);
+    TRY(tm.mark(2, st));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(launch_status("audio_ingest"));
+    TRY(tm.charge(0, stats[WH_STAT_INGEST_COPY_MS]));
+    TRY(tm.charge(1, stats[pcm ? WH_STAT_INGEST_KERNEL_MS : WH_STAT_FLAC_RESAMPLE_MS]));
+  }
+  if (dst == 0) audio_segs.clear();
+  audio_segs.emplace_back(dst, no);
+  audio_n = audio_segs.size() == 1 ? no : -1;
+  *n_out = no;
+  return 0;
+}
+
+// ------------------------------------------------------------ FLAC on the device
+// (include/whisper_hip.h, csrc/wh_flacdev.h).  Device buffers grow to the largest stream seen.
+// The stream of `plan` decoded into d_pcm as interleaved int32 (s32) or int16.  *ran = false:
+// the chain did not hold or a sample left int32, the device path does not run (d_pcm is
+// scratch; nothing else of the front end was touched).
+int AudioFront::flac_device(const uint8_t* data, int64_t n, const whflac::Plan& plan, bool s32, bool* ran) {
+  using namespace whflac;
+  *ran = false;
+  const int C = plan.si.channels;
+  const size_t nc = plan.cands.size();
+  if (nc > (size_t)(1 << 24)) return 0;  // lanes are counted in int
+  TRY(fl_bytes.reserve((size_t)n));
+  TRY(fl_cands.reserve(nc * sizeof(Cand)));
+  TRY(fl_subs.reserve(nc * C * sizeof(Sub)));
+  TRY(fl_ends.reserve(nc * 8));
+  TRY(fl_stage.reserve((size_t)plan.stage * 4));
+  TRY(fl_chain.reserve(nc * 4));
+  TRY(fl_starts.reserve((nc + 1) * 8 + 8));  // the flag lies behind the starts
+  TRY(d_pcm.reserve((size_t)plan.si.total * C * (s32 ? 4 : 2)));
+  TRY(tm.mark(0, st));
+  HIPCHK(hipMemcpyAsync(fl_bytes.p, data, (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(fl_cands.p, plan.cands.data(), nc * sizeof(Cand), hipMemcpyHostToDevice, st));
+  TRY(tm.mark(1, st));
+  launch_flac_parse(fl_bytes.p, n, fl_cands.p, (int)nc, C, plan.si.max_frame, fl_stage.p, fl_subs.p, fl_ends.p, st);
+  TRY(tm.mark(2, st));
+  std::vector<int64_t> ends(nc);
+  HIPCHK(hipMemcpyAsync(ends.data(), fl_ends.p, nc * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(launch_status("flac_decode"));
+  TRY(tm.charge(0, stats[WH_STAT_FLAC_UPLOAD_MS]));
+  TRY(tm.charge(1, stats[WH_STAT_FLAC_PARSE_MS]));
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<int32_t> frames;
+  std::vector<int64_t> starts;
+  const bool chained = flac_chain(plan, n, ends.data(), &frames, &starts);
+  charge_host(stats[WH_STAT_FLAC_INDEX_MS], t0);
+  if (!chained) return 0;
+  const int nf = (int)frames.size();
+  int* d_bad = (int*)(fl_starts.p + nf + 1);
+  starts.push_back(0);  // the flag, cleared with the same copy
+  HIPCHK(hipMemcpyAsync(fl_chain.p, frames.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(fl_starts.p, starts.data(), (size_t)(nf + 2) * 8, hipMemcpyHostToDevice, st));
+  TRY(tm.mark(0, st));
+  launch_flac_restore(fl_cands.p, fl_chain.p, nf, C, fl_stage.p, fl_subs.p, d_bad, st);
+  TRY(tm.mark(1, st));
+  launch_flac_gather(fl_cands.p, fl_chain.p, fl_starts.p, nf, C, fl_stage.p, d_pcm.p, s32 ? 1 : 0, plan.si.total, st);
+  TRY(tm.mark(2, st));
+  int bad = 1;
+  HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(launch_status("flac_decode"));
+  TRY(tm.charge(0, stats[WH_STAT_FLAC_RESTORE_MS]));
+  TRY(tm.charge(1, stats[WH_STAT_FLAC_GATHER_MS]));
+  *ran = bad == 0;
+  return 0;
+}
+// STREAMINFO and the index, timed into WH_STAT_FLAC_INDEX_MS.  < 0: not a FLAC stream (the
+// host decoder's error)
+int AudioFront::flac_plan_timed(const uint8_t* data, int64_t n, whflac::Plan* plan) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = whflac::flac_plan(data, n, plan);
+  charge_host(stats[WH_STAT_FLAC_INDEX_MS], t0);
+  if (rc < 0) return fail(rc, wh_flac_last_error());
+  return rc;
+}
+int AudioFront::flac_decode_device(const uint8_t* data, int64_t n, int32_t* out, int64_t cap, int64_t* n_frames,
+                                   int* path) {
+  if (!data || !out || !n_frames || !path) return fail(-1, "flac_decode_device: null argument");
+  whflac::Plan plan;
+  const int rc = flac_plan_timed(data, n, &plan);
+  if (rc < 0) return rc;
+  if (rc == 0 && plan.si.total <= cap) {
+    bool ran = false;
+    TRY(flac_device(data, n, plan, true, &ran));
+    if (ran) {
+      HIPCHK(hipMemcpy(out, d_pcm.p, (size_t)plan.si.total * plan.si.channels * 4, hipMemcpyDeviceToHost));
+      *n_frames = plan.si.total;
+      *path = 0;
+      return 0;
+    }
+  }
+  *path = 1;
+  const int hrc = wh_flac_decode(data, n, out, cap, n_frames);
+  return hrc ? fail(hrc, wh_flac_last_error()) : 0;
+}
+int AudioFront::flac_ingest(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps,
+                            int64_t dst, int64_t reserve, int64_t* n_out, int* path) {
+  const std::string who = "flac_ingest: ";
+  if (!data) return fail(-1, who + "null data");
+  if (!path) return fail(-1, who + "null path_out");
+  whflac::Plan plan;
+  const int rc = flac_plan_timed(data, n, &plan);
+  if (rc < 0) return rc;
+  const whflac::Info& si = plan.si;
+  const int format = si.bps <= 16 ? WH_PCM_S16 : WH_PCM_S32;
+  if (rc == 0) {
+    TRY(ingest_check(who, format, si.total, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out));
+    bool ran = false;
+    TRY(flac_device(data, n, plan, format == WH_PCM_S32, &ran));
+    if (ran) {
+      *path = 0;
+      return ingest_run(who, nullptr, format, si.total, si.channels, si.bps, up, down, taps, n_taps, dst, reserve,
+                        n_out);
+    }
+  }
+  // the host decoder and the PCM ingest, as a caller without this entry point would run them
+  *path = 1;
+  const int64_t cap = si.total > 0 ? si.total : n * 8;
+  std::vector<int32_t> pcm((size_t)cap * si.channels);
+  int64_t got = 0;
+  const int hrc = wh_flac_decode(data, n, pcm.data(), cap, &got);
+  if (hrc) return fail(hrc, wh_flac_last_error());
+  if (format == WH_PCM_S32) return audio_ingest(pcm.data(), format, got, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out);
+  std::vector<int16_t> pcm16(pcm.begin(), pcm.begin() + (size_t)got * si.channels);
+  return audio_ingest(pcm16.data(), format, got, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out);
+}
+int AudioFront::audio_read(float* out, int64_t offset, int64_t n) {
+  if (!out) return fail(-1, "audio_read: null out");
+  const int64_t end = audio_segs.empty() ? 0 : audio_segs.back().first + audio_segs.back().second;
+  if (offset < 0 || n < 0 || offset + n > end)
+    return fail(-8, "audio_read: [" + std::to_string(offset) + ", " + std::to_string(offset + n) +
+                        ") is outside the " + std::to_string(end) + " resident samples");
+  if (n) HIPCHK(hipMemcpy(out, d_audio.p + offset, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ------------------------------------------------------------ mel
+// what d_mel now holds
+void AudioFront::mel_is(int64_t frames, int64_t f0, int n_mels, int batch_files) {
+  mel_frames = frames; mel_f0 = f0; mel_nm = n_mels; mel_batch_files = batch_files;
+}
+// frames [frame0, frame0 + count) of the padded signal's log-mel (count < 0: to the
+// end); the front end keeps them with their absolute frame offset (mel_f0), so window
+// seeks stay absolute.  A rank of a sharded file computes only its own frames.
+int AudioFront::log_mel_frames(const float* audio, int64_t n, int64_t pad, int n_mels, int64_t frame0, int64_t count,
+                               int normalize, int64_t* total_frames) {
+  if (!h_filters.count(n_mels)) return fail(-7, "mel filters for n_mels=" + std::to_string(n_mels) + " not set");
+  if (n + pad <= 200 || n < 1) return fail(-7, "audio too short for reflect padding");
+  if (!audio && n != audio_n) return fail(-7, "no resident audio of that length");
+  const int64_t total = (n + pad) / 160;
+  if (count < 0) count = total - frame0;
+  if (frame0 < 0 || count < 1 || frame0 + count > total) return fail(-7, "mel frame range out of bounds");
+  if (audio) TRY(audio_room((size_t)n));
+  TRY(d_mel.reserve((size_t)n_mels * count * 4));
+  TRY(tm.mark(0, st));
+  if (audio) {
+    HIPCHK(hipMemcpyAsync(d_audio.p, audio, n * 4, hipMemcpyHostToDevice, st));
+    one_segment(n);
+  }
+  HIPCHK(hipMemsetAsync(gmax.p, 0, 16, st));
+  launch_mel(d_audio.p, n, n + pad, frame0, count, d_filters[n_mels], n_mels, d_mel.p, count, gmax.p, st);
+  if (normalize) launch_mel_norm(d_mel.p, count, count, n_mels, gmax.p, nullptr, st);
+  TRY(tm.finish(st, stats[WH_STAT_MEL_MS]));
+  mel_is(count, frame0, n_mels, 0);
+  *total_frames = total;
+  return 0;
+}
+// log-mel of n_files waveforms (concatenated in `audio`) in one pass: one upload, one
+// descriptor copy, the segmented frames + normalisation launches, one synchronisation.
+// The files' frames lie back to back in d_mel (row stride = all frames of the call).
+int AudioFront::log_mel_batch(const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
+                              int64_t* frame_base) {
+  if (n_files < 1) return fail(-7, "log_mel_batch: n_files = " + std::to_string(n_files) + ", need at least one file");
+  if (!n_samples || !frame_base) return fail(-1, "null argument");
+  if (pad < 0) return fail(-7, "log_mel_batch: negative padding");
+  if (!h_filters.count(n_mels)) return fail(-7, "mel filters for n_mels=" + std::to_string(n_mels) + " not set");
+  std::vector<MelFile> files(n_files);
+  int64_t samples = 0, frames = 0, blocks = 0;
+  for (int i = 0; i < n_files; ++i) {
+    const int64_t n = n_samples[i];
+    if (n < 1) return fail(-7, "log_mel_batch: file " + std::to_string(i) + " has no samples");
+    if (n + pad <= 200) return fail(-7, "log_mel_batch: file " + std::to_string(i) + " too short for reflect padding");
+    MelFile& f = files[i];
+    f.audio_off = samples;
+    f.n_real = n;
+    f.n_padded = n + pad;
+    f.nframes = (n + pad) / 160;
+    f.frame_base = frames;
+    f.block_base = blocks;
+    samples += n;
+    frames += f.nframes;
+    blocks += mel_blocks(f.nframes);
+  }
+  if (blocks > 0x7fffffff) return fail(-7, "log_mel_batch: too many frames for one call");
+  if (!audio) {
+    // the files are the resident segments (wh_audio_ingest), which stay resident
+    bool same = (int)audio_segs.size() == n_files;
+    for (int i = 0; same && i < n_files; ++i)
+      same = audio_segs[i].first == files[i].audio_off && audio_segs[i].second == files[i].n_real;
+    if (!same)
+      return fail(-7, "log_mel_batch: the " + std::to_string(audio_segs.size()) +
+                          " resident segments are not these " + std::to_string(n_files) + " files");
+  } else {
+    TRY(audio_room((size_t)samples));
+    audio_n = -1;  // the buffer now holds several files: no resident audio of any length
+    audio_segs.clear();
+  }
+  TRY(d_mel.reserve((size_t)n_mels * frames * 4));
+  const size_t room = std::max<size_t>(n_files, 64);
+  TRY(mel_files.reserve(room * sizeof(MelFile)));
+  TRY(gmax_files.reserve(room * 4));
+  mel_batch_files = 0;
+  TRY(tm.mark(0, st));
+  if (audio) HIPCHK(hipMemcpyAsync(d_audio.p, audio, (size_t)samples * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(mel_files.p, files.data(), n_files * sizeof(MelFile), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(gmax_files.p, 0, (size_t)n_files * 4, st));
+  launch_mel_seg(d_audio.p, mel_files.p, n_files, blocks, d_filters[n_mels], n_mels, d_mel.p, frames, gmax_files.p, st);
+  TRY(tm.finish(st, stats[WH_STAT_MEL_MS]));
+  mel_is(frames, 0, n_mels, n_files);
+  for (int i = 0; i < n_files; ++i) frame_base[i] = files[i].frame_base;
+  frame_base[n_files] = frames;
+  return 0;
+}
+// an ordered-uint maximum (as the kernels' atomicMax keeps it) back to its float
+static void ordered_to_float(unsigned u, float* g) {
+  const unsigned v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  memcpy(g, &v, 4);
+}
+int AudioFront::mel_max_batch(float* g, int n_files) {
+  if (!g) return fail(-1, "null argument");
+  if (n_files < 1 || n_files != mel_batch_files)
+    return fail(-7, "mel_max_batch: the context mel is of " + std::to_string(mel_batch_files) + " batch files, not " +
+                        std::to_string(n_files));
+  std::vector<unsigned> u(n_files);
+  HIPCHK(hipMemcpy(u.data(), gmax_files.p, (size_t)n_files * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n_files; ++i) ordered_to_float(u[i], g + i);
+  return 0;
+}
+int AudioFront::mel_max(float* g) {
+  unsigned u = 0;
+  HIPCHK(hipMemcpy(&u, gmax.p, 4, hipMemcpyDeviceToHost));
+  ordered_to_float(u, g);
+  return 0;
+}
+int AudioFront::mel_normalize(float g) {
+  if (mel_batch_files) return fail(-7, "mel_normalize: the context mel is of a wh_log_mel_batch call, each file already normalised");
+  float* ovr = (float*)(gmax.p + 4);
+  HIPCHK(hipMemcpyAsync(ovr, &g, 4, hipMemcpyHostToDevice, st));
+  launch_mel_norm(d_mel.p, mel_frames, mel_frames, mel_nm, gmax.p, ovr, st);
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+int AudioFront::mel_read(float* out, int64_t f0, int64_t nf) {
+  f0 -= mel_f0;  // absolute frame -> stored frame
+  if (f0 < 0 || nf < 0 || f0 + nf > mel_frames) return fail(-8, "mel_read out of range");
+  HIPCHK(hipMemcpy2D(out, nf * 4, d_mel.p + f0, mel_frames * 4, nf * 4, mel_nm, hipMemcpyDeviceToHost));
+  return 0;
+}
+// a host mel of the model's n_mels bins, nf frames from frame 0
+int AudioFront::mel_write(const float* mel, int64_t nf, int n_mels) {
+  const size_t need = (size_t)n_mels * nf;
+  TRY(d_mel.reserve(need * 4));
+  HIPCHK(hipMemcpy(d_mel.p, mel, need * 4, hipMemcpyHostToDevice));
+  mel_is(nf, 0, n_mels, 0);
+  return 0;
+}

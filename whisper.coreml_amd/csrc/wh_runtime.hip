@@ -10,55 +10,20 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <memory>
 #include <set>
 #include <string>
 #include <vector>
-#include <chrono>
 
 #include "whisper_hip.h"
 #include "wh_align.h"
-#include "wh_flacdev.h"
+#include "wh_audio.h"
 #include "wh_gemm.h"
+#include "wh_host.h"
 #include "wh_kernels.h"
 
 using namespace wh;
 
-static thread_local std::string g_err;
 static thread_local std::string g_release_error;  // a failed release in the last context destroy
-static int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIPCHK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) return fail(-100, std::string(#expr) + ": " + hipGetErrorString(e_));       \
-  } while (0)
-
-// A launch error (or any HIP error left pending) surfaces at the next hipGetLastError():
-// report it with the launch that raised it (tuning build: wh_launched checked every launch)
-// or, in the shipped build, the last launch before the check (wh_common.h)
-static int launch_status(const char* where) {
-  const hipError_t e = hipGetLastError();
-  std::string& first = wh_first_launch_error();
-  if (e == hipSuccess && first.empty()) return 0;
-  std::string msg = std::string(where) + ": ";
-  if (!first.empty()) msg += first;
-  else msg += std::string(hipGetErrorString(e)) + " (raised at or before the launch of " + wh_last_launch() + ")";
-  first.clear();
-  return fail(-100, msg);
-}
-
-static int enter(wh_ctx* ctx, const char* entry);
-
-#define TRY(expr)                  \
-  do {                             \
-    int rc_ = (expr);              \
-    if (rc_ != 0) return rc_;      \
-  } while (0)
 
 namespace {
 
@@ -107,15 +72,6 @@ struct DecLayer {
   T* wqx_f = nullptr;
 };
 
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr;
-  void create() { hipEventCreate(&a); hipEventCreate(&b); }
-  ~Timer() {
-    if (a) hipEventDestroy(a);
-    if (b) hipEventDestroy(b);
-  }
-};
-
 }  // namespace
 
 struct wh_ctx {
@@ -123,24 +79,6 @@ struct wh_ctx {
   virtual ~wh_ctx() {}
   virtual int load(const std::string& name, const float* data, const int64_t* shape, int ndim) = 0;
   virtual int finalize() = 0;
-  virtual int log_mel(const float* audio, int64_t n, int64_t pad, int n_mels, int normalize, int64_t* nf) = 0;
-  virtual int log_mel_frames(const float* audio, int64_t n, int64_t pad, int n_mels, int64_t frame0, int64_t count,
-                             int normalize, int64_t* total_frames) = 0;
-  virtual int audio_upload(const float* audio, int64_t n) = 0;
-  virtual int audio_ingest(const void* pcm, int format, int64_t n, int channels, int bits, int up, int down,
-                           const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) = 0;
-  virtual int audio_read(float* out, int64_t offset, int64_t n) = 0;
-  virtual int flac_decode_device(const uint8_t* data, int64_t n, int32_t* out, int64_t cap, int64_t* n_frames,
-                                 int* path) = 0;
-  virtual int flac_ingest(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps,
-                          int64_t dst, int64_t reserve, int64_t* n_out, int* path) = 0;
-  virtual int mel_max(float* g) = 0;
-  virtual int log_mel_batch(const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
-                            int64_t* frame_base) = 0;
-  virtual int mel_max_batch(float* g, int n_files) = 0;
-  virtual int mel_normalize(float g) = 0;
-  virtual int mel_read(float* out, int64_t f0, int64_t nf) = 0;
-  virtual int mel_write(const float* mel, int64_t nf) = 0;
   virtual int encode(int n_win, const int64_t* seeks, const int* segs) = 0;
   virtual int read_xa(int slot, float* out) = 0;
   virtual int read_ckv(int slot, int layer, float* k, float* v) = 0;
@@ -169,7 +107,9 @@ struct wh_ctx {
   int sharers = 0;
   wh_ctx* shares_from = nullptr;
   std::vector<float> token_ms;  // per-token wall ms of each decode_steps chunk
-  double stats[WH_N_STATS] = {0};
+  double stats[WH_N_STATS] = {0};  // WH_STAT_*
+  AudioFront audio;  // waveforms and the log-mel (csrc/wh_audio.h)
+  int n_mels = 0;    // the model's
   int maxc = 5;
   int maxc_stride = 1;
   int device = 0;
@@ -180,7 +120,7 @@ namespace {
 template <typename T>
 struct Ctx : public wh_ctx {
   wh_dims d;
-  int ns, nh, La, Ld, V, nm, K1p;
+  int ns, nh, La, Ld, V, K1p;
   int Wcap, Gcap;
   hipStream_t st = nullptr;
   Arena wa;  // weights
@@ -197,42 +137,7 @@ struct Ctx : public wh_ctx {
   std::vector<EncLayer<T>> enc;
   std::vector<DecLayer<T>> dec;
 
-  // mel
-  float* d_audio = nullptr;
-  size_t audio_cap = 0;
-  // resident audio: segments (offset, length) lying back to back in d_audio from sample 0
-  // (wh_audio_ingest appends; an upload leaves one; a host wh_log_mel_batch leaves none)
-  std::vector<std::pair<int64_t, int64_t>> audio_segs;
-  void* d_pcm = nullptr;  // wh_audio_ingest: the file's PCM as uploaded
-  size_t pcm_cap = 0;
-  std::map<std::pair<int, int>, double*> d_taps;  // resampling filters by (up, down)
-  // wh_flac_ingest / wh_flac_decode_device: the stream, its candidates, their subframe records,
-  // frame ends and staging slots, the chain and its first samples (the restore's flag behind them)
-  uint8_t* fl_bytes = nullptr;
-  whflac::Cand* fl_cands = nullptr;
-  whflac::Sub* fl_subs = nullptr;
-  int64_t* fl_ends = nullptr;
-  int32_t* fl_stage = nullptr;
-  int32_t* fl_chain = nullptr;
-  int64_t* fl_starts = nullptr;
-  size_t fl_bytes_cap = 0, fl_cands_cap = 0, fl_subs_cap = 0, fl_ends_cap = 0, fl_stage_cap = 0, fl_chain_cap = 0,
-         fl_starts_cap = 0;
-  hipEvent_t fl_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  Timer tm_in;
-  float* d_mel = nullptr;
-  size_t mel_cap = 0;
-  int64_t mel_frames = 0;
-  int64_t mel_f0 = 0;  // absolute index of the first stored frame
   std::vector<int64_t> h_seeks;
-  int mel_nm = 0;
-  unsigned* d_gmax = nullptr;
-  float* d_gmax_f = nullptr;
-  // wh_log_mel_batch: per-file descriptors and per-file ordered-uint maxima
-  MelFile* d_mel_files = nullptr;
-  unsigned* d_gmax_files = nullptr;
-  size_t mel_files_cap = 0;
-  int mel_batch_files = 0;  // files of the last wh_log_mel_batch (0: the mel is not from one)
-  std::map<int, float*> d_filters;
 
   // encoder buffers
   T *melT, *h1, *xn_e, *qkv_e, *vt_e, *att_e, *hm_e, *xa, *ckv;
@@ -302,12 +207,9 @@ struct Ctx : public wh_ctx {
     return 0;
   }
 
-  // every release checked: the first failure is kept (release_error) and reported by
+  // every release checked: the first failure is kept (rel.first) and reported by
   // wh_destroy instead of staying pending for the next context's first call
-  std::string release_error;
-  void rel(hipError_t e, const char* what) {
-    if (e != hipSuccess && release_error.empty()) release_error = std::string(what) + ": " + hipGetErrorString(e);
-  }
+  Releases rel;
   ~Ctx() override {
     if (st) rel(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (gexec) rel(hipGraphExecDestroy(gexec), "hipGraphExecDestroy");
@@ -315,25 +217,14 @@ struct Ctx : public wh_ctx {
     if (st) rel(hipStreamDestroy(st), "hipStreamDestroy");
     if (wbase) rel(hipFree(wbase), "hipFree(weights)");
     if (abase) rel(hipFree(abase), "hipFree(activations)");
-    if (d_audio) rel(hipFree(d_audio), "hipFree(audio)");
-    if (d_pcm) rel(hipFree(d_pcm), "hipFree(pcm)");
-    for (void* p : {(void*)fl_bytes, (void*)fl_cands, (void*)fl_subs, (void*)fl_ends, (void*)fl_stage, (void*)fl_chain,
-                    (void*)fl_starts})
-      if (p) rel(hipFree(p), "hipFree(flac)");
-    for (auto& e : fl_ev)
-      if (e) rel(hipEventDestroy(e), "hipEventDestroy(flac)");
-    for (auto& kv : d_taps) rel(hipFree(kv.second), "hipFree(resampling taps)");
-    if (d_mel) rel(hipFree(d_mel), "hipFree(mel)");
-    for (auto& kv : d_filters) rel(hipFree(kv.second), "hipFree(mel filters)");
-    if (d_gmax) rel(hipFree(d_gmax), "hipFree(mel max)");
-    if (d_mel_files) rel(hipFree(d_mel_files), "hipFree(mel files)");
-    if (d_gmax_files) rel(hipFree(d_gmax_files), "hipFree(mel file max)");
-    if (scratch) rel(hipFree(scratch), "hipFree(scratch)");
+    audio.release(rel);
+    scratch.release(rel, "hipFree(scratch)");
     if (h_done) rel(hipHostFree(h_done), "hipHostFree(done flags)");
     for (auto& e : poll_ev)
       if (e) rel(hipEventDestroy(e), "hipEventDestroy(poll)");
-    (void)hipGetLastError();  // what failed above is in release_error, not left pending
-    if (!release_error.empty()) g_release_error = release_error;
+    tm.release(rel);
+    (void)hipGetLastError();  // what failed above is in rel.first, not left pending
+    if (!rel.first.empty()) g_release_error = rel.first;
   }
 
   int init(int device_, const wh_dims& dims, int Wcap_, int Gcap_) {
@@ -344,7 +235,7 @@ struct Ctx : public wh_ctx {
     La = d.n_audio_layer;
     Ld = d.n_text_layer;
     V = d.n_vocab;
-    nm = d.n_mels;
+    n_mels = d.n_mels;
     if (d.n_audio_state != ns || d.n_audio_head != nh) return fail(-2, "audio/text state or head mismatch unsupported");
     if (ns != nh * 64) return fail(-2, "head dim must be 64 (decoder.py:62-64)");
     if (d.n_audio_ctx != 1500 || d.n_text_ctx != CTX) return fail(-2, "n_audio_ctx must be 1500, n_text_ctx 448");
@@ -354,11 +245,10 @@ struct Ctx : public wh_ctx {
     Gcap = Gcap_;
     if (Wcap < 1 || Gcap < 1 || Gcap > 8) return fail(-2, "bad max_windows / max_group");
     const int kb = 128 / (int)sizeof(T);
-    K1p = ((3 * nm + kb - 1) / kb) * kb;
+    K1p = ((3 * n_mels + kb - 1) / kb) * kb;
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    tm.create();
-    tm_in.create();
+    TRY(tm.create());
     HIPCHK(hipHostMalloc((void**)&h_done, sizeof(int) * 2 * Wcap));  // two poll buffers
     for (auto& e : poll_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     // ---------------- weights
@@ -417,7 +307,7 @@ struct Ctx : public wh_ctx {
     const int LR = std::max(Wcap * Gcap, 2 * Wcap);
     size_t ab = 0;
     auto addA = [&](size_t bytes) { ab += ((bytes + 255) & ~size_t(255)) + 256; };
-    addA((size_t)WE * MROWS * nm * sizeof(T)); addA((size_t)WE * H1ROWS * n * sizeof(T));
+    addA((size_t)WE * MROWS * n_mels * sizeof(T)); addA((size_t)WE * H1ROWS * n * sizeof(T));
     addA((size_t)WE * 1500 * n * 4); addA((size_t)WE * 1500 * n * sizeof(T)); addA((size_t)WE * 1500 * 3 * n * sizeof(T));
     addA((size_t)WE * 1500 * n * sizeof(T)); addA((size_t)WE * 1500 * 4 * n * sizeof(T));
     addA(((size_t)WE * nh * 64 * TKP + 64) * sizeof(T));  // encoder V^T (padding keys stay zero)
@@ -459,7 +349,7 @@ struct Ctx : public wh_ctx {
     auto ta = [&](size_t elems) { return (T*)aa.take(elems * sizeof(T)); };
     auto fa = [&](size_t elems) { return (float*)aa.take(elems * 4); };
     auto ia = [&](size_t elems) { return (int*)aa.take(elems * 4); };
-    melT = ta((size_t)WE * MROWS * nm); h1 = ta((size_t)WE * H1ROWS * n);
+    melT = ta((size_t)WE * MROWS * n_mels); h1 = ta((size_t)WE * H1ROWS * n);
     x_e = fa((size_t)WE * 1500 * n); xn_e = ta((size_t)WE * 1500 * n); qkv_e = ta((size_t)WE * 1500 * 3 * n);
     att_e = ta((size_t)WE * 1500 * n); hm_e = ta((size_t)WE * 1500 * 4 * n);
     vt_e = ta((size_t)WE * nh * 64 * TKP + 64);  // + the last key tile's read past TKP
@@ -493,9 +383,7 @@ struct Ctx : public wh_ctx {
     if (!fp_anc || !S.seed || !S.cand_idx || !S.lp_cnt || !S.lpw_cnt || !p1_cnt || !xs_cnt || !x2_d || !ekz_cnt)
       return fail(-3, "activation arena overflow");
     S.nw = Wcap; S.G = 1; S.ctx = CTX; S.hctx = HCTX; S.maxc = 16;
-    HIPCHK(hipMalloc(&d_gmax, 64));
-    d_gmax_f = (float*)(d_gmax + 4);
-    return 0;
+    return audio.init(st, stats);
   }
 
   // ------------------------------------------------------------ weights
@@ -520,7 +408,6 @@ struct Ctx : public wh_ctx {
   }
 
   int load(const std::string& name, const float* data, const int64_t* shape, int ndim) override {
-    auto numel = [&]() { int64_t c = 1; for (int i = 0; i < ndim; ++i) c *= shape[i]; return (size_t)c; };
     auto need = [&](std::initializer_list<int64_t> want) -> int {
       if ((int)want.size() != ndim) return fail(-4, name + ": bad rank");
       int i = 0;
@@ -532,11 +419,11 @@ struct Ctx : public wh_ctx {
     const float kscale = 0.125f;  // (64)^-0.5: encoder key (encoder.py:38), decoder query (decoder.py:20)
     int rc = 0;
     if (name == "encoder.conv1.weight") {
-      TRY(need({(int64_t)n, nm, 3}));
-      std::vector<float> t(n * K1p, 0.f);  // [o][j*nm + c] = w[o][c][j]
+      TRY(need({(int64_t)n, n_mels, 3}));
+      std::vector<float> t(n * K1p, 0.f);  // [o][j*n_mels + c] = w[o][c][j]
       for (size_t o = 0; o < n; ++o)
-        for (int c = 0; c < nm; ++c)
-          for (int j = 0; j < 3; ++j) t[o * K1p + j * nm + c] = data[(o * nm + c) * 3 + j];
+        for (int c = 0; c < n_mels; ++c)
+          for (int j = 0; j < 3; ++j) t[o * K1p + j * n_mels + c] = data[(o * n_mels + c) * 3 + j];
       rc = upT(conv1_w, t.data(), t.size());
     } else if (name == "encoder.conv1.bias") { TRY(need({(int64_t)n})); rc = upf(conv1_b, data, n); }
     else if (name == "encoder.conv2.weight") {
@@ -612,7 +499,6 @@ struct Ctx : public wh_ctx {
       }
     }
     if (rc) return rc;
-    (void)numel;
     loaded.insert(name);
     return 0;
   }
@@ -640,462 +526,6 @@ struct Ctx : public wh_ctx {
     return 0;
   }
 
-  // ------------------------------------------------------------ mel
-  int64_t audio_n = 0;
-  int audio_upload(const float* audio, int64_t n) override {
-    if ((size_t)n > audio_cap) {
-      if (d_audio) HIPCHK(hipFree(d_audio));
-      d_audio = nullptr;
-      audio_cap = std::max<size_t>(n, 16000);
-      HIPCHK(hipMalloc(&d_audio, audio_cap * 4));
-    }
-    HIPCHK(hipMemcpyAsync(d_audio, audio, n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    one_segment(n);
-    return 0;
-  }
-  void one_segment(int64_t n) {
-    audio_segs.assign(1, std::make_pair((int64_t)0, n));
-    audio_n = n;
-  }
-  // room for `need` samples; the first `keep` survive a move to a larger buffer
-  int audio_grow(size_t need, size_t keep) {
-    if (need <= audio_cap) return 0;
-    float* p = nullptr;
-    const size_t cap = std::max<size_t>(need, 16000);
-    HIPCHK(hipMalloc(&p, cap * 4));
-    if (keep && d_audio) {
-      HIPCHK(hipMemcpyAsync(p, d_audio, keep * 4, hipMemcpyDeviceToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
-    if (d_audio) HIPCHK(hipFree(d_audio));
-    d_audio = p;
-    audio_cap = cap;
-    return 0;
-  }
-  // PCM of one file -> mono float32 at 16 kHz, appended to the resident segments at dst
-  // (include/whisper_hip.h).  Everything is checked before the first HIP call.
-  int audio_ingest(const void* pcm, int format, int64_t n, int channels, int bits, int up, int down,
-                   const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) override {
-    const std::string who = "audio_ingest: ";
-    if (!pcm) return fail(-1, who + "null pcm");
-    TRY(ingest_check(who, format, n, channels, bits, up, down, taps, n_taps, dst, reserve, n_out));
-    return ingest_run(who, pcm, format, n, channels, bits, up, down, taps, n_taps, dst, reserve, n_out);
-  }
-  // what wh_audio_ingest refuses, before any HIP call
-  int ingest_check(const std::string& who, int format, int64_t n, int channels, int bits, int up, int down,
-                   const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) {
-    if (!n_out) return fail(-1, who + "null n_out");
-    if (format != WH_PCM_S16 && format != WH_PCM_S32 && format != WH_PCM_F32)
-      return fail(-7, who + "unknown format " + std::to_string(format));
-    if (n < 1 || n > ((int64_t)1 << 40)) return fail(-7, who + "n_frames = " + std::to_string(n) + " out of range");
-    if (channels < 1 || channels > 256) return fail(-7, who + "channels = " + std::to_string(channels) + " out of range");
-    if (up < 1 || down < 1 || up > (1 << 20) || down > (1 << 20))
-      return fail(-7, who + "up = " + std::to_string(up) + ", down = " + std::to_string(down) + " out of range");
-    const bool f32 = format == WH_PCM_F32;
-    const bool filt = !f32 && up != down;
-    if (f32) {
-      if (channels != 1 || up != 1 || down != 1)
-        return fail(-7, who + "format WH_PCM_F32 is a mono waveform at 16 kHz: channels, up and down must be 1");
-    } else {
-      if (bits < 1 || bits > 32 || (format == WH_PCM_S16 && bits > 16))
-        return fail(-7, who + "bits = " + std::to_string(bits) + " out of range for the format");
-      const int64_t want = 2 * 10 * (int64_t)std::max(up, down) + 1;
-      if (filt && (!taps || n_taps != want))
-        return fail(-7, who + "n_taps = " + std::to_string(taps ? n_taps : 0) + ", the filter of up = " +
-                            std::to_string(up) + ", down = " + std::to_string(down) + " has " + std::to_string(want));
-    }
-    const int64_t end = audio_segs.empty() ? 0 : audio_segs.back().first + audio_segs.back().second;
-    if (dst != 0 && dst != end)
-      return fail(-7, who + "dst_offset = " + std::to_string(dst) + " is neither 0 nor the end of the resident segments (" +
-                          std::to_string(end) + ")");
-    if (reserve < 0) return fail(-7, who + "negative reserve");
-    return 0;
-  }
-  // pcm: the host PCM to upload, or null when the device PCM buffer (d_pcm) already holds it
-  // (wh_flac_ingest's device path; its resampling time goes to stats[12])
-  int ingest_run(const std::string& who, const void* pcm, int format, int64_t n, int channels, int bits, int up,
-                 int down, const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out) {
-    const bool f32 = format == WH_PCM_F32;
-    const bool filt = !f32 && up != down;
-    const int64_t no = filt ? (n * up + down - 1) / down : n;
-    double* dt = nullptr;
-    if (filt) {
-      const auto key = std::make_pair(up, down);
-      auto it = d_taps.find(key);
-      if (it == d_taps.end()) {
-        HIPCHK(hipMalloc(&dt, (size_t)n_taps * 8));
-        if (hipMemcpy(dt, taps, (size_t)n_taps * 8, hipMemcpyHostToDevice) != hipSuccess) {
-          (void)hipFree(dt);
-          return fail(-100, who + "copying the filter taps failed");
-        }
-        d_taps[key] = dt;
-      } else {
-        dt = it->second;
-      }
-    }
-    TRY(audio_grow((size_t)std::max(dst + no, reserve), (size_t)dst));
-    float copy_ms = 0, kernel_ms = 0;
-    if (f32) {
-      HIPCHK(hipEventRecord(tm_in.a, st));
-      HIPCHK(hipMemcpyAsync(d_audio + dst, pcm, (size_t)n * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipEventRecord(tm_in.b, st));
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(hipEventElapsedTime(&copy_ms, tm_in.a, tm_in.b));
-    } else {
-      const size_t bytes = (size_t)n * channels * (format == WH_PCM_S32 ? 4 : 2);
-      if (pcm) TRY(pcm_room(bytes));
-      HIPCHK(hipEventRecord(tm_in.a, st));
-      if (pcm) HIPCHK(hipMemcpyAsync(d_pcm, pcm, bytes, hipMemcpyHostToDevice, st));
-      HIPCHK(hipEventRecord(tm_in.b, st));
-      launch_pcm_resample(d_pcm, format == WH_PCM_S32, n, channels, bits, up, down, dt, d_audio + dst, no, st);
-      HIPCHK(hipEventRecord(tm.b, st));
-      HIPCHK(hipStreamSynchronize(st));
-      TRY(launch_status("audio_ingest"));
-      HIPCHK(hipEventElapsedTime(&copy_ms, tm_in.a, tm_in.b));
-      HIPCHK(hipEventElapsedTime(&kernel_ms, tm_in.b, tm.b));
-    }
-    stats[6] += copy_ms;
-    stats[pcm ? 7 : 12] += kernel_ms;
-    if (dst == 0) audio_segs.clear();
-    audio_segs.emplace_back(dst, no);
-    audio_n = audio_segs.size() == 1 ? no : -1;
-    *n_out = no;
-    return 0;
-  }
-  int pcm_room(size_t bytes) {
-    if (bytes > pcm_cap) {
-      if (d_pcm) HIPCHK(hipFree(d_pcm));
-      d_pcm = nullptr;
-      pcm_cap = 0;
-      HIPCHK(hipMalloc(&d_pcm, bytes));
-      pcm_cap = bytes;
-    }
-    return 0;
-  }
-
-  // ------------------------------------------------------------ FLAC on the device
-  // (include/whisper_hip.h, csrc/wh_flacdev.h).  Device buffers grow to the largest stream seen.
-  template <typename P>
-  int flac_room(P*& p, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return 0;
-    if (p) HIPCHK(hipFree(p));
-    p = nullptr;
-    cap = 0;
-    HIPCHK(hipMalloc(&p, bytes));
-    cap = bytes;
-    return 0;
-  }
-  // The stream of `plan` decoded into d_pcm as interleaved int32 (s32) or int16.  *ran = false:
-  // the chain did not hold or a sample left int32, the device path does not run (d_pcm is
-  // scratch; nothing else of the context was touched).
-  int flac_device(const uint8_t* data, int64_t n, const whflac::Plan& plan, bool s32, bool* ran) {
-    using namespace whflac;
-    *ran = false;
-    const int C = plan.si.channels;
-    const size_t nc = plan.cands.size();
-    if (nc > (size_t)(1 << 24)) return 0;  // lanes are counted in int
-    if (!fl_ev[0])
-      for (auto& e : fl_ev) HIPCHK(hipEventCreate(&e));
-    TRY(flac_room(fl_bytes, fl_bytes_cap, (size_t)n));
-    TRY(flac_room(fl_cands, fl_cands_cap, nc * sizeof(Cand)));
-    TRY(flac_room(fl_subs, fl_subs_cap, nc * C * sizeof(Sub)));
-    TRY(flac_room(fl_ends, fl_ends_cap, nc * 8));
-    TRY(flac_room(fl_stage, fl_stage_cap, (size_t)plan.stage * 4));
-    TRY(flac_room(fl_chain, fl_chain_cap, nc * 4));
-    TRY(flac_room(fl_starts, fl_starts_cap, (nc + 1) * 8 + 8));  // the flag lies behind the starts
-    TRY(pcm_room((size_t)plan.si.total * C * (s32 ? 4 : 2)));
-    HIPCHK(hipEventRecord(fl_ev[0], st));
-    HIPCHK(hipMemcpyAsync(fl_bytes, data, (size_t)n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(fl_cands, plan.cands.data(), nc * sizeof(Cand), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(fl_ev[1], st));
-    launch_flac_parse(fl_bytes, n, fl_cands, (int)nc, C, plan.si.max_frame, fl_stage, fl_subs, fl_ends, st);
-    HIPCHK(hipEventRecord(fl_ev[2], st));
-    std::vector<int64_t> ends(nc);
-    HIPCHK(hipMemcpyAsync(ends.data(), fl_ends, nc * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    TRY(launch_status("flac_decode"));
-    float up_ms = 0, parse_ms = 0, restore_ms = 0, gather_ms = 0;
-    HIPCHK(hipEventElapsedTime(&up_ms, fl_ev[0], fl_ev[1]));
-    HIPCHK(hipEventElapsedTime(&parse_ms, fl_ev[1], fl_ev[2]));
-    stats[8] += up_ms;
-    stats[9] += parse_ms;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<int32_t> frames;
-    std::vector<int64_t> starts;
-    const bool chained = flac_chain(plan, n, ends.data(), &frames, &starts);
-    stats[13] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (!chained) return 0;
-    const int nf = (int)frames.size();
-    int* d_bad = (int*)(fl_starts + nf + 1);
-    starts.push_back(0);  // the flag, cleared with the same copy
-    HIPCHK(hipMemcpyAsync(fl_chain, frames.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(fl_starts, starts.data(), (size_t)(nf + 2) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(fl_ev[3], st));
-    launch_flac_restore(fl_cands, fl_chain, nf, C, fl_stage, fl_subs, d_bad, st);
-    HIPCHK(hipEventRecord(fl_ev[4], st));
-    launch_flac_gather(fl_cands, fl_chain, fl_starts, nf, C, fl_stage, d_pcm, s32 ? 1 : 0, plan.si.total, st);
-    HIPCHK(hipEventRecord(fl_ev[5], st));
-    int bad = 1;
-    HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    TRY(launch_status("flac_decode"));
-    HIPCHK(hipEventElapsedTime(&restore_ms, fl_ev[3], fl_ev[4]));
-    HIPCHK(hipEventElapsedTime(&gather_ms, fl_ev[4], fl_ev[5]));
-    stats[10] += restore_ms;
-    stats[11] += gather_ms;
-    *ran = bad == 0;
-    return 0;
-  }
-  // STREAMINFO and the index, timed into stats[13].  < 0: not a FLAC stream (the host decoder's error)
-  int flac_plan_timed(const uint8_t* data, int64_t n, whflac::Plan* plan) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const int rc = whflac::flac_plan(data, n, plan);
-    stats[13] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (rc < 0) return fail(rc, wh_flac_last_error());
-    return rc;
-  }
-  int flac_decode_device(const uint8_t* data, int64_t n, int32_t* out, int64_t cap, int64_t* n_frames,
-                         int* path) override {
-    if (!data || !out || !n_frames || !path) return fail(-1, "flac_decode_device: null argument");
-    whflac::Plan plan;
-    const int rc = flac_plan_timed(data, n, &plan);
-    if (rc < 0) return rc;
-    if (rc == 0 && plan.si.total <= cap) {
-      bool ran = false;
-      TRY(flac_device(data, n, plan, true, &ran));
-      if (ran) {
-        HIPCHK(hipMemcpy(out, d_pcm, (size_t)plan.si.total * plan.si.channels * 4, hipMemcpyDeviceToHost));
-        *n_frames = plan.si.total;
-        *path = 0;
-        return 0;
-      }
-    }
-    *path = 1;
-    const int hrc = wh_flac_decode(data, n, out, cap, n_frames);
-    return hrc ? fail(hrc, wh_flac_last_error()) : 0;
-  }
-  int flac_ingest(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps, int64_t dst,
-                  int64_t reserve, int64_t* n_out, int* path) override {
-    const std::string who = "flac_ingest: ";
-    if (!data) return fail(-1, who + "null data");
-    if (!path) return fail(-1, who + "null path_out");
-    whflac::Plan plan;
-    const int rc = flac_plan_timed(data, n, &plan);
-    if (rc < 0) return rc;
-    const whflac::Info& si = plan.si;
-    const int format = si.bps <= 16 ? WH_PCM_S16 : WH_PCM_S32;
-    if (rc == 0) {
-      TRY(ingest_check(who, format, si.total, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out));
-      bool ran = false;
-      TRY(flac_device(data, n, plan, format == WH_PCM_S32, &ran));
-      if (ran) {
-        *path = 0;
-        return ingest_run(who, nullptr, format, si.total, si.channels, si.bps, up, down, taps, n_taps, dst, reserve,
-                          n_out);
-      }
-    }
-    // the host decoder and the PCM ingest, as a caller without this entry point would run them
-    *path = 1;
-    const int64_t cap = si.total > 0 ? si.total : n * 8;
-    std::vector<int32_t> pcm((size_t)cap * si.channels);
-    int64_t got = 0;
-    const int hrc = wh_flac_decode(data, n, pcm.data(), cap, &got);
-    if (hrc) return fail(hrc, wh_flac_last_error());
-    if (format == WH_PCM_S32) return audio_ingest(pcm.data(), format, got, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out);
-    std::vector<int16_t> pcm16(pcm.begin(), pcm.begin() + (size_t)got * si.channels);
-    return audio_ingest(pcm16.data(), format, got, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out);
-  }
-  int audio_read(float* out, int64_t offset, int64_t n) override {
-    if (!out) return fail(-1, "audio_read: null out");
-    const int64_t end = audio_segs.empty() ? 0 : audio_segs.back().first + audio_segs.back().second;
-    if (offset < 0 || n < 0 || offset + n > end)
-      return fail(-8, "audio_read: [" + std::to_string(offset) + ", " + std::to_string(offset + n) +
-                          ") is outside the " + std::to_string(end) + " resident samples");
-    if (n) HIPCHK(hipMemcpy(out, d_audio + offset, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return 0;
-  }
-  // audio == nullptr: use the resident buffer of wh_audio_upload (n must match)
-  int log_mel(const float* audio, int64_t n, int64_t pad, int n_mels, int normalize, int64_t* nf) override {
-    int64_t total = 0;
-    TRY(log_mel_frames(audio, n, pad, n_mels, 0, -1, normalize, &total));
-    *nf = total;
-    return 0;
-  }
-  // frames [frame0, frame0 + count) of the padded signal's log-mel (count < 0: to the
-  // end); the context keeps them with their absolute frame offset (mel_f0), so window
-  // seeks stay absolute.  A rank of a sharded file computes only its own frames.
-  int log_mel_frames(const float* audio, int64_t n, int64_t pad, int n_mels, int64_t frame0, int64_t count,
-                     int normalize, int64_t* total_frames) override {
-    if (!h_filters.count(n_mels)) return fail(-7, "mel filters for n_mels=" + std::to_string(n_mels) + " not set");
-    if (n + pad <= 200 || n < 1) return fail(-7, "audio too short for reflect padding");
-    if (!audio && n != audio_n) return fail(-7, "no resident audio of that length");
-    const int64_t total = (n + pad) / 160;
-    if (count < 0) count = total - frame0;
-    if (frame0 < 0 || count < 1 || frame0 + count > total) return fail(-7, "mel frame range out of bounds");
-    if (audio && (size_t)n > audio_cap) {
-      if (d_audio) HIPCHK(hipFree(d_audio));
-      d_audio = nullptr;
-      audio_cap = std::max<size_t>(n, 16000);
-      HIPCHK(hipMalloc(&d_audio, audio_cap * 4));
-    }
-    const size_t need = (size_t)n_mels * count;
-    if (need > mel_cap) {
-      if (d_mel) HIPCHK(hipFree(d_mel));
-      d_mel = nullptr;
-      mel_cap = need;
-      HIPCHK(hipMalloc(&d_mel, mel_cap * 4));
-    }
-    HIPCHK(hipEventRecord(tm.a, st));
-    if (audio) {
-      HIPCHK(hipMemcpyAsync(d_audio, audio, n * 4, hipMemcpyHostToDevice, st));
-      one_segment(n);
-    }
-    HIPCHK(hipMemsetAsync(d_gmax, 0, 16, st));
-    launch_mel(d_audio, n, n + pad, frame0, count, d_filters[n_mels], n_mels, d_mel, count, d_gmax, st);
-    if (normalize) launch_mel_norm(d_mel, count, count, n_mels, d_gmax, nullptr, st);
-    HIPCHK(hipEventRecord(tm.b, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tm.a, tm.b));
-    stats[0] += ms;
-    mel_frames = count;
-    mel_f0 = frame0;
-    mel_nm = n_mels;
-    mel_batch_files = 0;
-    *total_frames = total;
-    return 0;
-  }
-  // log-mel of n_files waveforms (concatenated in `audio`) in one pass: one upload, one
-  // descriptor copy, the segmented frames + normalisation launches, one synchronisation.
-  // The files' frames lie back to back in d_mel (row stride = all frames of the call).
-  int log_mel_batch(const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
-                    int64_t* frame_base) override {
-    if (n_files < 1) return fail(-7, "log_mel_batch: n_files = " + std::to_string(n_files) + ", need at least one file");
-    if (!n_samples || !frame_base) return fail(-1, "null argument");
-    if (pad < 0) return fail(-7, "log_mel_batch: negative padding");
-    if (!h_filters.count(n_mels)) return fail(-7, "mel filters for n_mels=" + std::to_string(n_mels) + " not set");
-    std::vector<MelFile> files(n_files);
-    int64_t samples = 0, frames = 0, blocks = 0;
-    for (int i = 0; i < n_files; ++i) {
-      const int64_t n = n_samples[i];
-      if (n < 1) return fail(-7, "log_mel_batch: file " + std::to_string(i) + " has no samples");
-      if (n + pad <= 200) return fail(-7, "log_mel_batch: file " + std::to_string(i) + " too short for reflect padding");
-      MelFile& f = files[i];
-      f.audio_off = samples;
-      f.n_real = n;
-      f.n_padded = n + pad;
-      f.nframes = (n + pad) / 160;
-      f.frame_base = frames;
-      f.block_base = blocks;
-      samples += n;
-      frames += f.nframes;
-      blocks += mel_blocks(f.nframes);
-    }
-    if (blocks > 0x7fffffff) return fail(-7, "log_mel_batch: too many frames for one call");
-    if (!audio) {
-      // the files are the resident segments (wh_audio_ingest), which stay resident
-      bool same = (int)audio_segs.size() == n_files;
-      for (int i = 0; same && i < n_files; ++i)
-        same = audio_segs[i].first == files[i].audio_off && audio_segs[i].second == files[i].n_real;
-      if (!same)
-        return fail(-7, "log_mel_batch: the " + std::to_string(audio_segs.size()) +
-                            " resident segments are not these " + std::to_string(n_files) + " files");
-    } else {
-      if ((size_t)samples > audio_cap) {
-        if (d_audio) HIPCHK(hipFree(d_audio));
-        d_audio = nullptr;
-        audio_cap = std::max<size_t>(samples, 16000);
-        HIPCHK(hipMalloc(&d_audio, audio_cap * 4));
-      }
-      audio_n = -1;  // the buffer now holds several files: no resident audio of any length
-      audio_segs.clear();
-    }
-    const size_t need = (size_t)n_mels * frames;
-    if (need > mel_cap) {
-      if (d_mel) HIPCHK(hipFree(d_mel));
-      d_mel = nullptr;
-      mel_cap = need;
-      HIPCHK(hipMalloc(&d_mel, mel_cap * 4));
-    }
-    if ((size_t)n_files > mel_files_cap) {
-      if (d_mel_files) HIPCHK(hipFree(d_mel_files));
-      if (d_gmax_files) HIPCHK(hipFree(d_gmax_files));
-      d_mel_files = nullptr;
-      d_gmax_files = nullptr;
-      mel_files_cap = std::max<size_t>(n_files, 64);
-      HIPCHK(hipMalloc(&d_mel_files, mel_files_cap * sizeof(MelFile)));
-      HIPCHK(hipMalloc(&d_gmax_files, mel_files_cap * 4));
-    }
-    mel_batch_files = 0;
-    HIPCHK(hipEventRecord(tm.a, st));
-    if (audio) HIPCHK(hipMemcpyAsync(d_audio, audio, (size_t)samples * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_mel_files, files.data(), n_files * sizeof(MelFile), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_gmax_files, 0, (size_t)n_files * 4, st));
-    launch_mel_seg(d_audio, d_mel_files, n_files, blocks, d_filters[n_mels], n_mels, d_mel, frames, d_gmax_files, st);
-    HIPCHK(hipEventRecord(tm.b, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tm.a, tm.b));
-    stats[0] += ms;
-    mel_frames = frames;
-    mel_f0 = 0;
-    mel_nm = n_mels;
-    mel_batch_files = n_files;
-    for (int i = 0; i < n_files; ++i) frame_base[i] = files[i].frame_base;
-    frame_base[n_files] = frames;
-    return 0;
-  }
-  int mel_max_batch(float* g, int n_files) override {
-    if (!g) return fail(-1, "null argument");
-    if (n_files < 1 || n_files != mel_batch_files)
-      return fail(-7, "mel_max_batch: the context mel is of " + std::to_string(mel_batch_files) + " batch files, not " +
-                          std::to_string(n_files));
-    std::vector<unsigned> u(n_files);
-    HIPCHK(hipMemcpy(u.data(), d_gmax_files, (size_t)n_files * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n_files; ++i) {
-      const unsigned v = (u[i] & 0x80000000u) ? (u[i] & 0x7fffffffu) : ~u[i];
-      memcpy(g + i, &v, 4);
-    }
-    return 0;
-  }
-  std::map<int, std::vector<float>> h_filters;
-  int mel_max(float* g) override {
-    unsigned u = 0;
-    HIPCHK(hipMemcpy(&u, d_gmax, 4, hipMemcpyDeviceToHost));
-    const unsigned v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    memcpy(g, &v, 4);
-    return 0;
-  }
-  int mel_normalize(float g) override {
-    if (mel_batch_files) return fail(-7, "mel_normalize: the context mel is of a wh_log_mel_batch call, each file already normalised");
-    HIPCHK(hipMemcpyAsync(d_gmax_f, &g, 4, hipMemcpyHostToDevice, st));
-    launch_mel_norm(d_mel, mel_frames, mel_frames, mel_nm, d_gmax, d_gmax_f, st);
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
-  }
-  int mel_read(float* out, int64_t f0, int64_t nf) override {
-    f0 -= mel_f0;  // absolute frame -> stored frame
-    if (f0 < 0 || nf < 0 || f0 + nf > mel_frames) return fail(-8, "mel_read out of range");
-    HIPCHK(hipMemcpy2D(out, nf * 4, d_mel + f0, mel_frames * 4, nf * 4, mel_nm, hipMemcpyDeviceToHost));
-    return 0;
-  }
-  int mel_write(const float* mel, int64_t nf) override {
-    const size_t need = (size_t)nm * nf;
-    if (need > mel_cap) {
-      if (d_mel) HIPCHK(hipFree(d_mel));
-      d_mel = nullptr;
-      mel_cap = need;
-      HIPCHK(hipMalloc(&d_mel, mel_cap * 4));
-    }
-    HIPCHK(hipMemcpy(d_mel, mel, need * 4, hipMemcpyHostToDevice));
-    mel_frames = nf;
-    mel_f0 = 0;
-    mel_nm = nm;
-    mel_batch_files = 0;
-    return 0;
-  }
-
   // ------------------------------------------------------------ encoder
   // single: the encode is ONE window (its decode batch runs the single-window path too):
   // the residual GEMMs (conv2, out, fc2) split K in two halves inside the launch — within
@@ -1111,11 +541,12 @@ struct Ctx : public wh_ctx {
       ga.p1_slabs = EKZ_TILES(n) * 64;
     };
     // mel windows -> time-major (T), conv1 as overlapping-row GEMM (lda = n_mels)
-    launch_mel_windows<T>(d_mel, mel_frames, nm, d_seeks + s0, d_segs + s0, melT, (int64_t)MROWS * nm, MROWS, we, st);
+    const MelView mel = audio.mel();
+    launch_mel_windows<T>(mel.p, mel.frames, n_mels, d_seeks + s0, d_segs + s0, melT, (int64_t)MROWS * n_mels, MROWS, we, st);
     g = GemmArgs();
-    g.x_group_rows = 3000; g.x_group_stride = (int64_t)MROWS * nm;
+    g.x_group_rows = 3000; g.x_group_stride = (int64_t)MROWS * n_mels;
     g.out = h1; g.ldo = n; g.out_group_stride = (int64_t)H1ROWS * n; g.out_row_off = 1;
-    TRY(gemm(melT, nm, conv1_w, conv1_b, we * 3000, n, K1p, EPI_STORE_GELU, g));
+    TRY(gemm(melT, n_mels, conv1_w, conv1_b, we * 3000, n, K1p, EPI_STORE_GELU, g));
     launch_zero_rows<T>(h1, (int64_t)H1ROWS * n, n, 0, H1ROWS - 1, we, st);
     // conv2 (stride 2): row t reads padded rows 2t..2t+2 -> lda = 2n; + GELU + positional embedding
     g = GemmArgs();
@@ -1156,25 +587,22 @@ struct Ctx : public wh_ctx {
   int encode(int n_win, const int64_t* seeks, const int* segs) override {
     if (!finalized) return fail(-9, "weights not finalized");
     if (n_win < 1 || n_win > Wcap) return fail(-9, "n_win out of range");
-    if (!d_mel || mel_nm != nm) return fail(-9, "no mel of the model's n_mels in the context");
-    // seeks are absolute frames; the stored mel starts at mel_f0
+    const MelView mel = audio.mel();
+    if (!mel.p || mel.n_mels != n_mels) return fail(-9, "no mel of the model's n_mels in the context");
+    // seeks are absolute frames; the stored mel starts at mel.f0
     h_seeks.resize(n_win);
     for (int i = 0; i < n_win; ++i) {
-      const int64_t s = seeks[i] - mel_f0;
-      if (s < 0 || segs[i] < 1 || s + std::min(segs[i], 3000) > mel_frames) return fail(-9, "bad window");
+      const int64_t s = seeks[i] - mel.f0;
+      if (s < 0 || segs[i] < 1 || s + std::min(segs[i], 3000) > mel.frames) return fail(-9, "bad window");
       h_seeks[i] = s;
     }
-    HIPCHK(hipEventRecord(tm.a, st));
+    TRY(tm.mark(0, st));
     HIPCHK(hipMemcpyAsync(d_seeks, h_seeks.data(), n_win * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_segs, segs, n_win * 4, hipMemcpyHostToDevice, st));
     const int WE = std::min(Wcap, enc_chunk());
     for (int s0 = 0; s0 < n_win; s0 += WE) TRY(encode_chunk(s0, std::min(WE, n_win - s0), n_win == 1));
-    HIPCHK(hipEventRecord(tm.b, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tm.a, tm.b));
-    stats[1] += ms;
-    stats[5] += n_win;
+    TRY(tm.finish(st, stats[WH_STAT_ENCODE_MS]));
+    stats[WH_STAT_ENCODE_WINDOWS] += n_win;
     TRY(launch_status(__func__));
     return 0;
   }
@@ -1689,7 +1117,7 @@ struct Ctx : public wh_ctx {
     if (!finalized) return fail(-9, "weights not finalized");
     if (n_win < 1 || n_win > Wcap) return fail(-11, "n_win out of range");
     TRY(set_opts(o));
-    HIPCHK(hipEventRecord(tm.a, st));
+    TRY(tm.mark(0, st));
     TRY(begin_batch(n_win, o->group, init, n_init, max_init, sot_index, o->no_speech, slots));
     S.maxc = std::max(maxc, 1);
     maxc_stride = S.maxc;
@@ -1698,13 +1126,7 @@ struct Ctx : public wh_ctx {
     // embeds each row's new token: the first step's input rows
     launch_select_merge(logits, V, S, O, n_win, st, merge_embed());
     rows_dirty = false;
-    HIPCHK(hipEventRecord(tm.b, st));
-    HIPCHK(hipStreamSynchronize(st));
-    TRY(launch_status(__func__));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tm.a, tm.b));
-    stats[2] += ms;
-    return 0;
+    return tm.finish(st, stats[WH_STAT_PREFILL_MS], __func__);
   }
 
   // The device loop's step input rows (x_d, row_pos) are written by the previous update's
@@ -1744,17 +1166,11 @@ struct Ctx : public wh_ctx {
   bool step_api = false;
   int step_prefill(int n_win, int G, const int* init, const int* n_init, int max_init, const int* sot_index,
                    float* lg) override {
-    HIPCHK(hipEventRecord(tm.a, st));
+    TRY(tm.mark(0, st));
     TRY(begin_batch(n_win, G, init, n_init, max_init, sot_index, -1));
     step_api = true;
     if (lg) HIPCHK(hipMemcpyAsync(lg, logits2, (size_t)2 * n_win * V * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(tm.b, st));
-    HIPCHK(hipStreamSynchronize(st));
-    TRY(launch_status(__func__));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tm.a, tm.b));
-    stats[2] += ms;
-    return 0;
+    return tm.finish(st, stats[WH_STAT_PREFILL_MS], __func__);
   }
 
   int step_tokens(const int* tok, const int* offsets, float* lg) override {
@@ -1768,7 +1184,7 @@ struct Ctx : public wh_ctx {
         return fail(-13, "text_offset " + std::to_string(offsets[w]) + " of window " + std::to_string(w) +
                              " != cached length " + std::to_string(h_len[w]));
     }
-    HIPCHK(hipEventRecord(tm.a, st));
+    TRY(tm.mark(0, st));
     HIPCHK(hipMemcpyAsync(rows_in, tok, R * 4, hipMemcpyHostToDevice, st));
     launch_append_tokens(S, rows_in, cur_nwin, st);
     launch_embed<T>(E, Pdec, ns, nullptr, row_pos, S.hist, S.len, cur_G, HCTX, CTX - 1, x_d, R, st);
@@ -1776,14 +1192,9 @@ struct Ctx : public wh_ctx {
                    nullptr, nullptr, 0, true));
     TRY(vocab(nullptr, R, logits));
     if (lg) HIPCHK(hipMemcpyAsync(lg, logits, (size_t)R * V * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(tm.b, st));
-    HIPCHK(hipStreamSynchronize(st));  // the host token buffer must outlive its copy
-    TRY(launch_status(__func__));
+    TRY(tm.finish(st, stats[WH_STAT_STEPS_MS], __func__));  // the wait: the host tokens outlive their copy
     for (auto& l : h_len) ++l;
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tm.a, tm.b));
-    stats[3] += ms;
-    stats[4] += 1;
+    stats[WH_STAT_STEPS] += 1;
     return 0;
   }
 
@@ -1857,7 +1268,7 @@ struct Ctx : public wh_ctx {
     if (cur_nwin < 1) return fail(-13, "no decode in progress");
     if (step_api) return fail(-13, "the batch was begun with wh_prefill (per-step mode): use wh_step");
     if (!eager()) TRY(ensure_graph());
-    HIPCHK(hipEventRecord(tm.a, st));
+    TRY(tm.mark(0, st));
     restore_rows();
     int steps = 0, done = 0;
     static const int chunk = [] {  // WHISPER_HIP_POLL_CHUNK: steps per done-flag poll (A/B)
@@ -1895,12 +1306,8 @@ struct Ctx : public wh_ctx {
       if (done == cur_nwin || kq[nb] == 0) break;
       b = nb;
     }
-    HIPCHK(hipEventRecord(tm.b, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tm.a, tm.b));
-    stats[3] += ms;
-    stats[4] += steps;
+    TRY(tm.finish(st, stats[WH_STAT_STEPS_MS]));
+    stats[WH_STAT_STEPS] += steps;
     *n_done = done;
     return 0;
   }
@@ -1979,17 +1386,11 @@ struct Ctx : public wh_ctx {
   }
 
   // grow-only device scratch for the alignment / prefill readbacks
-  char* scratch = nullptr;
-  size_t scratch_cap = 0;
+  DevBuf<char> scratch;
   int ensure_scratch(size_t bytes) {
-    if (bytes <= scratch_cap) return 0;
+    if (bytes <= scratch.cap) return 0;
     HIPCHK(hipStreamSynchronize(st));
-    if (scratch) HIPCHK(hipFree(scratch));
-    scratch = nullptr;
-    scratch_cap = 0;
-    HIPCHK(hipMalloc((void**)&scratch, bytes));
-    scratch_cap = bytes;
-    return 0;
+    return scratch.reserve(bytes);
   }
 
   // find_alignment's device half (timing.py:163-231) for a batch of windows: window w
@@ -2033,7 +1434,7 @@ struct Ctx : public wh_ctx {
                  b_tr = al(tr_off[n_win]), b_path = al(path_off[n_win] * 4), b_pr = al(prob_off[n_win] * 4 + 16),
                  b_pl = al((size_t)n_win * 4), b_jobs = al((size_t)n_win * sizeof(DtwJob));
     TRY(ensure_scratch(b_qk + b_lg + b_mat + b_tr + b_path + 2 * b_pr + b_pl + b_jobs));
-    char* p = scratch;
+    char* p = scratch.p;
     float* d_qk = (float*)p; p += b_qk;
     float* d_lg = (float*)p; p += b_lg;
     float* d_mat = (float*)p; p += b_mat;
@@ -2127,7 +1528,7 @@ struct Ctx : public wh_ctx {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t b_x = al((size_t)N * M * 4), b_tr = al(dtw_trace_bytes(N, M)), b_path = al((size_t)2 * (N + M) * 4);
     TRY(ensure_scratch(b_x + b_tr + b_path + 256 + al(sizeof(DtwJob))));
-    char* p = scratch;
+    char* p = scratch.p;
     float* d_x = (float*)p; p += b_x;
     unsigned* d_tr = (unsigned*)p; p += b_tr;
     int* d_path = (int*)p; p += b_path;
@@ -2182,13 +1583,13 @@ struct Ctx : public wh_ctx {
     if (what == 0) {
       if (cur_nwin < 1) return fail(-16, "no decode batch");
       if (!eager()) TRY(ensure_graph());
-      HIPCHK(hipEventRecord(tm.a, st));
+      HIPCHK(hipEventRecord(tm.ev[0], st));
       for (int i = 0; i < iters; ++i) TRY(launch_step());
-      HIPCHK(hipEventRecord(tm.b, st));
+      HIPCHK(hipEventRecord(tm.ev[1], st));
     } else if (what == 1) {
-      HIPCHK(hipEventRecord(tm.a, st));
+      HIPCHK(hipEventRecord(tm.ev[0], st));
       for (int i = 0; i < iters; ++i) TRY(encode_chunk(0, 1, true));
-      HIPCHK(hipEventRecord(tm.b, st));
+      HIPCHK(hipEventRecord(tm.ev[1], st));
     } else if (what == 2 || what == 3 || what == 5 || what == 6) {
       // per-launch time of one decoder-step kernel at the current batch, over all
       // layers (so weights / cross-KV stream from HBM as in the step, not from cache):
@@ -2201,7 +1602,7 @@ struct Ctx : public wh_ctx {
       const int nl = warm ? 1 : Ld;
       const int R = cur_nwin * cur_G, n = ns;
       int launches = 0;
-      HIPCHK(hipEventRecord(tm.a, st));
+      HIPCHK(hipEventRecord(tm.ev[0], st));
       for (int i = 0; i < iters * (warm ? Ld : 1); ++i)
         for (int l = 0; l < nl; ++l) {
           auto& e = dec[l];
@@ -2221,10 +1622,10 @@ struct Ctx : public wh_ctx {
             ++launches;
           }
         }
-      HIPCHK(hipEventRecord(tm.b, st));
+      HIPCHK(hipEventRecord(tm.ev[1], st));
       HIPCHK(hipStreamSynchronize(st));
       float t = 0;
-      HIPCHK(hipEventElapsedTime(&t, tm.a, tm.b));
+      HIPCHK(hipEventElapsedTime(&t, tm.ev[0], tm.ev[1]));
       *ms = t / launches;
       return 0;
     } else if (what == 7) {
@@ -2275,13 +1676,13 @@ struct Ctx : public wh_ctx {
         HIPCHK(hipMemsetAsync(S.anc, 0, ab, st));
       }
       int rc = 0;
-      if (hipEventRecord(tm.a, st) != hipSuccess) rc = fail(-100, "time_stage(8/9): hipEventRecord failed");
+      if (hipEventRecord(tm.ev[0], st) != hipSuccess) rc = fail(-100, "time_stage(8/9): hipEventRecord failed");
       for (int i = 0; rc == 0 && i < iters; ++i)
         for (int l = 0; rc == 0 && l < Ld; ++l)
           if (launch_self_attn_qkv<T>(part, sa_probe_ks, (int64_t)R * 3 * n, dec[l].bqkv, n, kc[l], vc[l], st_row_win,
                                       st_row_slot, row_pos, S.anc, cur_G, Gcap, nh, CTX, att_d, n, R, st, sa_probe_half))
             rc = fail(-20, "time_stage(8/9): self-attention launch refused");
-      if (rc == 0 && hipEventRecord(tm.b, st) != hipSuccess) rc = fail(-100, "time_stage(8/9): hipEventRecord failed");
+      if (rc == 0 && hipEventRecord(tm.ev[1], st) != hipSuccess) rc = fail(-100, "time_stage(8/9): hipEventRecord failed");
       if (saved) {
         if (hipMemcpyAsync(S.anc, saved, ab, hipMemcpyDeviceToDevice, st) != hipSuccess && rc == 0)
           rc = fail(-100, "time_stage(9): ancestry restore failed");
@@ -2291,32 +1692,41 @@ struct Ctx : public wh_ctx {
       if (rc) return rc;
       HIPCHK(hipStreamSynchronize(st));
       float t = 0;
-      HIPCHK(hipEventElapsedTime(&t, tm.a, tm.b));
+      HIPCHK(hipEventElapsedTime(&t, tm.ev[0], tm.ev[1]));
       *ms = t / (iters * Ld);
       return 0;
     } else if (what == 4) {
       // the token-selection kernel alone on the current logits (state unchanged)
       if (cur_nwin < 1) return fail(-16, "no decode batch");
-      HIPCHK(hipEventRecord(tm.a, st));
+      HIPCHK(hipEventRecord(tm.ev[0], st));
       for (int i = 0; i < iters; ++i) launch_logit_rows(logits, V, S, O, cur_nwin, st);
-      HIPCHK(hipEventRecord(tm.b, st));
+      HIPCHK(hipEventRecord(tm.ev[1], st));
     } else {
       return fail(-2, "time_stage: unknown stage");
     }
     HIPCHK(hipStreamSynchronize(st));
     float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, tm.a, tm.b));
+    HIPCHK(hipEventElapsedTime(&t, tm.ev[0], tm.ev[1]));
     *ms = t / iters;
     return 0;
   }
 };
+
+template <typename T>
+int create(int device, const wh_dims& dims, int max_windows, int max_group, wh_ctx** out) {
+  auto c = new Ctx<T>();
+  const int rc = c->init(device, dims, max_windows, max_group);
+  if (rc) { delete c; return rc; }
+  *out = c;
+  return 0;
+}
 
 }  // namespace
 
 // ============================================================ C ABI
 extern "C" {
 
-const char* wh_last_error(void) { return g_err.c_str(); }
+const char* wh_last_error(void) { return wh_error().c_str(); }
 int wh_version(void) { return 1; }
 
 int wh_create(int device, const wh_dims* dims, int compute_dtype, int max_windows, int max_group, wh_ctx** out) {
@@ -2325,21 +1735,9 @@ int wh_create(int device, const wh_dims* dims, int compute_dtype, int max_window
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(-1, "no HIP device");
   if (device < 0 || device >= ndev) return fail(-1, "device out of range");
-  int rc;
-  if (compute_dtype == WH_F16) {
-    auto c = new Ctx<half_t>();
-    rc = c->init(device, *dims, max_windows, max_group);
-    if (rc) { delete c; return rc; }
-    *out = c;
-  } else if (compute_dtype == WH_F32) {
-    auto c = new Ctx<float>();
-    rc = c->init(device, *dims, max_windows, max_group);
-    if (rc) { delete c; return rc; }
-    *out = c;
-  } else {
-    return fail(-1, "compute_dtype must be WH_F32 or WH_F16");
-  }
-  return 0;
+  if (compute_dtype == WH_F16) return create<half_t>(device, *dims, max_windows, max_group, out);
+  if (compute_dtype == WH_F32) return create<float>(device, *dims, max_windows, max_group, out);
+  return fail(-1, "compute_dtype must be WH_F32 or WH_F16");
 }
 
 int wh_destroy(wh_ctx* ctx) {
@@ -2355,26 +1753,6 @@ int wh_destroy(wh_ctx* ctx) {
   return 0;
 }
 
-int wh_set_mel_filters(wh_ctx* ctx, int n_mels, const float* filters) {
-  if (!ctx || !filters) return fail(-1, "null argument");
-  if (const int rc = enter(ctx, __func__)) return rc;
-  std::vector<float> f(filters, filters + (size_t)n_mels * 201);
-  // both element-type contexts share the filter map through the base pointer cast
-  auto* c16 = dynamic_cast<Ctx<half_t>*>(ctx);
-  auto* c32 = dynamic_cast<Ctx<float>*>(ctx);
-  std::map<int, float*>& dm = c16 ? c16->d_filters : c32->d_filters;
-  std::map<int, std::vector<float>>& hm = c16 ? c16->h_filters : c32->h_filters;
-  float* d = nullptr;
-  if (dm.count(n_mels)) d = dm[n_mels];
-  else {
-    HIPCHK(hipMalloc(&d, f.size() * 4));
-    dm[n_mels] = d;
-  }
-  HIPCHK(hipMemcpy(d, f.data(), f.size() * 4, hipMemcpyHostToDevice));
-  hm[n_mels] = f;
-  return 0;
-}
-
 // every context call: on the context's device, and no HIP error pending from before it
 // (a pending one belongs to an earlier call: reported as such, not as this call's failure)
 static int enter(wh_ctx* ctx, const char* entry) {
@@ -2382,7 +1760,7 @@ static int enter(wh_ctx* ctx, const char* entry) {
   const hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return fail(-100, std::string(entry) + ": hipSetDevice: " + hipGetErrorString(e));
   const int rc = launch_status("HIP error pending before this call");
-  if (rc) g_err = std::string(entry) + ": " + g_err;
+  if (rc) wh_error() = std::string(entry) + ": " + wh_error();
   return rc;
 }
 #define CTXCALL(expr)                            \
@@ -2392,6 +1770,10 @@ static int enter(wh_ctx* ctx, const char* entry) {
     return (expr);                               \
   } while (0)
 
+int wh_set_mel_filters(wh_ctx* ctx, int n_mels, const float* filters) {
+  if (!ctx || !filters) return fail(-1, "null argument");
+  CTXCALL(ctx->audio.set_mel_filters(n_mels, filters));
+}
 int wh_load_tensor(wh_ctx* ctx, const char* name, const float* data, const int64_t* shape, int ndim) {
   if (!name || !data || !shape) return fail(-1, "null argument");
   CTXCALL(ctx->load(name, data, shape, ndim));
@@ -2407,38 +1789,38 @@ int wh_token_ms(wh_ctx* ctx, float* out, int cap, int* n, int reset) {
   return 0;
 }
 int wh_log_mel(wh_ctx* ctx, const float* audio, int64_t n, int64_t pad, int n_mels, int normalize, int64_t* nf) {
-  CTXCALL(ctx->log_mel(audio, n, pad, n_mels, normalize, nf));
+  CTXCALL(ctx->audio.log_mel(audio, n, pad, n_mels, normalize, nf));
 }
 int wh_log_mel_frames(wh_ctx* ctx, const float* audio, int64_t n, int64_t pad, int n_mels, int64_t frame0,
                       int64_t count, int normalize, int64_t* total_frames) {
-  CTXCALL(ctx->log_mel_frames(audio, n, pad, n_mels, frame0, count, normalize, total_frames));
+  CTXCALL(ctx->audio.log_mel_frames(audio, n, pad, n_mels, frame0, count, normalize, total_frames));
 }
 int wh_audio_upload(wh_ctx* ctx, const float* audio, int64_t n) {
   if (!audio || n <= 0) return fail(-1, "bad audio");
-  CTXCALL(ctx->audio_upload(audio, n));
+  CTXCALL(ctx->audio.audio_upload(audio, n));
 }
 int wh_audio_ingest(wh_ctx* ctx, const void* pcm, int format, int64_t n_frames, int channels, int bits, int up,
                     int down, const double* taps, int n_taps, int64_t dst_offset, int64_t reserve, int64_t* n_out) {
-  CTXCALL(ctx->audio_ingest(pcm, format, n_frames, channels, bits, up, down, taps, n_taps, dst_offset, reserve, n_out));
+  CTXCALL(ctx->audio.audio_ingest(pcm, format, n_frames, channels, bits, up, down, taps, n_taps, dst_offset, reserve, n_out));
 }
-int wh_audio_read(wh_ctx* ctx, float* out, int64_t offset, int64_t n) { CTXCALL(ctx->audio_read(out, offset, n)); }
+int wh_audio_read(wh_ctx* ctx, float* out, int64_t offset, int64_t n) { CTXCALL(ctx->audio.audio_read(out, offset, n)); }
 int wh_flac_decode_device(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int32_t* out, int64_t cap_frames,
                           int64_t* n_frames, int* path_out) {
-  CTXCALL(ctx->flac_decode_device(data, n_bytes, out, cap_frames, n_frames, path_out));
+  CTXCALL(ctx->audio.flac_decode_device(data, n_bytes, out, cap_frames, n_frames, path_out));
 }
 int wh_flac_ingest(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int down, const double* taps, int n_taps,
                    int64_t dst_offset, int64_t reserve, int64_t* n_out, int* path_out) {
-  CTXCALL(ctx->flac_ingest(data, n_bytes, up, down, taps, n_taps, dst_offset, reserve, n_out, path_out));
+  CTXCALL(ctx->audio.flac_ingest(data, n_bytes, up, down, taps, n_taps, dst_offset, reserve, n_out, path_out));
 }
-int wh_mel_max(wh_ctx* ctx, float* g) { CTXCALL(ctx->mel_max(g)); }
+int wh_mel_max(wh_ctx* ctx, float* g) { CTXCALL(ctx->audio.mel_max(g)); }
 int wh_log_mel_batch(wh_ctx* ctx, const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
                      int64_t* frame_base) {
-  CTXCALL(ctx->log_mel_batch(audio, n_files, n_samples, pad, n_mels, frame_base));
+  CTXCALL(ctx->audio.log_mel_batch(audio, n_files, n_samples, pad, n_mels, frame_base));
 }
-int wh_mel_max_batch(wh_ctx* ctx, float* g, int n_files) { CTXCALL(ctx->mel_max_batch(g, n_files)); }
-int wh_mel_normalize(wh_ctx* ctx, float g) { CTXCALL(ctx->mel_normalize(g)); }
-int wh_mel_read(wh_ctx* ctx, float* out, int64_t f0, int64_t nf) { CTXCALL(ctx->mel_read(out, f0, nf)); }
-int wh_mel_write(wh_ctx* ctx, const float* mel, int64_t nf) { CTXCALL(ctx->mel_write(mel, nf)); }
+int wh_mel_max_batch(wh_ctx* ctx, float* g, int n_files) { CTXCALL(ctx->audio.mel_max_batch(g, n_files)); }
+int wh_mel_normalize(wh_ctx* ctx, float g) { CTXCALL(ctx->audio.mel_normalize(g)); }
+int wh_mel_read(wh_ctx* ctx, float* out, int64_t f0, int64_t nf) { CTXCALL(ctx->audio.mel_read(out, f0, nf)); }
+int wh_mel_write(wh_ctx* ctx, const float* mel, int64_t nf) { CTXCALL(ctx->audio.mel_write(mel, nf, ctx->n_mels)); }
 int wh_encode(wh_ctx* ctx, int n_win, const int64_t* seeks, const int* segs) { CTXCALL(ctx->encode(n_win, seeks, segs)); }
 int wh_read_audio_features(wh_ctx* ctx, int slot, float* out) { CTXCALL(ctx->read_xa(slot, out)); }
 int wh_read_cross_kv(wh_ctx* ctx, int slot, int layer, float* k, float* v) { CTXCALL(ctx->read_ckv(slot, layer, k, v)); }
