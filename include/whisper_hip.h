@@ -130,6 +130,51 @@ int wh_audio_ingest(wh_ctx* ctx, const void* pcm, int format, int64_t n_frames, 
 /* resident samples [offset, offset + n) back to the host */
 int wh_audio_read(wh_ctx* ctx, float* out, int64_t offset, int64_t n);
 
+/* ---- speech spans: which frames of a resident file hold speech, found on the device so that
+   only those are encoded and decoded (whisper/vad.py restates this in numpy).  The definition
+   is in integers, so host and device agree exactly and the summation order cannot matter.
+   Per file, a resident segment (offset, n) of 16 kHz float32 samples x:
+     1. q[i] = clamp(rint(32768 * x[i]), -32768, 32767), rint in fp32 to even (the product is
+        exact); a NaN sample counts as 0.
+     2. frame f is samples [160 f, 160 f + 160) of the file, F = ceil(n / 160), samples past n
+        are zeros; E[f] = sum q^2 as uint64 (at most 160 * 2^30).  Frames are the mel's hop:
+        100 per second, frame indices are seek frames.
+     3. histogram of 160 quarter-octave bins: bin 0 holds E == 0; for E >= 1, m = floor(log2 E),
+        sub = (E >> (m-2)) & 3 if m >= 2 else (E << (2-m)) & 3, bin = 1 + 4 m + sub, whose lower
+        edge is (4 + sub) << (m-2) if m >= 2 else (4 + sub) >> (2-m) (bin 0: 0).
+     4. rank = max(1, ceil(F * percentile / 100)); N = the lower edge of the first bin whose
+        cumulative count reaches rank (the noise level);
+        T = min(max((N * ratio_q8) >> 8, t_lo), t_hi).
+     5. active[f] = E[f] > T.  A run of fewer than min_silence inactive frames between two
+        active frames becomes active; active runs shorter than min_speech frames are then
+        dropped; each remaining run [s, e) becomes [max(0, s - pad), min(F, e + pad)); runs
+        that now overlap or touch are merged.
+   The caller turns decibels into the integers: ratio_q8 = round(256 * 10^(margin_db / 10))
+   with margin_db <= 40 (the product stays under 2^64), t_lo = round(160 * 2^30 *
+   10^(floor_db / 10)), t_hi the same of ceil_db.
+   wh_speech_spans runs this for the first n_files resident segments (wh_audio_ingest /
+   wh_flac_ingest / wh_audio_upload): two kernels on the context's stream with no host round
+   trip between them, then one small copy.  spans [n_files][cap][2] int32 frames, n_spans
+   [n_files], thresholds [n_files] = T.  A file with more than cap spans reports the count it
+   needs in n_spans and has none written (the call still returns 0): call again with that
+   capacity.  A file has at most F / 2 + 1 spans; room beyond that of the largest file is
+   neither allocated nor copied.  Refused before the first HIP call: null opts / n_spans / thresholds, null spans
+   with cap > 0, cap < 0, percentile outside 1..99, ratio_q8 outside [256, 2560000],
+   t_lo > t_hi, a negative or > 2^30 frame count, n_files < 1 or more files than there are
+   resident segments (the message says "resident"), a file of 2^30 frames or more.
+   wh_frame_energy_read: E (energy_out, capacity cap values, needs F) and the histogram
+   (hist_out [160], nullable) of resident segment `file`, computed by the first kernel alone.
+   With energy_out NULL nothing is computed and the return value is F (the one call whose
+   success is not 0). */
+typedef struct wh_vad_opts {
+  uint64_t ratio_q8, t_lo, t_hi;
+  int percentile;                   /* 1..99 */
+  int min_silence, min_speech, pad; /* frames */
+} wh_vad_opts;
+int wh_speech_spans(wh_ctx* ctx, const wh_vad_opts* opts, int n_files, int32_t* spans, int cap, int32_t* n_spans,
+                    uint64_t* thresholds);
+int wh_frame_energy_read(wh_ctx* ctx, int file, uint64_t* energy_out, int64_t cap, uint32_t* hist_out);
+
 int wh_mel_max(wh_ctx* ctx, float* gmax);              /* raw log10 max of the last wh_log_mel */
 int wh_mel_normalize(wh_ctx* ctx, float gmax);         /* floor at gmax-8, (x+4)/4 */
 /* log-mel of n_files waveforms, concatenated in `audio` (file i has n_samples[i] floats),
@@ -240,12 +285,14 @@ int wh_step_kernels(wh_ctx* ctx, int n_win, int group, char* buf, int cap);
    [6] its host-to-device copies [7] its resampling kernel; device ms of wh_flac_ingest /
    wh_flac_decode_device on the device path: [8] upload of the stream and the candidate table
    [9] k_flac_parse [10] k_flac_restore [11] k_flac_gather [12] the resampling kernel; [13] host
-   ms of the candidate index and the chain.  WH_N_STATS values in all. */
-enum { WH_N_STATS = 14 };
+   ms of the candidate index and the chain; device ms of wh_speech_spans / wh_frame_energy_read:
+   [14] k_frame_energy [15] k_speech_spans.  WH_N_STATS values in all. */
+enum { WH_N_STATS = 16 };
 enum {
   WH_STAT_MEL_MS = 0, WH_STAT_ENCODE_MS, WH_STAT_PREFILL_MS, WH_STAT_STEPS_MS, WH_STAT_STEPS, WH_STAT_ENCODE_WINDOWS,
   WH_STAT_INGEST_COPY_MS, WH_STAT_INGEST_KERNEL_MS, WH_STAT_FLAC_UPLOAD_MS, WH_STAT_FLAC_PARSE_MS,
-  WH_STAT_FLAC_RESTORE_MS, WH_STAT_FLAC_GATHER_MS, WH_STAT_FLAC_RESAMPLE_MS, WH_STAT_FLAC_INDEX_MS
+  WH_STAT_FLAC_RESTORE_MS, WH_STAT_FLAC_GATHER_MS, WH_STAT_FLAC_RESAMPLE_MS, WH_STAT_FLAC_INDEX_MS,
+  WH_STAT_VAD_ENERGY_MS, WH_STAT_VAD_SPANS_MS
 };
 int wh_stats(wh_ctx* ctx, double* out, int n);
 int wh_sync(wh_ctx* ctx);

@@ -11,6 +11,8 @@
 #include "wh_flacdev.h"
 #include "wh_host.h"
 #include "wh_kernels.h"
+#include "wh_vad.h"
+#include "whisper_hip.h"
 
 // the stored log-mel as the encoder reads it: rows of `frames` floats, one per mel bin
 struct MelView {
@@ -46,6 +48,10 @@ struct AudioFront {
   int mel_normalize(float g);
   int mel_read(float* out, int64_t f0, int64_t nf);
   int mel_write(const float* mel, int64_t nf, int n_mels);
+  // speech spans of the first n_files resident segments (include/whisper_hip.h)
+  int speech_spans(const wh_vad_opts* o, int n_files, int32_t* spans, int cap, int32_t* n_spans,
+                   uint64_t* thresholds);
+  int frame_energy_read(int file, uint64_t* energy_out, int64_t cap, uint32_t* hist_out);
 
  private:
   hipStream_t st = nullptr;  // the context's
@@ -81,7 +87,17 @@ struct AudioFront {
   std::map<int, float*> d_filters;
   std::map<int, std::vector<float>> h_filters;
 
+  // wh_speech_spans: the files' descriptors, frame energies and histograms, the run scratch
+  // between the two rules, and what goes back to the host (thresholds, counts, spans)
+  DevBuf<wh::VadFile> vad_files;
+  DevBuf<unsigned long long> vad_energy;
+  DevBuf<unsigned> vad_hist;
+  DevBuf<int> vad_runs;
+  DevBuf<char> vad_out;
+
   void one_segment(int64_t n);
+  int vad_plan(const char* who, int n_files, std::vector<wh::VadFile>* files, int64_t* blocks);
+  int vad_energy_launch(const std::vector<wh::VadFile>& files, int64_t blocks);
   int audio_room(size_t samples);
   void mel_is(int64_t frames, int64_t f0, int n_mels, int batch_files);
   int ingest_check(const std::string& who, int format, int64_t n, int channels, int bits, int up, int down,

@@ -1,5 +1,5 @@
 // The audio front end of a context (csrc/wh_audio.h): host code only, every kernel it
-// launches lives in wh_kernels.hip, wh_ingest.hip or wh_flacdev.hip.
+// launches lives in wh_kernels.hip, wh_ingest.hip, wh_flacdev.hip or wh_vad.hip.
 #include "wh_audio.h"
 
 #include <algorithm>
@@ -33,6 +33,11 @@ void AudioFront::release(Releases& rel) {
   gmax.release(rel, "hipFree(mel max)");
   mel_files.release(rel, "hipFree(mel files)");
   gmax_files.release(rel, "hipFree(mel file max)");
+  vad_files.release(rel, "hipFree(vad files)");
+  vad_energy.release(rel, "hipFree(vad energy)");
+  vad_hist.release(rel, "hipFree(vad histograms)");
+  vad_runs.release(rel, "hipFree(vad runs)");
+  vad_out.release(rel, "hipFree(vad spans)");
   tm.release(rel);
 }
 
@@ -275,6 +280,127 @@ int AudioFront::audio_read(float* out, int64_t offset, int64_t n) {
                         ") is outside the " + std::to_string(end) + " resident samples");
   if (n) HIPCHK(hipMemcpy(out, d_audio.p + offset, (size_t)n * 4, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ------------------------------------------------------------ speech spans
+// (include/whisper_hip.h, csrc/wh_vad.hip).  The files are the first n_files resident
+// segments; nothing here touches the segments or the mel.
+int AudioFront::vad_plan(const char* who, int n_files, std::vector<VadFile>* files, int64_t* blocks) {
+  const std::string w = std::string(who) + ": ";
+  if (n_files < 1) return fail(-7, w + "n_files = " + std::to_string(n_files) + ", need at least one file");
+  if ((size_t)n_files > audio_segs.size())
+    return fail(-7, w + std::to_string(n_files) + " files asked for, " + std::to_string(audio_segs.size()) +
+                        " segments are resident");
+  files->resize(n_files);
+  int64_t frames = 0, nb = 0, pairs = 0;
+  for (int i = 0; i < n_files; ++i) {
+    VadFile& f = (*files)[i];
+    f.off = audio_segs[i].first;
+    f.n = audio_segs[i].second;
+    f.frames = (f.n + VAD_HOP - 1) / VAD_HOP;
+    if (f.n < 1 || f.frames >= ((int64_t)1 << 30))
+      return fail(-7, w + "resident file " + std::to_string(i) + " has " + std::to_string(f.n) + " samples: out of range");
+    f.e_base = frames;
+    f.block_base = nb;
+    f.run_base = pairs;
+    frames += f.frames;
+    nb += vad_blocks(f.frames);
+    pairs += vad_run_pairs(f.frames);
+  }
+  if (nb > 0x7fffffff) return fail(-7, w + "too many frames for one call");
+  *blocks = nb;
+  return 0;
+}
+// descriptors up, histograms cleared, k_frame_energy launched (between the caller's marks)
+int AudioFront::vad_energy_launch(const std::vector<VadFile>& files, int64_t blocks) {
+  const int n_files = (int)files.size();
+  HIPCHK(hipMemcpyAsync(vad_files.p, files.data(), files.size() * sizeof(VadFile), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(vad_hist.p, 0, (size_t)n_files * VAD_BINS * 4, st));
+  launch_frame_energy(d_audio.p, vad_files.p, n_files, blocks, vad_energy.p, vad_hist.p, st);
+  return 0;
+}
+int AudioFront::speech_spans(const wh_vad_opts* o, int n_files, int32_t* spans, int cap, int32_t* n_spans,
+                             uint64_t* thresholds) {
+  const char* who = "speech_spans";
+  const std::string w = "speech_spans: ";
+  if (!o || !n_spans || !thresholds) return fail(-1, w + "null argument");
+  if (cap < 0 || cap > (1 << 29)) return fail(-7, w + "cap = " + std::to_string(cap) + " out of range");
+  if (cap > 0 && !spans) return fail(-1, w + "null spans with cap > 0");
+  if (o->percentile < 1 || o->percentile > 99)
+    return fail(-7, w + "percentile = " + std::to_string(o->percentile) + " outside 1..99");
+  if (o->ratio_q8 < 256 || o->ratio_q8 > 2560000)
+    return fail(-7, w + "ratio_q8 = " + std::to_string(o->ratio_q8) + " outside [256, 2560000] (0 to 40 dB)");
+  if (o->t_lo > o->t_hi) return fail(-7, w + "t_lo above t_hi");
+  const int lim = 1 << 30;
+  if (o->min_silence < 0 || o->min_speech < 0 || o->pad < 0 || o->min_silence > lim || o->min_speech > lim || o->pad > lim)
+    return fail(-7, w + "min_silence, min_speech and pad are frame counts from 0 to 2^30");
+  std::vector<VadFile> files;
+  int64_t blocks = 0;
+  TRY(vad_plan(who, n_files, &files, &blocks));
+  const VadFile& last = files.back();
+  // a file has at most frames / 2 + 1 spans: more room than the largest file can fill is not
+  // allocated or copied (the caller's rows keep their stride of cap)
+  int64_t most = 0;
+  for (const VadFile& f : files) most = std::max(most, vad_run_pairs(f.frames));
+  const int dcap = (int)std::min<int64_t>(cap, most);
+  const size_t room = std::max<size_t>(n_files, 64);
+  TRY(vad_files.reserve(room * sizeof(VadFile)));
+  TRY(vad_hist.reserve(room * VAD_BINS * 4));
+  TRY(vad_energy.reserve((size_t)(last.e_base + last.frames) * 8));
+  TRY(vad_runs.reserve((size_t)(last.run_base + vad_run_pairs(last.frames)) * 8));
+  // what goes back: thresholds [n_files] uint64, counts [n_files] int, spans [n_files][cap][2] int
+  const size_t off_cnt = (size_t)n_files * 8, off_spans = off_cnt + (size_t)n_files * 4;
+  const size_t bytes = off_spans + (size_t)n_files * dcap * 8;
+  TRY(vad_out.reserve(std::max<size_t>(bytes, 4096)));
+  std::vector<char> host(bytes);
+  VadOpts vo;
+  vo.ratio_q8 = o->ratio_q8; vo.t_lo = o->t_lo; vo.t_hi = o->t_hi;
+  vo.percentile = o->percentile; vo.min_silence = o->min_silence; vo.min_speech = o->min_speech; vo.pad = o->pad;
+  TRY(tm.mark(0, st));
+  TRY(vad_energy_launch(files, blocks));
+  TRY(tm.mark(1, st));
+  launch_speech_spans(vad_energy.p, vad_hist.p, vad_files.p, n_files, vo, vad_runs.p, dcap,
+                      (unsigned long long*)vad_out.p, (int*)(vad_out.p + off_cnt), (int*)(vad_out.p + off_spans), st);
+  TRY(tm.mark(2, st));
+  HIPCHK(hipMemcpyAsync(host.data(), vad_out.p, bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(launch_status(who));
+  TRY(tm.charge(0, stats[WH_STAT_VAD_ENERGY_MS]));
+  TRY(tm.charge(1, stats[WH_STAT_VAD_SPANS_MS]));
+  memcpy(thresholds, host.data(), (size_t)n_files * 8);
+  memcpy(n_spans, host.data() + off_cnt, (size_t)n_files * 4);
+  // a file that needs more room has none written: its part of the buffer is not data
+  for (int i = 0; i < n_files; ++i)
+    if (n_spans[i] <= dcap && n_spans[i] > 0)
+      memcpy(spans + (size_t)i * cap * 2, host.data() + off_spans + (size_t)i * dcap * 8, (size_t)n_spans[i] * 8);
+  return 0;
+}
+int AudioFront::frame_energy_read(int file, uint64_t* energy_out, int64_t cap, uint32_t* hist_out) {
+  const char* who = "frame_energy_read";
+  if (file < 0 || (size_t)file >= audio_segs.size())
+    return fail(-7, "frame_energy_read: file = " + std::to_string(file) + ", " + std::to_string(audio_segs.size()) +
+                        " segments are resident");
+  std::vector<VadFile> files;
+  int64_t blocks = 0;
+  TRY(vad_plan(who, file + 1, &files, &blocks));
+  const VadFile& f = files[file];
+  if (!energy_out) return (int)f.frames;  // the size query: nothing is computed
+  if (cap < f.frames)
+    return fail(-7, "frame_energy_read: cap = " + std::to_string(cap) + ", the file has " + std::to_string(f.frames) +
+                        " frames");
+  const size_t room = std::max<size_t>(files.size(), 64);
+  TRY(vad_files.reserve(room * sizeof(VadFile)));
+  TRY(vad_hist.reserve(room * VAD_BINS * 4));
+  TRY(vad_energy.reserve((size_t)(f.e_base + f.frames) * 8));
+  TRY(tm.mark(0, st));
+  TRY(vad_energy_launch(files, blocks));
+  TRY(tm.mark(1, st));
+  HIPCHK(hipMemcpyAsync(energy_out, vad_energy.p + f.e_base, (size_t)f.frames * 8, hipMemcpyDeviceToHost, st));
+  if (hist_out)
+    HIPCHK(hipMemcpyAsync(hist_out, vad_hist.p + (size_t)file * VAD_BINS, VAD_BINS * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(launch_status(who));
+  return tm.charge(0, stats[WH_STAT_VAD_ENERGY_MS]);
 }
 
 // ------------------------------------------------------------ mel

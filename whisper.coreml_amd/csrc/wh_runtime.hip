@@ -1812,6 +1812,13 @@ int wh_flac_ingest(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, in
                    int64_t dst_offset, int64_t reserve, int64_t* n_out, int* path_out) {
   CTXCALL(ctx->audio.flac_ingest(data, n_bytes, up, down, taps, n_taps, dst_offset, reserve, n_out, path_out));
 }
+int wh_speech_spans(wh_ctx* ctx, const wh_vad_opts* opts, int n_files, int32_t* spans, int cap, int32_t* n_spans,
+                    uint64_t* thresholds) {
+  CTXCALL(ctx->audio.speech_spans(opts, n_files, spans, cap, n_spans, thresholds));
+}
+int wh_frame_energy_read(wh_ctx* ctx, int file, uint64_t* energy_out, int64_t cap, uint32_t* hist_out) {
+  CTXCALL(ctx->audio.frame_energy_read(file, energy_out, cap, hist_out));
+}
 int wh_mel_max(wh_ctx* ctx, float* g) { CTXCALL(ctx->audio.mel_max(g)); }
 int wh_log_mel_batch(wh_ctx* ctx, const float* audio, int n_files, const int64_t* n_samples, int64_t pad, int n_mels,
                      int64_t* frame_base) {

@@ -41,6 +41,11 @@ class WhDecodeOpts(ctypes.Structure):
                 ("seed", c_uint64), ("max_candidates", c_int)]
 
 
+class WhVadOpts(ctypes.Structure):
+    _fields_ = [("ratio_q8", c_uint64), ("t_lo", c_uint64), ("t_hi", c_uint64), ("percentile", c_int),
+                ("min_silence", c_int), ("min_speech", c_int), ("pad", c_int)]
+
+
 _lib = None
 _EXPORTS = {
     # name: (restype, argtypes)
@@ -58,6 +63,8 @@ _EXPORTS = {
     "wh_audio_ingest": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                 c_int64, c_int64, POINTER(c_int64)]),
     "wh_audio_read": (c_int, [c_void_p, c_void_p, c_int64, c_int64]),
+    "wh_speech_spans": (c_int, [c_void_p, POINTER(WhVadOpts), c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "wh_frame_energy_read": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p]),
     "wh_mel_max": (c_int, [c_void_p, POINTER(c_float)]),
     "wh_mel_normalize": (c_int, [c_void_p, c_float]),
     "wh_log_mel_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p]),
@@ -99,7 +106,7 @@ _EXPORTS = {
     "wh_flac_ingest": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_int64,
                                POINTER(c_int64), POINTER(c_int)]),
 }
-N_STATS = 14  # WH_N_STATS
+N_STATS = 16  # WH_N_STATS
 FLAC_PATHS = ("device", "host")
 
 
@@ -353,6 +360,41 @@ class HipContext:
         self._check(self.lib.wh_audio_read(self.h, _ptr(out), int(offset), int(n)), "wh_audio_read")
         return out
 
+    # -- speech spans
+    def speech_spans(self, params, n_files: int = 1, cap: int = 256):
+        """wh_speech_spans on the first ``n_files`` resident segments: per file (spans int32
+        [k][2] in frames, threshold T).  ``params``: ``vad.VadParams`` (the integers of the
+        definition).  ``cap`` is the room per file of the first try (the library trims it to
+        what the largest file could fill, so a generous value costs a short file nothing); a
+        file with more spans reports how many and the call, both kernels, is repeated once
+        with that room."""
+        o = WhVadOpts(ratio_q8=int(params.ratio_q8), t_lo=int(params.t_lo), t_hi=int(params.t_hi),
+                      percentile=int(params.percentile), min_silence=int(params.min_silence),
+                      min_speech=int(params.min_speech), pad=int(params.pad))
+        n_files, cap = int(n_files), max(int(cap), 0)
+        counts = np.zeros(max(n_files, 1), dtype=np.int32)
+        thr = np.zeros(max(n_files, 1), dtype=np.uint64)
+        for _ in range(2):
+            spans = np.zeros((max(n_files, 1), max(cap, 1), 2), dtype=np.int32)
+            self._check(self.lib.wh_speech_spans(self.h, ctypes.byref(o), n_files, _ptr(spans), cap, _ptr(counts),
+                                                 _ptr(thr)), "wh_speech_spans")
+            need = int(counts[:n_files].max())
+            if need <= cap:
+                return [(spans[i, :counts[i]].copy(), int(thr[i])) for i in range(n_files)]
+            cap = need
+        raise HipBackendError(f"wh_speech_spans asked for room twice ({need} spans after {cap})")
+
+    def frame_energy(self, file: int = 0):
+        """(E uint64 [F], histogram uint32 [160]) of resident segment ``file``
+        (wh_frame_energy_read: the detector's first kernel alone)."""
+        n = self.lib.wh_frame_energy_read(self.h, int(file), None, 0, None)  # the size query
+        self._check(0 if n > 0 else (n or -1), "wh_frame_energy_read")
+        energy = np.zeros(n, dtype=np.uint64)
+        hist = np.zeros(160, dtype=np.uint32)
+        self._check(self.lib.wh_frame_energy_read(self.h, int(file), _ptr(energy), n, _ptr(hist)),
+                    "wh_frame_energy_read")
+        return energy, hist
+
     def log_mel_batch_resident(self, n_samples: Sequence[int], n_mels: int, padding: int = 0) -> np.ndarray:
         """``log_mel_batch`` of the resident segments (``audio_ingest`` back to back), which
         must be exactly these lengths; nothing is uploaded and they stay resident."""
@@ -563,7 +605,7 @@ class HipContext:
         self._check(self.lib.wh_stats(self.h, out, N_STATS), "wh_stats")
         keys = ["mel_ms", "encode_ms", "prefill_ms", "steps_ms", "steps", "encode_windows", "ingest_copy_ms",
                 "ingest_kernel_ms", "flac_upload_ms", "flac_parse_ms", "flac_restore_ms", "flac_gather_ms",
-                "flac_resample_ms", "flac_index_ms"]
+                "flac_resample_ms", "flac_index_ms", "vad_energy_ms", "vad_spans_ms"]
         return {k: out[i] for i, k in enumerate(keys)}
 
     def sync(self):

@@ -29,7 +29,8 @@ from .audio import HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, ingest_source
 from .backend_hip import DeviceAudio
 from .decoding import DecodingResult, language_probs, next_seed
 from .tokenizer import LANGUAGES, get_tokenizer
-from .transcribe import Window, _Lane, _check_fp16, _device_round, _plan_file, _run_round
+from .transcribe import Window, _Lane, _check_fp16, _device_round, _plan_file, _run_round, _skip_silence_params
+from .vad import clamp_clips, frames_to_seconds, resident_spans
 
 if TYPE_CHECKING:
     from .model import Whisper
@@ -137,7 +138,7 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
                      initial_prompt=None, carry_initial_prompt: bool = False, word_timestamps: bool = False,
                      prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
                      clip_timestamps="0", hallucination_silence_threshold: Optional[float] = None,
-                     **decode_options) -> List[dict]:
+                     skip_silence: Union[bool, dict] = False, **decode_options) -> List[dict]:
     """``[transcribe(model, a, **kwargs) for a in audios]`` with the files decoded
     together: ``result[i]`` is what ``transcribe(model, audios[i], ...)`` returns.
 
@@ -145,12 +146,15 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     multilingual model), one code, or one per file.  ``initial_prompt`` and
     ``clip_timestamps``: one value for all files, or a list with one per file (a list of
     ints is one token prompt, a list of numbers one clip list).  ``mel_budget_frames``
-    bounds the log-mel frames held on the device at a time.  The other keywords are
+    bounds the log-mel frames held on the device at a time.  ``skip_silence``: the speech
+    spans of all files of a group come from one detector call after the group's ingest and
+    become the files' clips; a file without speech takes no lane.  The other keywords are
     transcribe()'s."""
     for k in ("schedule", "mel_max_reduce", "_mel_prepared"):
         if k in decode_options:
             raise TypeError(f"transcribe_batch() does not take {k!r}")
     _check_fp16(model, decode_options.pop("fp16", True))
+    vad_params = _skip_silence_params(skip_silence, clip_timestamps)
     ctx = model.ctx
     n_mels = model.dims.n_mels
     if isinstance(audios, (str, np.ndarray, DeviceAudio)):
@@ -194,16 +198,30 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
             if seg.n_samples != lengths[i]:
                 raise RuntimeError(f"audio {i}: {seg.n_samples} samples ingested, {lengths[i]} planned")
             offset += seg.n_samples
+        if vad_params is not None:
+            # one detector call for the group, on the segments that were just ingested
+            for i, (sp, _) in zip(group, resident_spans(ctx, len(group), vad_params)):
+                spans[i] = sp
         return ctx.log_mel_batch_resident([lengths[i] for i in group], n_mels, padding=N_SAMPLES)
+
+    spans: dict = {}       # skip_silence: file -> its speech spans in frames
+    clips_of: dict = {}    # and the clips they give (clamped to the file's whole frames)
+
+    def file_clips(k: int, i: int, bases):
+        if vad_params is not None and i not in clips_of:
+            clips_of[i] = clamp_clips(spans[i], int(bases[k + 1] - bases[k]) - N_FRAMES)
+        return clips_of.get(i)
 
     def detect(group: List[int], bases) -> None:
         """Language of every file of the group that has none: the first window of up to
         max_windows files per encode, one <|startoftranscript|> pass per slot."""
-        todo = [k for k, i in enumerate(group) if languages[i] is None]
+        # with skip_silence the probe window starts at the first span; a file without one is not probed
+        first = {k: (file_clips(k, i, bases) or [(0, 0)])[0][0] for k, i in enumerate(group)}
+        todo = [k for k, i in enumerate(group) if languages[i] is None and file_clips(k, i, bases) != []]
         for c0 in range(0, len(todo), ctx.max_windows):
             chunk = todo[c0:c0 + ctx.max_windows]
-            seeks = [int(bases[k]) for k in chunk]
-            sizes = [min(N_FRAMES, int(bases[k + 1] - bases[k])) for k in chunk]
+            seeks = [int(bases[k]) + first[k] for k in chunk]
+            sizes = [min(N_FRAMES, int(bases[k + 1] - bases[k]) - first[k]) for k in chunk]
             ctx.encode(seeks, sizes)
             model._last_windows = (seeks, sizes)
             for slot, k in enumerate(chunk):
@@ -225,12 +243,15 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
         lanes = []
         for k, i in enumerate(group):
             content_frames = int(bases[k + 1] - bases[k]) - N_FRAMES
+            clips_i = file_clips(k, i, bases)
+            if clips_i == []:
+                clips_i = [(0, 0)]  # no speech: a clip that offers no window, so the file takes no lane
             opts = dict(decode_options, language=languages[i])
             plan = _plan_file(model, content_frames, languages[i], opts, temperature=temperature,
                               thresholds=thresholds, initial_prompt=prompts[i], word_timestamps=word_timestamps,
                               prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
                               clip_timestamps=clips[i],
-                              hallucination_silence_threshold=hallucination_silence_threshold)
+                              hallucination_silence_threshold=hallucination_silence_threshold, seek_clips=clips_i)
             plans[i] = plan
             tokenizer, seek_clips, prompt_tokens, st = plan
             lanes.append(_Lane(model.dims.n_text_ctx, seek_clips, prompt_tokens, condition_on_previous_text,
@@ -253,4 +274,6 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
                 print(f"[{i}] [{s['start']:.2f} --> {s['end']:.2f}] {s['text']}")
         results.append(dict(text=tokenizer.decode(all_tokens[len(prompt_tokens):]), segments=segments,
                             language=languages[i]))
+        if vad_params is not None:
+            results[-1]["speech_spans"] = frames_to_seconds(spans[i])
     return results

@@ -43,6 +43,7 @@ from .backend_hip import DeviceAudio
 from .decoding import DecodingOptions, DecodingResult, detect_language, next_seed, run_windows
 from .timing import WordTiming, apply_alignment, find_alignment_batch
 from .tokenizer import LANGUAGES, get_tokenizer
+from .vad import clamp_clips, frames_to_seconds, resident_spans, resolve_options
 
 if TYPE_CHECKING:
     from .model import Whisper
@@ -172,9 +173,11 @@ def _clear_empty(tokenizer, segs: List[dict]):
 
 def _plan_file(model: "Whisper", content_frames: int, language: str, decode_options: dict, *, temperature,
                thresholds, initial_prompt, word_timestamps, prepend_punctuations, append_punctuations,
-               clip_timestamps, hallucination_silence_threshold):
+               clip_timestamps, hallucination_silence_threshold, seek_clips=None):
     """What one file's loop needs besides its mel (transcribe.py:141-183, 230-254):
-    (tokenizer, clips, initial prompt tokens, state of the window loop)."""
+    (tokenizer, clips, initial prompt tokens, state of the window loop).  ``seek_clips``:
+    the clips already in frames (the speech spans of ``skip_silence``), instead of
+    ``clip_timestamps``."""
     task = decode_options.get("task", "transcribe")
     tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=language,
                               task=task)
@@ -187,7 +190,10 @@ def _plan_file(model: "Whisper", content_frames: int, language: str, decode_opti
         seek_points.append(0)
     if len(seek_points) % 2 == 1:
         seek_points.append(content_frames)
-    seek_clips = list(zip(seek_points[::2], seek_points[1::2]))
+    if seek_clips is None:
+        seek_clips = list(zip(seek_points[::2], seek_points[1::2]))
+    else:
+        seek_clips = [(int(s), int(e)) for s, e in seek_clips]
 
     temperatures = [temperature] if isinstance(temperature, (int, float)) else list(temperature)
     base = DecodingOptions(**{k: v for k, v in decode_options.items() if k in DecodingOptions.__dataclass_fields__})
@@ -217,14 +223,20 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
                append_punctuations: str = "\"'.。,，!！?？:：”)]}、", clip_timestamps: Union[str, List[float]] = "0",
                hallucination_silence_threshold: Optional[float] = None, schedule: str = "auto",
                mel_max_reduce=None, _mel_prepared: Optional[Tuple[int, int, int]] = None,
-               **decode_options) -> dict:
+               skip_silence: Union[bool, dict] = False, **decode_options) -> dict:
     """transcribe.py:41-524.  Extra keywords: ``schedule`` ("auto", "sequential",
-    "batched") and ``mel_max_reduce`` (callable local max -> global max, used when
+    "batched"), ``mel_max_reduce`` (callable local max -> global max, used when
     one file is sharded over GPUs: the log-mel floor is a whole-file max,
-    audio.py:155, so ranks all-reduce it before normalizing)."""
+    audio.py:155, so ranks all-reduce it before normalizing) and ``skip_silence``
+    (True, or a dict of ``vad.DEFAULTS`` options): the speech spans of the resident
+    waveform are found on the device (``vad.speech_spans``) and become the clips, so
+    only they are encoded and decoded; the result gains ``"speech_spans"`` in seconds."""
     _check_fp16(model, decode_options.pop("fp16", True))
     ctx = model.ctx
     n_mels = model.dims.n_mels
+    vad_params = _skip_silence_params(skip_silence, clip_timestamps)
+    if vad_params is not None and _mel_prepared is not None:
+        raise ValueError("skip_silence is not available on the sharded path (_mel_prepared)")
     if isinstance(audio, str) and _mel_prepared is None:
         # a path: its PCM is mixed down and resampled on the device and stays there
         audio = load_audio_device(model, audio)
@@ -249,15 +261,33 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
     else:
         audio = np.ascontiguousarray(audio.detach().cpu().numpy() if hasattr(audio, "detach") else audio,
                                      dtype=np.float32)
+        if vad_params is not None:
+            # the detector reads the resident waveform: upload once, the mel is computed from it too
+            resident = ctx.audio_upload(audio).n_samples
 
-        def compute_mel():
-            return ctx.log_mel(audio, n_mels, padding=N_SAMPLES, normalize=mel_max_reduce is None)
+            def compute_mel():
+                return ctx.log_mel_resident(resident, n_mels, padding=N_SAMPLES, normalize=mel_max_reduce is None)
+        else:
+            def compute_mel():
+                return ctx.log_mel(audio, n_mels, padding=N_SAMPLES, normalize=mel_max_reduce is None)
 
     def prepare_mel():
         nf = compute_mel()
         if mel_max_reduce is not None and _mel_prepared is None:
             ctx.mel_normalize(float(mel_max_reduce(ctx.mel_max())))
         return nf
+
+    spans = seek_clips = None
+    probe_frame = 0  # where the language probe window starts
+    if vad_params is not None:
+        # the detector runs first, on the waveform: a file without speech costs neither mel nor encode
+        spans = resident_spans(ctx, 1, vad_params)[0][0]
+        seek_clips = clamp_clips(spans, resident // HOP_LENGTH)  # the mel's content_frames
+        if not seek_clips:
+            # nothing to decode; an empty clip list would mean "the whole file" (_plan_file)
+            language = decode_options.get("language") or (None if model.is_multilingual else "en")
+            return dict(text="", segments=[], language=language, speech_spans=frames_to_seconds(spans))
+        probe_frame = seek_clips[0][0]
 
     frames = prepare_mel()
     content_frames = frames - N_FRAMES
@@ -266,7 +296,7 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
         if not model.is_multilingual:
             decode_options["language"] = "en"
         else:
-            seg = ctx.mel_read(n_mels, 0, min(N_FRAMES, frames))
+            seg = ctx.mel_read(n_mels, probe_frame, min(N_FRAMES, frames - probe_frame))
             if seg.shape[1] < N_FRAMES:
                 seg = np.pad(seg, ((0, 0), (0, N_FRAMES - seg.shape[1])))
             _, probs = detect_language(model, seg)
@@ -281,7 +311,7 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
                       initial_prompt=initial_prompt, word_timestamps=word_timestamps,
                       prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
                       clip_timestamps=clip_timestamps,
-                      hallucination_silence_threshold=hallucination_silence_threshold)
+                      hallucination_silence_threshold=hallucination_silence_threshold, seek_clips=seek_clips)
     tokenizer, seek_clips, initial_prompt_tokens, state = plan
     batched = schedule == "batched" or (
         schedule == "auto" and not condition_on_previous_text and not carry_initial_prompt
@@ -301,8 +331,26 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
         all_tokens.extend(s["tokens"])
         if verbose:
             print(f"[{s['start']:.2f} --> {s['end']:.2f}] {s['text']}")
-    return dict(text=tokenizer.decode(all_tokens[len(initial_prompt_tokens):]), segments=all_segments,
-                language=language)
+    result = dict(text=tokenizer.decode(all_tokens[len(initial_prompt_tokens):]), segments=all_segments,
+                  language=language)
+    if spans is not None:
+        result["speech_spans"] = frames_to_seconds(spans)
+    return result
+
+
+def _skip_silence_params(skip_silence, clip_timestamps):
+    """``skip_silence`` of transcribe() / transcribe_batch() -> ``vad.VadParams``, None when it
+    is off.  The spans become the clips, so explicit ``clip_timestamps`` cannot be combined."""
+    if skip_silence is None or skip_silence is False:
+        return None
+    if skip_silence is True:
+        skip_silence = {}
+    if not isinstance(skip_silence, dict):
+        raise TypeError(f"skip_silence must be a bool or a dict of options, not {type(skip_silence).__name__}")
+    params = resolve_options(**skip_silence)
+    if not (isinstance(clip_timestamps, str) and clip_timestamps == "0"):
+        raise ValueError("skip_silence chooses the clips itself: it cannot be combined with clip_timestamps")
+    return params
 
 
 def _window_at(seek: int, clip: Tuple[int, int], content_frames: int):
