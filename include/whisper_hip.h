@@ -367,6 +367,51 @@ int wh_flac_decode_device(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int
 int wh_flac_ingest(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int down, const double* taps,
                    int n_taps, int64_t dst_offset, int64_t reserve, int64_t* n_out, int* path_out);
 
+/* ---- WAV in every common sample encoding.  wh_wav_info (host only, no context / GPU needed)
+   reads the RIFF/WAVE header; the samples are decoded from the file's own bytes on the device
+   (wh_wav_ingest).  No read passes data + n for any input.  Errors: < 0, wh_wav_last_error().
+   Chunk walk: "RIFF" <size> "WAVE", then chunks (id, 32-bit size, body, a pad byte after an odd
+     size).  The first `fmt ` must precede `data`; later `fmt ` chunks and unknown chunks (LIST,
+     fact, bext, ...) are skipped; a chunk before `data` that runs past the end is refused.
+     RF64 / BW64 are refused by name.
+   Format tag: 1 PCM, 3 IEEE float, 6 A-law, 7 mu-law, 0xFFFE extensible (cbSize >= 22; the tag
+     is the first two bytes of SubFormat, whose other 14 bytes must be 00 00 00 00 10 00 80 00
+     00 AA 00 38 9B 71).  Any other tag is refused and the message names it.
+   Sample container: block_align / channels bytes, which must divide exactly and be what
+     bits-per-sample rounds up to.  PCM: 1, 2, 3, 4 bytes give U8, S16, S24, S32, and the WHOLE
+     container is the sample (WAV left-justifies fewer valid bits: 20-in-24 scales by 2^-23);
+     valid_bits (wValidBitsPerSample of an extensible header, else bits-per-sample) is reported
+     only.  Float: 4 or 8.  A-law / mu-law: 1.  Anything else is refused.
+   Limits: channels 1..256, rate >= 1 (wh_audio_ingest's).
+   Frames: n_frames = min(declared data size, bytes present after the data header) / block_align;
+     a declared size of 0 or 0xFFFFFFFF means "to the end of the file"; a trailing partial frame
+     is dropped; zero frames is refused.  data_offset + n_frames * block_align <= n always.
+
+   The value of a sample (whisper/audio.py restates this in numpy), little-endian:
+     U8 byte - 128 at 8 bits; S16 / S24 / S32 two's complement at 16 / 24 / 32 bits;
+     mu-law  u = ~b & 0xFF, e = (u >> 4) & 7, m = u & 15, mag = (((m << 3) + 0x84) << e) - 0x84,
+             negative iff u & 0x80, at 16 bits;
+     A-law   a = b ^ 0x55, e = (a >> 4) & 7, m = a & 15,
+             mag = e ? ((m << 4) + 0x108) << (e - 1) : (m << 4) + 8, positive iff a & 0x80, at 16 bits;
+     F32 / F64 widened to fp64, a non-finite value is 0.0, finite values clamped to [-256, 256].
+   An integer frame is x[m] of wh_audio_ingest (the int64 sum of the channels * 2^-(bits-1) /
+   channels); a float frame is its channels added in channel order in fp64, divided by channels.
+   From x[m] on everything is wh_audio_ingest's: the filter, the quantisation, the segments.
+
+   wh_wav_ingest: a whole WAV file -> the resident 16 kHz waveform.  Only the data chunk is
+   uploaded (3 bytes per 24-bit sample, 1 per G.711 sample) and the resampling kernel reads the
+   encoding itself.  up, down, taps as for wh_audio_ingest, from the file's rate (wh_wav_info).
+   wh_audio_ingest's segment semantics (dst_offset, reserve, n_out) and refusals before the first
+   HIP call (a stream wh_wav_info refuses, null data / n_out, up / down, n_taps, dst_offset,
+   reserve): the resident segments and the mel stay as they were.  It moves
+   WH_STAT_INGEST_COPY_MS and WH_STAT_INGEST_KERNEL_MS and no other counter. */
+enum { WH_WAV_U8 = 0, WH_WAV_S16, WH_WAV_S24, WH_WAV_S32, WH_WAV_F32, WH_WAV_F64, WH_WAV_ALAW, WH_WAV_ULAW };
+typedef struct wh_wav_fmt { int encoding, channels, sample_rate, valid_bits; int64_t data_offset, n_frames; } wh_wav_fmt;
+int wh_wav_info(const uint8_t* data, int64_t n, wh_wav_fmt* out);
+const char* wh_wav_last_error(void);
+int wh_wav_ingest(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int down, const double* taps,
+                  int n_taps, int64_t dst_offset, int64_t reserve, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

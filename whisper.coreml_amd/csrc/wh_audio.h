@@ -35,6 +35,8 @@ struct AudioFront {
   int flac_decode_device(const uint8_t* data, int64_t n, int32_t* out, int64_t cap, int64_t* n_frames, int* path);
   int flac_ingest(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps, int64_t dst,
                   int64_t reserve, int64_t* n_out, int* path);
+  int wav_ingest(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps, int64_t dst,
+                 int64_t reserve, int64_t* n_out);
   // audio == nullptr: use the resident buffer of wh_audio_upload (n must match)
   int log_mel(const float* audio, int64_t n, int64_t pad, int n_mels, int normalize, int64_t* nf) {
     return log_mel_frames(audio, n, pad, n_mels, 0, -1, normalize, nf);
@@ -63,7 +65,7 @@ struct AudioFront {
   // resident audio: segments (offset, length) lying back to back in d_audio from sample 0
   // (wh_audio_ingest appends; an upload leaves one; a host wh_log_mel_batch leaves none)
   std::vector<std::pair<int64_t, int64_t>> audio_segs;
-  DevBuf<char> d_pcm;  // wh_audio_ingest: the file's PCM as uploaded
+  DevBuf<char> d_pcm;  // wh_audio_ingest / wh_wav_ingest: the file's PCM as uploaded
   std::map<std::pair<int, int>, double*> d_taps;  // resampling filters by (up, down)
   // wh_flac_ingest / wh_flac_decode_device: the stream, its candidates, their subframe records,
   // frame ends and staging slots, the chain and its first samples (the restore's flag behind them)
@@ -103,7 +105,8 @@ struct AudioFront {
   int ingest_check(const std::string& who, int format, int64_t n, int channels, int bits, int up, int down,
                    const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out);
   int ingest_run(const std::string& who, const void* pcm, int format, int64_t n, int channels, int bits, int up,
-                 int down, const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out);
+                 int down, const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out,
+                 int wav_encoding = -1, int frame_bytes = 0);
   int flac_device(const uint8_t* data, int64_t n, const whflac::Plan& plan, bool s32, bool* ran);
   int flac_plan_timed(const uint8_t* data, int64_t n, whflac::Plan* plan);
 };

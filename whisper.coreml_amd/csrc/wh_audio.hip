@@ -108,11 +108,15 @@ int AudioFront::ingest_check(const std::string& who, int format, int64_t n, int 
   return 0;
 }
 // pcm: the host PCM to upload, or null when the device PCM buffer (d_pcm) already holds it
-// (wh_flac_ingest's device path; its resampling time goes to WH_STAT_FLAC_RESAMPLE_MS)
+// (wh_flac_ingest's device path; its resampling time goes to WH_STAT_FLAC_RESAMPLE_MS).
+// wav_encoding >= 0 (wh_wav_ingest): pcm is a WAV data chunk in that WH_WAV_* encoding,
+// frame_bytes per frame; otherwise the encoding is the format's, int16 or int32
 int AudioFront::ingest_run(const std::string& who, const void* pcm, int format, int64_t n, int channels, int bits,
                            int up, int down, const double* taps, int n_taps, int64_t dst, int64_t reserve,
-                           int64_t* n_out) {
+                           int64_t* n_out, int wav_encoding, int frame_bytes) {
   const bool f32 = format == WH_PCM_F32;
+  const int encoding = wav_encoding >= 0 ? wav_encoding : format == WH_PCM_S32 ? WH_WAV_S32 : WH_WAV_S16;
+  if (wav_encoding < 0) frame_bytes = channels * (format == WH_PCM_S32 ? 4 : 2);
   const bool filt = !f32 && up != down;
   const int64_t no = filt ? (n * up + down - 1) / down : n;
   double* dt = nullptr;
@@ -137,12 +141,12 @@ int AudioFront::ingest_run(const std::string& who, const void* pcm, int format, 
     HIPCHK(hipMemcpyAsync(d_audio.p + dst, pcm, (size_t)n * 4, hipMemcpyHostToDevice, st));
     TRY(tm.finish(st, stats[WH_STAT_INGEST_COPY_MS]));
   } else {
-    const size_t bytes = (size_t)n * channels * (format == WH_PCM_S32 ? 4 : 2);
-    if (pcm) TRY(d_pcm.reserve(bytes));
+    const size_t bytes = (size_t)n * frame_bytes;
+    if (pcm) TRY(d_pcm.reserve(bytes + 8));  // 24-bit samples are read as aligned dwords
     TRY(tm.mark(0, st));
     if (pcm) HIPCHK(hipMemcpyAsync(d_pcm.p, pcm, bytes, hipMemcpyHostToDevice, st));
     TRY(tm.mark(1, st));
-    launch_pcm_resample(d_pcm.p, format == WH_PCM_S32, n, channels, bits, up, down, dt, d_audio.p + dst, no, st);
+    launch_pcm_resample(d_pcm.p, encoding, n, channels, bits, up, down, dt, d_audio.p + dst, no, st);
     TRY(tm.mark(2, st));
     HIPCHK(hipStreamSynchronize(st));
     TRY(launch_status("audio_ingest"));
@@ -271,6 +275,23 @@ int AudioFront::flac_ingest(const uint8_t* data, int64_t n, int up, int down, co
   if (format == WH_PCM_S32) return audio_ingest(pcm.data(), format, got, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out);
   std::vector<int16_t> pcm16(pcm.begin(), pcm.begin() + (size_t)got * si.channels);
   return audio_ingest(pcm16.data(), format, got, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out);
+}
+// ------------------------------------------------------------ WAV
+// (include/whisper_hip.h).  The header is parsed on the host (csrc/wh_wav.cpp); the data chunk
+// goes up as it is and the resampling kernel reads its encoding.
+int AudioFront::wav_ingest(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps,
+                           int64_t dst, int64_t reserve, int64_t* n_out) {
+  const std::string who = "wav_ingest: ";
+  if (!data) return fail(-1, who + "null data");
+  wh_wav_fmt f;
+  if (wh_wav_info(data, n, &f) != 0) return fail(-7, who + wh_wav_last_error());
+  //                         U8 S16 S24 S32 F32 F64 ALAW ULAW
+  static const int container[8] = {1, 2, 3, 4, 4, 8, 1, 1};
+  static const int bits[8] = {8, 16, 24, 32, 1, 1, 16, 16};  // the scale is 2^-(bits-1): 1 for floats
+  // the ingest's own refusals; the sample format is the file's, so a valid one stands in
+  TRY(ingest_check(who, WH_PCM_S32, f.n_frames, f.channels, 32, up, down, taps, n_taps, dst, reserve, n_out));
+  return ingest_run(who, data + f.data_offset, WH_PCM_S32, f.n_frames, f.channels, bits[f.encoding], up, down, taps,
+                    n_taps, dst, reserve, n_out, f.encoding, container[f.encoding] * f.channels);
 }
 int AudioFront::audio_read(float* out, int64_t offset, int64_t n) {
   if (!out) return fail(-1, "audio_read: null out");

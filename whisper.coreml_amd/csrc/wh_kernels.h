@@ -96,11 +96,13 @@ int mel_blocks(int64_t nframes);  // frame blocks one file takes (whole blocks)
 // segmented log-mel of every file, raw values then each file's own max-8 floor and scaling
 void launch_mel_seg(const float* audio, const MelFile* files, int n_files, int64_t n_blocks, const float* filters,
                     int n_mels, float* mel, int64_t ld, unsigned* gmax, hipStream_t st);
-// wh_audio_ingest's kernel: interleaved int16 (s32 = 0) or int32 PCM [n_frames][channels] of
-// `bits` significant bits -> n_out mono float32 samples at 16 kHz, accumulated in fp64 and
-// quantised to 16-bit steps.  taps [2*10*max(up, down) + 1] doubles on the device, or null
-// when up == down (mix and quantise only).  One launch.
-void launch_pcm_resample(const void* pcm, int s32, int64_t n_frames, int channels, int bits, int up, int down,
+// wh_audio_ingest's kernel: interleaved PCM [n_frames][channels] in `encoding` (a WH_WAV_* code
+// of include/whisper_hip.h; S16 and S32 are what wh_audio_ingest and the FLAC path hold) at
+// 2^-(bits-1) per step (bits = 1 for the float encodings) -> n_out mono float32 samples at
+// 16 kHz, accumulated in fp64 and quantised to 16-bit steps.  taps [2*10*max(up, down) + 1]
+// doubles on the device, or null when up == down (mix and quantise only).  The buffer must be
+// allocated 8 bytes past the samples (24-bit samples are read as aligned dwords).  One launch.
+void launch_pcm_resample(const void* pcm, int encoding, int64_t n_frames, int channels, int bits, int up, int down,
                          const double* taps, float* out, int64_t n_out, hipStream_t st);
 
 // ------------------------------------------------------------ decode state (device)

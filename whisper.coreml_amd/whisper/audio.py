@@ -30,7 +30,9 @@ def load_audio(file: str, sr: int = SAMPLE_RATE) -> np.ndarray:
     """Mono float32 waveform at ``sr`` (audio.py:25-62).  The reference pipes the file
     through the ffmpeg CLI (``-ac 1 -ar sr -f s16le``), which neither this image nor
     the GPU box has.  Here: FLAC is decoded by the library's host FLAC reader
-    (bit-exact, ``wh_flac_decode``) and 16-bit PCM WAV by ``wave``; then, as ffmpeg's
+    (bit-exact, ``wh_flac_decode``), plain 16-bit PCM WAV by ``wave`` and every other WAV
+    encoding (8 / 24 / 32-bit PCM, float, A-law, mu-law, extensible headers) by
+    ``wav_info`` and ``wav_samples``; then, as ffmpeg's
     command line asks, channels are averaged to mono, the rate is converted to ``sr``
     (polyphase FIR, ``scipy.signal.resample_poly``) and the result is quantised to
     16-bit PCM and scaled by 1/32768.  ffmpeg's own resampling filter is not
@@ -41,19 +43,102 @@ def load_audio(file: str, sr: int = SAMPLE_RATE) -> np.ndarray:
 
 def read_pcm(file: str):
     """The file's samples as stored: (pcm [frames][channels], sample rate, bits per sample).
-    FLAC gives int32 (``wh_flac_decode``), 16-bit PCM WAV gives int16."""
+    FLAC gives int32 (``wh_flac_decode``), a plain 16-bit PCM WAV gives int16 (read with
+    ``wave``).  Every other WAV goes through ``wav_info`` and ``wav_samples``: the integer
+    and G.711 encodings give integers at 8 / 16 / 24 / 32 bits, the float encodings give
+    ``(float64 [frames][channels], rate, 0)``."""
     low = file.lower()
     if low.endswith(".flac"):
         from .backend_hip import decode_flac
         with open(file, "rb") as f:
             return decode_flac(f.read())
     if low.endswith(".wav"):
+        plain = _read_wav16(file)
+        if plain is not None:
+            return plain
+        with open(file, "rb") as f:
+            data = f.read()
+        try:
+            info = wav_info(data)
+        except RuntimeError as e:
+            raise RuntimeError(f"Failed to load audio: {file}: {e}") from None
+        pcm, bits = wav_samples(data, info)
+        return pcm, info.sample_rate, bits
+    raise RuntimeError(f"Failed to load audio: {file}: without ffmpeg only .flac and .wav are supported (WAV: PCM at "
+                       "8, 16, 24 or 32 bits, IEEE float at 32 or 64 bits, A-law, mu-law; plain or extensible header)")
+
+
+def _read_wav16(file: str):
+    """(int16 pcm, rate, 16) of a plain (format tag 1) 16-bit PCM WAV read with ``wave``; None
+    for any WAV that ``wave`` does not take or that is not 16-bit."""
+    try:
         with wave.open(file, "rb") as w:
             if w.getsampwidth() != 2:
-                raise RuntimeError(f"Failed to load audio: {file}: need 16-bit PCM WAV")
+                return None
             pcm = np.frombuffer(w.readframes(w.getnframes()), np.int16).reshape(-1, w.getnchannels())
             return pcm, w.getframerate(), 16
-    raise RuntimeError(f"Failed to load audio: {file}: only .flac and 16-bit PCM .wav are supported without ffmpeg")
+    except (wave.Error, EOFError):
+        return None
+
+
+WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32, WAV_F64, WAV_ALAW, WAV_ULAW = range(8)  # WH_WAV_*
+WAV_ENCODINGS = ("u8", "s16", "s24", "s32", "f32", "f64", "alaw", "ulaw")
+WAV_CONTAINER = (1, 2, 3, 4, 4, 8, 1, 1)  # bytes per sample
+
+
+def wav_info(data: bytes):
+    """``wh_wav_info`` of a WAV file's bytes: ``WavInfo(encoding, channels, sample_rate,
+    valid_bits, data_offset, n_frames)``, ``encoding`` one of ``WAV_*`` (include/whisper_hip.h
+    has the parsing rules).  Raises ``HipBackendError`` with the parser's message."""
+    from .backend_hip import wav_info as _wav_info
+    return _wav_info(data)
+
+
+@lru_cache(maxsize=None)
+def g711_table(encoding: int) -> np.ndarray:
+    """The 256 int16 values of the A-law / mu-law codes (ITU-T G.711, the formulas of
+    include/whisper_hip.h; read-only)."""
+    b = np.arange(256, dtype=np.int32)
+    if encoding == WAV_ULAW:
+        u = ~b & 0xFF
+        e, m = (u >> 4) & 7, u & 15
+        mag = (((m << 3) + 0x84) << e) - 0x84
+        t = np.where(u & 0x80, -mag, mag)
+    elif encoding == WAV_ALAW:
+        a = b ^ 0x55
+        e, m = (a >> 4) & 7, a & 15
+        mag = np.where(e > 0, ((m << 4) + 0x108) << np.maximum(e - 1, 0), (m << 4) + 8)
+        t = np.where(a & 0x80, mag, -mag)
+    else:
+        raise ValueError(f"encoding {encoding} is not G.711")
+    t = t.astype(np.int16)
+    t.setflags(write=False)
+    return t
+
+
+def wav_samples(data: bytes, info):
+    """The samples of a WAV data chunk on the host, the definition the device reader matches:
+    (pcm [frames][channels], bits).  U8 is ``byte - 128`` at 8 bits; S16 / S24 / S32 are
+    little-endian two's complement at 16 / 24 / 32 bits (the whole container, whatever
+    ``valid_bits`` says); A-law / mu-law expand to int16 at 16 bits; the float encodings give
+    float64 with ``bits = 0``."""
+    enc, ch = info.encoding, info.channels
+    raw = np.frombuffer(data, np.uint8, info.n_frames * ch * WAV_CONTAINER[enc], info.data_offset).copy()
+    if enc == WAV_U8:
+        pcm, bits = raw.astype(np.int16) - 128, 8
+    elif enc == WAV_S16:
+        pcm, bits = raw.view("<i2"), 16
+    elif enc == WAV_S24:
+        b = raw.reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | b[:, 1] << 8 | b[:, 2] << 16
+        pcm, bits = (v ^ 0x800000) - 0x800000, 24
+    elif enc == WAV_S32:
+        pcm, bits = raw.view("<i4"), 32
+    elif enc in (WAV_F32, WAV_F64):
+        pcm, bits = raw.view("<f4" if enc == WAV_F32 else "<f8").astype(np.float64), 0
+    else:
+        pcm, bits = g711_table(enc)[raw], 16
+    return pcm.reshape(info.n_frames, ch), bits
 
 
 def _ratio(rate: int, sr: int = SAMPLE_RATE):
@@ -63,11 +148,21 @@ def _ratio(rate: int, sr: int = SAMPLE_RATE):
 
 
 def pcm_to_waveform(pcm: np.ndarray, rate: int, bits: int, sr: int = SAMPLE_RATE) -> np.ndarray:
-    """Integer PCM [frames][channels] -> mono float32 at ``sr`` on the host, in float64:
-    channel mean, polyphase FIR, 16-bit quantisation, scaling by 1/32768.  The device path
-    (``HipContext.audio_ingest``) gives the same samples bit for bit."""
-    x = np.asarray(pcm).reshape(len(pcm), -1).astype(np.float64) / float(1 << (bits - 1))
-    x = x.mean(axis=1)
+    """PCM [frames][channels] -> mono float32 at ``sr`` on the host, in float64: channel mean,
+    polyphase FIR, 16-bit quantisation, scaling by 1/32768.  Integers of ``bits`` bits scale
+    by 2^-(bits-1).  ``bits == 0``: float samples; a non-finite one counts as 0.0, finite ones
+    are clamped to [-256, 256], and a frame's channels are added in channel order.  The device
+    paths (``HipContext.audio_ingest`` / ``wav_ingest``) give the same samples bit for bit."""
+    if bits == 0:
+        x = np.asarray(pcm, dtype=np.float64).reshape(len(pcm), -1)
+        x = np.clip(np.where(np.isfinite(x), x, 0.0), -256.0, 256.0)
+        total = x[:, 0].copy()
+        for c in range(1, x.shape[1]):  # not mean(axis=1): its order changes with the channel count
+            total += x[:, c]
+        x = total / x.shape[1]
+    else:
+        x = np.asarray(pcm).reshape(len(pcm), -1).astype(np.float64) / float(1 << (bits - 1))
+        x = x.mean(axis=1)
     if rate != sr:
         from scipy.signal import resample_poly
         x = resample_poly(x, *_ratio(rate, sr))
@@ -176,9 +271,12 @@ def device_filter_taps(rate: int, sr: int = SAMPLE_RATE) -> int:
 def ingest_source(file: str, need_length: bool = False):
     """How a file's audio reaches the device, decided in one place: (source, length).
     ``source`` is ``(flac bytes,)`` for ``HipContext.flac_ingest`` (the frames are decoded
-    on the device), ``(pcm, rate, bits)`` for ``HipContext.audio_ingest`` (mixed down and
-    resampled on the device), or the 16 kHz waveform as an array when the rate's filter
-    would exceed ``MAX_DEVICE_TAPS`` and the host resampled it.  ``length`` is the 16 kHz
+    on the device), ``(wav bytes, wav_info)`` for ``HipContext.wav_ingest`` (every WAV but the
+    plain 16-bit one: the data chunk is uploaded in the file's own encoding and read by the
+    resampling kernel), ``(pcm, rate, bits)`` for ``HipContext.audio_ingest`` (a plain 16-bit
+    WAV, or a FLAC decoded on the host: mixed down and resampled on the device), or the
+    16 kHz waveform as an array when the rate's filter would exceed ``MAX_DEVICE_TAPS`` and
+    the host resampled it.  ``length`` is the 16 kHz
     sample count the source gives; None for a FLAC whose STREAMINFO has no total, unless
     ``need_length``: then such a file is decoded on the host instead."""
     if file.lower().endswith(".flac"):
@@ -189,12 +287,29 @@ def ingest_source(file: str, need_length: bool = False):
         if device_filter_taps(rate) <= MAX_DEVICE_TAPS and (frames > 0 or not need_length):
             up, down = _ratio(rate)
             return (data,), (frames * up + down - 1) // down if frames > 0 else None
-    pcm, rate, bits = read_pcm(file)
+    plain = _read_wav16(file) if file.lower().endswith(".wav") else None
+    if file.lower().endswith(".wav") and plain is None:
+        with open(file, "rb") as f:
+            data = f.read()
+        info = wav_info(data)
+        if device_filter_taps(info.sample_rate) <= MAX_DEVICE_TAPS:
+            up, down = _ratio(info.sample_rate)
+            return (data, info), (info.n_frames * up + down - 1) // down
+    pcm, rate, bits = plain if plain is not None else read_pcm(file)
     if device_filter_taps(rate) > MAX_DEVICE_TAPS:
         waveform = pcm_to_waveform(pcm, rate, bits)
         return waveform, len(waveform)
     up, down = _ratio(rate)
     return (pcm, rate, bits), (len(pcm) * up + down - 1) // down
+
+
+def ingest(ctx, source, dst_offset: int = 0, reserve: int = 0):
+    """A tuple ``ingest_source`` returned, sent to the context call its shape names."""
+    if len(source) == 1:
+        return ctx.flac_ingest(source[0], dst_offset=dst_offset, reserve=reserve)
+    if len(source) == 2:
+        return ctx.wav_ingest(source[0], dst_offset=dst_offset, reserve=reserve)
+    return ctx.audio_ingest(*source, dst_offset=dst_offset, reserve=reserve)
 
 
 def load_audio_device(model, file: str):
@@ -206,6 +321,9 @@ def load_audio_device(model, file: str):
     A ``.flac`` file is not decoded on the host at all: its bytes are uploaded and its frames
     are decoded in parallel on the device (``HipContext.flac_ingest``; ``decoded_on`` of the
     result says "host" when the stream was outside that path and the host decoder ran).
+    A ``.wav`` file other than plain 16-bit PCM (24- and 32-bit, 8-bit, float, A-law, mu-law,
+    extensible headers) is not unpacked on the host either: its data chunk is uploaded as it
+    is and the kernel reads the encoding (``HipContext.wav_ingest``).
     A rate whose filter would exceed ``MAX_DEVICE_TAPS`` is resampled on the host and
     uploaded instead (``ingest_source`` decides)."""
     ctx = getattr(model, "ctx", model)
@@ -214,7 +332,7 @@ def load_audio_device(model, file: str):
     source, _ = ingest_source(file)
     if isinstance(source, np.ndarray):
         return ctx.audio_upload(source)
-    return ctx.flac_ingest(*source) if len(source) == 1 else ctx.audio_ingest(*source)
+    return ingest(ctx, source)
 
 
 def log_mel_spectrogram(audio: Union[str, np.ndarray], n_mels: int = 80, padding: int = 0,

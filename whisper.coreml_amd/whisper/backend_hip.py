@@ -12,7 +12,7 @@ Differences from the reference shim, on purpose:
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -44,6 +44,21 @@ class WhDecodeOpts(ctypes.Structure):
 class WhVadOpts(ctypes.Structure):
     _fields_ = [("ratio_q8", c_uint64), ("t_lo", c_uint64), ("t_hi", c_uint64), ("percentile", c_int),
                 ("min_silence", c_int), ("min_speech", c_int), ("pad", c_int)]
+
+
+class WhWavFmt(ctypes.Structure):
+    _fields_ = [("encoding", c_int), ("channels", c_int), ("sample_rate", c_int), ("valid_bits", c_int),
+                ("data_offset", c_int64), ("n_frames", c_int64)]
+
+
+class WavInfo(NamedTuple):
+    """What ``wh_wav_info`` reads from a WAV header (``encoding``: a WH_WAV_* code)."""
+    encoding: int
+    channels: int
+    sample_rate: int
+    valid_bits: int
+    data_offset: int
+    n_frames: int
 
 
 _lib = None
@@ -105,6 +120,10 @@ _EXPORTS = {
                                       POINTER(c_int)]),
     "wh_flac_ingest": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_int64,
                                POINTER(c_int64), POINTER(c_int)]),
+    "wh_wav_info": (c_int, [c_void_p, c_int64, POINTER(WhWavFmt)]),
+    "wh_wav_last_error": (c_char_p, []),
+    "wh_wav_ingest": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_int64,
+                              POINTER(c_int64)]),
 }
 N_STATS = 16  # WH_N_STATS
 FLAC_PATHS = ("device", "host")
@@ -201,9 +220,21 @@ def decode_flac_indexed(data: bytes):
     return out[: n.value], rate, bps, FLAC_PATHS[lib.wh_flac_last_path()]
 
 
+def wav_info(data: bytes) -> WavInfo:
+    """The header of a WAV file's bytes (wh_wav_info; host only)."""
+    lib = load_library()
+    buf = np.frombuffer(data, np.uint8)
+    f = WhWavFmt()
+    rc = lib.wh_wav_info(_ptr(buf) if len(buf) else None, len(buf), ctypes.byref(f))
+    if rc != 0:
+        msg = lib.wh_wav_last_error().decode(errors="replace") if len(buf) else "wav: empty file"
+        raise HipBackendError(f"wh_wav_info failed ({rc}): {msg}")
+    return WavInfo(f.encoding, f.channels, f.sample_rate, f.valid_bits, f.data_offset, f.n_frames)
+
+
 class DeviceAudio:
     """Audio already resident in a context's HBM (``HipContext.audio_upload`` /
-    ``audio_ingest`` / ``flac_ingest``); ``transcribe`` then starts from device memory (no
+    ``audio_ingest`` / ``flac_ingest`` / ``wav_ingest``); ``transcribe`` then starts from device memory (no
     host-to-device copy).  ``offset``: where the segment starts in the resident buffer (0
     unless it was ingested behind other files).  ``decoded_on``: "device" or "host" for a
     FLAC stream given to ``flac_ingest``, None for anything else."""
@@ -341,6 +372,20 @@ class HipContext:
                                             0 if taps is None else taps.shape[0], int(dst_offset), int(reserve),
                                             ctypes.byref(n_out), ctypes.byref(path)), "wh_flac_ingest")
         return DeviceAudio(self, n_out.value, int(dst_offset), FLAC_PATHS[path.value])
+
+    def wav_ingest(self, data: bytes, dst_offset: int = 0, reserve: int = 0) -> "DeviceAudio":
+        """A WAV file's bytes -> the waveform of ``audio.load_audio`` in the resident buffer
+        (wh_wav_ingest), with ``audio_ingest``'s segment semantics.  Only the data chunk is
+        uploaded, in the file's own sample encoding (8 / 16 / 24 / 32-bit PCM, 32 / 64-bit
+        float, A-law, mu-law), and the resampling kernel reads it."""
+        from .audio import resample_filter
+        buf = np.frombuffer(data, np.uint8)
+        up, down, taps = resample_filter(wav_info(data).sample_rate)
+        n_out = c_int64()
+        self._check(self.lib.wh_wav_ingest(self.h, _ptr(buf), len(buf), up, down, None if taps is None else _ptr(taps),
+                                           0 if taps is None else taps.shape[0], int(dst_offset), int(reserve),
+                                           ctypes.byref(n_out)), "wh_wav_ingest")
+        return DeviceAudio(self, n_out.value, int(dst_offset))
 
     def flac_decode_device(self, data: bytes):
         """``decode_flac`` on the device (wh_flac_decode_device): (samples int32

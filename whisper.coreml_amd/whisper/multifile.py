@@ -12,7 +12,8 @@ driver of it and adds only which lanes are live.
 Files are taken in groups whose log-mel fits ``mel_budget_frames``.  A group's files
 are ingested back to back into the context's resident audio (``audio.ingest_source``
 decides how: a path's PCM is mixed down and resampled there, ``HipContext.audio_ingest``;
-a ``.flac`` path's frames are also decoded there, ``HipContext.flac_ingest``; an array is
+a ``.flac`` path's frames are also decoded there, ``HipContext.flac_ingest``; a ``.wav``
+path's data chunk is read there in its own encoding, ``HipContext.wav_ingest``; an array is
 copied), and one
 ``log_mel_batch_resident`` call computes the group's mel (each file normalised with
 its own max), the files' frames lying back to back in the context mel.  At most
@@ -25,7 +26,7 @@ from typing import TYPE_CHECKING, Callable, List, Optional, Sequence, Tuple, Uni
 
 import numpy as np
 
-from .audio import HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, ingest_source
+from .audio import HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, ingest, ingest_source
 from .backend_hip import DeviceAudio
 from .decoding import DecodingResult, language_probs, next_seed
 from .tokenizer import LANGUAGES, get_tokenizer
@@ -159,8 +160,8 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     n_mels = model.dims.n_mels
     if isinstance(audios, (str, np.ndarray, DeviceAudio)):
         raise TypeError("audios must be a sequence of paths and/or 1-D arrays")
-    # what audio_ingest takes per file, (pcm or waveform, rate, bits), or (FLAC bytes,) for
-    # flac_ingest, and the 16 kHz length it gives
+    # what audio_ingest takes per file, (pcm or waveform, rate, bits), (FLAC bytes,) for
+    # flac_ingest or (WAV bytes, its wav_info) for wav_ingest, and the 16 kHz length it gives
     sources: List[tuple] = []
     lengths: List[int] = []
     for i, a in enumerate(audios):
@@ -193,8 +194,7 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
         total = sum(lengths[i] for i in group)
         offset = 0
         for i in group:
-            ingest = ctx.flac_ingest if len(sources[i]) == 1 else ctx.audio_ingest
-            seg = ingest(*sources[i], dst_offset=offset, reserve=total)
+            seg = ingest(ctx, sources[i], dst_offset=offset, reserve=total)
             if seg.n_samples != lengths[i]:
                 raise RuntimeError(f"audio {i}: {seg.n_samples} samples ingested, {lengths[i]} planned")
             offset += seg.n_samples
