@@ -67,6 +67,30 @@ typedef struct wh_decode_opts {
   unsigned long long seed; /* sampling RNG seed */
   int max_candidates;    /* beam: round(beam_size * patience) as the host computes it
                             (Python round, decoding.py:339); <= 0: derived from patience */
+  /* Repetition controls of the device loop (wh_version >= 2).  Both are off when zero, so a
+     caller that zero-initialises the struct and fills the fields above decodes as before.
+     They act on the raw logits of every update, ahead of SuppressBlank, SuppressTokens and
+     ApplyTimestampRules (a LogitFilter at the head of the reference's list, decoding.py:
+     450-532), so the timestamp-versus-text comparison sees the filtered logits.  Per row,
+     seq = tokens[sample_begin : len]: the sampled tokens only, not the prompt, the SOT
+     sequence or a prefix.
+       repetition_penalty p (0 or 1 = off): for every distinct id t < eot in seq,
+         x[t] = x[t] > 0 ? x[t] / p : x[t] * p, in fp32 (the division correctly rounded),
+         once per id however often it occurs.
+       no_repeat_ngram n (0 = off, 1..16), only if len(seq) >= n: with suf the last n - 1
+         tokens of seq, for every q in [0, len(seq) - n] with seq[q : q+n-1] == suf and
+         seq[q+n-1] < eot: x[seq[q+n-1]] = -inf.  The window at q may overlap suf; matching
+         is on raw ids, so timestamp tokens take part in the n-grams; n = 1 bans every text
+         id sampled so far.
+     The penalty comes first, then the ban.  eot and every id above it (specials,
+     timestamps) are never changed, so a row cannot become all -inf through these.
+     wh_decode_begin refuses (-11, the field named in wh_last_error, the context's decode
+     state unchanged) an n outside 0..16, a penalty that is negative, NaN or infinite, and
+     either option where the selection would not run in its sliced kernels (a vocabulary
+     they do not fit, or the tuning switch WHISPER_HIP_LOGIT_SPLIT=0).  wh_prefill / wh_step
+     hand the logits to the host and apply no filter. */
+  int no_repeat_ngram;
+  float repetition_penalty;
 } wh_decode_opts;
 
 const char* wh_last_error(void);

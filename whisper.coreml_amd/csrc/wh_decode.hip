@@ -643,7 +643,15 @@ __device__ __forceinline__ void lp_combine(const LPRec* rec, int r, const DecSta
 // merge_window<512, sc1 candidate loads>).  A finished window's rows are re-embedded by
 // its first row's first slice.
 //
-template <int NS, int LP_EPT, bool MERGE = false>
+// RF: the repetition filter (DecOpts::no_repeat_ngram / repetition_penalty), on the raw
+// logits ahead of the other filters.  The row's history goes to LDS (it is already loaded
+// one position per thread); the thread of a sampled position p in [sb, len) whose token is a
+// text id (< eot) of this slice sets its bit in the slice's `seen` mask, and in the `ban`
+// mask when the n - 1 tokens before p equal the last n - 1 of the row (p - (n - 1) >= sb:
+// the window lies in the sampled part, which also makes len - sb >= n).  LDS atomics, one
+// barrier more than the unfiltered kernel (the masks are cleared before it); step 3 reads
+// two bits per element.  The timestamp slice holds no text id: it skips all of it.
+template <int NS, int LP_EPT, bool MERGE = false, bool RF = false>
 __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __restrict__ logits, int ldl, DecState s,
                                                            DecOpts o, MergeEmbed em) {
   CT_MARK(CT_LOGIT, 0);
@@ -678,6 +686,28 @@ __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __r
     if constexpr (MERGE)
       if (j == 0 && r == w * s.G) merge_window<LP_THREADS, false>(s, o, em, w, tid, mlds);
     return;
+  }
+  constexpr int RF_WORDS = RF ? LP_THREADS * LP_EPT / 32 : 1;  // hi - lo <= LP_THREADS * LP_EPT (the launcher)
+  __shared__ unsigned rf_seen[RF_WORDS], rf_ban[RF_WORDS];
+  __shared__ int rf_hist[RF ? LP_THREADS : 1];
+  const bool rf = RF && j != NS - 1;  // one slice per workgroup: uniform
+  const float pen = o.repetition_penalty;
+  if constexpr (RF) {
+    if (rf) {
+      rf_hist[tid] = hp;
+      for (int k = tid; k < RF_WORDS; k += LP_THREADS) { rf_seen[k] = 0u; rf_ban[k] = 0u; }
+      wh_lds_barrier();
+      if (tid >= sb && tid < len && hp >= lo && hp < hi && hp < o.eot) {
+        const int b = hp - lo;
+        if (pen != 1.f) __hip_atomic_fetch_or(&rf_seen[b >> 5], 1u << (b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const int n = o.no_repeat_ngram;
+        if (n > 0 && tid - (n - 1) >= sb) {
+          bool eq = true;
+          for (int k = 1; k < n; ++k) eq &= rf_hist[tid - k] == rf_hist[len - k];
+          if (eq) __hip_atomic_fetch_or(&rf_ban[b >> 5], 1u << (b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
+    }
   }
   // 2. history facts (decoding.py:503-508): the last timestamp token of the sampled
   // part [sb, len) and the last two tokens (through LDS, across the barrier)
@@ -731,6 +761,18 @@ __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __r
     const int i = lo + tid + LP_THREADS * u;
     if (i >= hi) { xv[u] = -INFINITY; continue; }
     bool kill = (sw[u] >> (i & 31)) & 1u;
+    if constexpr (RF) {
+      if (rf) {
+        const int b = i - lo;
+        if ((rf_seen[b >> 5] >> (b & 31)) & 1u) {
+          // the correctly rounded division (no reciprocal multiply: tokens are compared
+          // with a host restatement), once per id
+          xv[u] = xv[u] > 0.f ? xv[u] / pen : xv[u] * pen;
+          row[i] = xv[u];
+        }
+        kill |= (rf_ban[b >> 5] >> (b & 31)) & 1u;
+      }
+    }
 #pragma unroll
     for (int b = 0; b < 5; ++b) kill |= i == kid[b];
 #pragma unroll
@@ -987,24 +1029,38 @@ __device__ __forceinline__ void lp_combine(const LPRec* rec, int r, const DecSta
   }
 }
 
-// the selection of one update; with `em` (launch_select_merge) the fused k_logit_part also
-// runs each window's merge and this returns true
-static bool select_rows(float* logits, int ldl, const DecState& s, const DecOpts& o, int nwin, hipStream_t st,
-                        const MergeEmbed* em) {
+int logit_slices(const DecState& s, const DecOpts& o, int nwin) {
   // the sliced selection (k_logit_part) unless WHISPER_HIP_LOGIT_SPLIT=0
   // (config 2, turbo one window: 0.380 -> 0.346 ms per token; config 3 unchanged)
   static const bool split = [] {
     const char* e = tune_env("WHISPER_HIP_LOGIT_SPLIT");
     return !(e && e[0] == '0');
   }();
+  const bool sp = split && s.hctx <= LP_THREADS;  // k_logit_part: one history position per thread
+  const bool one_win = nwin == 1;
+  if (sp && !one_win && o.ts_begin > 0 && (o.ts_begin + 14) / 15 <= LP_THREADS * 8 && o.V - o.ts_begin <= LP_THREADS * 8)
+    return 16;
+  if (sp && o.ts_begin > 0 && one_win && (o.ts_begin + 30) / 31 <= LP_THREADS * 4 && o.V - o.ts_begin <= LP_THREADS * 4)
+    return 32;
+  if (sp && o.ts_begin > 0 && (o.ts_begin + 6) / 7 <= LP_THREADS * 16 && o.V - o.ts_begin <= LP_THREADS * 16)
+    return 8;
+  return 0;
+}
+
+// the selection of one update; with `em` (launch_select_merge) the fused k_logit_part also
+// runs each window's merge and this returns true
+static bool select_rows(float* logits, int ldl, const DecState& s, const DecOpts& o, int nwin, hipStream_t st,
+                        const MergeEmbed* em) {
   const int rows = nwin * s.G;
   const bool merge = em && s.lpw_cnt && s.G <= MG_MAXG;  // the window's merge in the selection launch
-  const bool sp = split && s.hctx <= LP_THREADS;  // k_logit_part: one history position per thread
+  const bool rfo = repeat_filter_on(o);
   const MergeEmbed none;
   const MergeEmbed& e = em ? *em : none;
 #define LP(NS_, EPT_)                                                                                                  \
   do {                                                                                                                 \
-    if (merge) k_logit_part<NS_, EPT_, true><<<dim3(rows, NS_), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part"); \
+    if (merge && rfo) k_logit_part<NS_, EPT_, true, true><<<dim3(rows, NS_), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part"); \
+    else if (rfo) k_logit_part<NS_, EPT_, false, true><<<dim3(rows, NS_), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part"); \
+    else if (merge) k_logit_part<NS_, EPT_, true><<<dim3(rows, NS_), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part"); \
     else k_logit_part<NS_, EPT_><<<dim3(rows, NS_), LP_THREADS, 0, st>>>(logits, ldl, s, o, e), wh_launched("k_logit_part"); \
     return merge;                                                                                                      \
   } while (0)
@@ -1016,14 +1072,13 @@ static bool select_rows(float* logits, int ldl, const DecState& s, const DecOpts
   // the same window-count cut as the k_proj1 layers (wh_runtime.hip p1_active), so the
   // rule holds for greedy and small beams too.  8 slices (16 elements per lane) serve the
   // vocabularies too large for either.
-  const bool one_win = nwin == 1;
-  if (sp && !one_win && o.ts_begin > 0 && (o.ts_begin + 14) / 15 <= LP_THREADS * 8 && o.V - o.ts_begin <= LP_THREADS * 8)
-    LP(16, 8);
-  if (sp && o.ts_begin > 0 && one_win && (o.ts_begin + 30) / 31 <= LP_THREADS * 4 && o.V - o.ts_begin <= LP_THREADS * 4)
-    LP(32, 4);
-  if (sp && o.ts_begin > 0 && (o.ts_begin + 6) / 7 <= LP_THREADS * 16 && o.V - o.ts_begin <= LP_THREADS * 16)
-    LP(8, 16);
+  const int ns = logit_slices(s, o, nwin);
+  if (ns == 16) LP(16, 8);
+  if (ns == 32) LP(32, 4);
+  if (ns == 8) LP(8, 16);
 #undef LP
+  // the repetition filter has no single-workgroup form: wh_decode_begin refuses the options
+  // wherever logit_slices gives 0, so this launch never drops them
   k_logit_rows<<<nwin * s.G, LR_THREADS, 0, st>>>(logits, ldl, s, o), wh_launched("k_logit_rows");
   return false;
 }

@@ -138,11 +138,22 @@ struct DecOpts {
   int sample_len;                    // max updates
   int n_ctx;                         // text context (448): stop when len > n_ctx
   float temperature;                 // > 0: Gumbel-max sampling (greedy decoder)
+  // repetition filter over the sampled tokens hist[sample_begin, len) of each row, on the raw
+  // logits ahead of every other filter (include/whisper_hip.h, wh_decode_opts):
+  int no_repeat_ngram;               // 0 = off, 1..16: ban the text ids that would repeat an n-gram
+  float repetition_penalty;          // 1 = off (set_opts stores 1 for 0): x > 0 ? x / p : x * p for
+                                     // every text id sampled so far
 };
+inline bool repeat_filter_on(const DecOpts& o) {
+  return o.no_repeat_ngram > 0 || (o.repetition_penalty != 1.f && o.repetition_penalty != 0.f);
+}
 
 constexpr int LP_SLICES = 32;  // vocabulary slices per row: 31 text slices + [timestamp_begin, V)
 constexpr int LP_REC = 32;    // words per slice record
 void launch_logit_rows(float* logits, int ldl, const DecState& s, const DecOpts& o, int nwin, hipStream_t st);
+// vocabulary slices per row the selection of nwin windows runs with (k_logit_part), 0 where
+// it is k_logit_rows; the repetition filter exists in the sliced kernels only
+int logit_slices(const DecState& s, const DecOpts& o, int nwin);
 // k_merge also writes the NEXT step's decoder input rows (the embedding of each row's
 // newest token, k_embed's arithmetic) when em.x is set: the step graph then starts with
 // the first layer instead of a separate k_embed launch (round 4)

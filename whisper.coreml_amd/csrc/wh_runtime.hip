@@ -955,9 +955,29 @@ struct Ctx : public wh_ctx {
   }
 
   // ------------------------------------------------------------ decoding
-  int set_opts(const wh_decode_opts* o) {
+  int set_opts(const wh_decode_opts* o, int n_win) {
+    // every refusal comes before the first write: a refused call leaves O, S and maxc alone
     if (o->group < 1 || o->group > Gcap) return fail(-11, "group exceeds context max_group");
+    // max_candidates = round(beam_size * patience) (decoding.py:339): Python rounds half
+    // to even; the host passes its own value, else nearbyint (default mode: half to even)
+    const int mc = !o->beam ? 0
+                   : o->max_candidates > 0 ? o->max_candidates
+                                           : (int)std::nearbyint((double)o->group * (o->patience > 0 ? o->patience : 1.0));
+    if (o->beam && (mc < 1 || mc > 16)) return fail(-11, "max_candidates out of range (1..16)");
+    if (o->no_repeat_ngram < 0 || o->no_repeat_ngram > 16)
+      return fail(-11, "no_repeat_ngram " + std::to_string(o->no_repeat_ngram) + " out of range (0..16)");
+    if (!(o->repetition_penalty >= 0.f) || std::isinf(o->repetition_penalty))
+      return fail(-11, "repetition_penalty must be finite and not negative (0 or 1: off)");
+    const float pen = o->repetition_penalty == 0.f ? 1.f : o->repetition_penalty;
+    if (o->no_repeat_ngram > 0 || pen != 1.f) {
+      DecOpts q = DecOpts();
+      q.V = V; q.ts_begin = o->timestamp_begin;
+      if (!logit_slices(S, q, n_win))
+        return fail(-11, "no_repeat_ngram / repetition_penalty need the sliced selection (k_logit_part): "
+                         "not with this vocabulary or WHISPER_HIP_LOGIT_SPLIT=0");
+    }
     O = DecOpts();
+    O.no_repeat_ngram = o->no_repeat_ngram; O.repetition_penalty = pen;
     O.V = V; O.eot = o->eot; O.ts_begin = o->timestamp_begin; O.no_ts = o->no_timestamps;
     O.n_blank = std::min(o->n_blank, 3);
     for (int i = 0; i < O.n_blank; ++i) O.blank[i] = o->blank[i];
@@ -973,12 +993,7 @@ struct Ctx : public wh_ctx {
     }
     HIPCHK(hipMemcpyAsync(suppress, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, st));
     O.suppress = o->n_suppress > 0 ? suppress : nullptr;
-    // max_candidates = round(beam_size * patience) (decoding.py:339): Python rounds half
-    // to even; the host passes its own value, else nearbyint (default mode: half to even)
-    maxc = !o->beam ? 0
-           : o->max_candidates > 0 ? o->max_candidates
-                                   : (int)std::nearbyint((double)o->group * (o->patience > 0 ? o->patience : 1.0));
-    if (o->beam && (maxc < 1 || maxc > 16)) return fail(-11, "max_candidates out of range (1..16)");
+    maxc = mc;
     S.G = o->group;
     S.maxc = 16;
     return 0;
@@ -1116,7 +1131,7 @@ struct Ctx : public wh_ctx {
                    const int* sot_index, const int* slots) override {
     if (!finalized) return fail(-9, "weights not finalized");
     if (n_win < 1 || n_win > Wcap) return fail(-11, "n_win out of range");
-    TRY(set_opts(o));
+    TRY(set_opts(o, n_win));
     TRY(tm.mark(0, st));
     TRY(begin_batch(n_win, o->group, init, n_init, max_init, sot_index, o->no_speech, slots));
     S.maxc = std::max(maxc, 1);
@@ -1727,7 +1742,7 @@ int create(int device, const wh_dims& dims, int max_windows, int max_group, wh_c
 extern "C" {
 
 const char* wh_last_error(void) { return wh_error().c_str(); }
-int wh_version(void) { return 1; }
+int wh_version(void) { return 2; }  // 2: wh_decode_opts.no_repeat_ngram / repetition_penalty
 
 int wh_create(int device, const wh_dims* dims, int compute_dtype, int max_windows, int max_group, wh_ctx** out) {
   if (!dims || !out) return fail(-1, "null argument");

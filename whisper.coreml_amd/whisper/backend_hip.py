@@ -38,7 +38,8 @@ class WhDecodeOpts(ctypes.Structure):
                 ("sample_len", c_int), ("suppress_blank", c_int), ("timestamps", c_int), ("max_initial", c_int),
                 ("eot", c_int), ("no_speech", c_int), ("no_timestamps", c_int), ("timestamp_begin", c_int),
                 ("blank", c_int * 4), ("n_blank", c_int), ("suppress", POINTER(c_int)), ("n_suppress", c_int),
-                ("seed", c_uint64), ("max_candidates", c_int)]
+                ("seed", c_uint64), ("max_candidates", c_int),
+                ("no_repeat_ngram", c_int), ("repetition_penalty", c_float)]
 
 
 class WhVadOpts(ctypes.Structure):

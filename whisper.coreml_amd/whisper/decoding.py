@@ -57,6 +57,10 @@ class DecodingOptions:
     without_timestamps: bool = False
     max_initial_timestamp: Optional[float] = 1.0
     fp16: bool = True
+    # repetition controls of the device loop (not in the reference; include/whisper_hip.h,
+    # wh_decode_opts): over the sampled tokens of each row, ahead of the other logit filters
+    no_repeat_ngram_size: int = 0      # 0 = off, 1..16: no n-gram ending in a text token repeats
+    repetition_penalty: float = 1.0    # 1 (or 0) = off: x > 0 ? x / p : x * p for sampled text ids
 
 
 @dataclass(frozen=True)
@@ -101,6 +105,11 @@ class DecodingTask:
             raise ValueError("patience requires beam_size to be given")
         if o.length_penalty is not None and not (0 <= o.length_penalty <= 1):
             raise ValueError("length_penalty (alpha) should be a value between 0 and 1")
+        n, p = o.no_repeat_ngram_size, o.repetition_penalty
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not (0 <= n <= 16):
+            raise ValueError("no_repeat_ngram_size should be an integer between 0 and 16")
+        if not (p >= 0) or np.isinf(p):  # NaN fails the comparison
+            raise ValueError("repetition_penalty should be a finite value, not negative (1 = off)")
         return o
 
     def _text_ids(self, v) -> List[int]:
@@ -164,6 +173,8 @@ class DecodingTask:
         import ctypes
         w.suppress = self._sup.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
         w.n_suppress = len(sup)
+        w.no_repeat_ngram = int(o.no_repeat_ngram_size)
+        w.repetition_penalty = float(o.repetition_penalty)
         # the seed is part of the captured step graph: keep it constant for T = 0
         if w.temperature > 0:
             w.seed = next_seed() if seed is None else seed % (1 << 64)

@@ -150,7 +150,8 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     bounds the log-mel frames held on the device at a time.  ``skip_silence``: the speech
     spans of all files of a group come from one detector call after the group's ingest and
     become the files' clips; a file without speech takes no lane.  The other keywords are
-    transcribe()'s."""
+    transcribe()'s; the decoding options among them (``no_repeat_ngram_size`` and
+    ``repetition_penalty`` included) are one value for all files."""
     for k in ("schedule", "mel_max_reduce", "_mel_prepared"):
         if k in decode_options:
             raise TypeError(f"transcribe_batch() does not take {k!r}")

@@ -230,7 +230,10 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
     audio.py:155, so ranks all-reduce it before normalizing) and ``skip_silence``
     (True, or a dict of ``vad.DEFAULTS`` options): the speech spans of the resident
     waveform are found on the device (``vad.speech_spans``) and become the clips, so
-    only they are encoded and decoded; the result gains ``"speech_spans"`` in seconds."""
+    only they are encoded and decoded; the result gains ``"speech_spans"`` in seconds.
+    ``no_repeat_ngram_size`` and ``repetition_penalty`` are decoding options like the
+    others (``DecodingOptions``): they hold for every window and every rung of the
+    temperature ladder."""
     _check_fp16(model, decode_options.pop("fp16", True))
     ctx = model.ctx
     n_mels = model.dims.n_mels
