@@ -109,6 +109,38 @@ int wh_finalize(wh_ctx* ctx);
    Slaney formula librosa uses and checks it against the reference asset in tests) */
 int wh_set_mel_filters(wh_ctx* ctx, int n_mels, const float* filters);
 
+/* Phrase biasing (hotwords) of the device decode loop (wh_version >= 3).  A phrase table is
+   n_phrases phrases; phrase j has the token ids p_j = tokens[offsets[j] .. offsets[j+1]) (m_j of
+   them) and the boost b_j = boost[j]; the scalar `start` is shared by all phrases.
+   For every row and every update, with seq = tokens[sample_begin : len] (the sampled tokens
+   only, the seq of the repetition controls above: never the prompt, the SOT sequence or a
+   prefix), the pair (j, k), 0 <= k < m_j, fires when
+     k == 0: fl32(b_j * start) > 0; its bonus is fl32(b_j * start);
+     k >= 1: len(seq) >= k and seq[-k:] == p_j[:k]; its bonus is b_j.
+   Matching is on raw ids, so a timestamp token inside seq breaks a match.  Overlapping
+   matches all count: [a, a, b] after "... a a" fires k = 1 and k = 2.  For every id t = p_j[k]
+   named by at least one firing pair, x[t] = x[t] + B(t) in fp32, B(t) the largest bonus among
+   those pairs: a max, not a sum, so the result does not depend on evaluation order.  Nothing
+   is retracted when a phrase is abandoned.
+   Order at the head of the filter list: repetition penalty, phrase bias, n-gram ban, then
+   SuppressBlank, SuppressTokens and ApplyTimestampRules.  A banned or suppressed id stays at
+   -inf; eot and every id above it are never touched.  The log-probabilities the loop
+   accumulates and reports (sum_logprobs, and so avg_logprob) are those of the biased
+   distribution.
+   Limits: 1..128 phrases, 1..16 tokens each, at most 512 tokens in total, every id in
+   [0, n_vocab) and, at decode time, below eot; every b_j finite and > 0; start in [0, 1].
+   The table is context state, kept on the host: the next wh_decode_begin /
+   wh_decode_begin_slots uploads it, a decode in progress keeps the table it began with.
+   n_phrases == 0 clears the table (the pointers may then be null).  Every breach of the
+   limits is refused before any write (a negative code; wh_last_error names phrase_bias and
+   the offending phrase), and a refused call leaves the previous table in place.
+   With a non-empty table wh_decode_begin refuses (-11, phrase_bias in the message, the
+   decode state unchanged) a table id >= opts.eot, and a selection that would not run in the
+   sliced kernels, the rule of the repetition controls.  wh_prefill / wh_step hand out raw
+   logits and apply nothing. */
+int wh_set_phrase_bias(wh_ctx* ctx, int n_phrases, const int* tokens, const int* offsets /*[n_phrases+1]*/,
+                       const float* boost /*[n_phrases]*/, float start);
+
 /* log-mel of a whole file into the context's mel buffer: n_frames = (n + padding) / 160.
    normalize = 1 applies the global-max floor and scaling immediately. */
 int wh_log_mel(wh_ctx* ctx, const float* audio, int64_t n_samples, int64_t padding, int n_mels, int normalize,

@@ -651,6 +651,8 @@ __device__ __forceinline__ void lp_combine(const LPRec* rec, int r, const DecSta
 // the window lies in the sampled part, which also makes len - sb >= n).  LDS atomics, one
 // barrier more than the unfiltered kernel (the masks are cleared before it); step 3 reads
 // two bits per element.  The timestamp slice holds no text id: it skips all of it.
+// The same instantiations carry the phrase bias (PB below), behind the same two barriers;
+// which of penalty, bias and ban act is decided by kernel arguments at run time.
 template <int NS, int LP_EPT, bool MERGE = false, bool RF = false>
 __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __restrict__ logits, int ldl, DecState s,
                                                            DecOpts o, MergeEmbed em) {
@@ -692,11 +694,41 @@ __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __r
   __shared__ int rf_hist[RF ? LP_THREADS : 1];
   const bool rf = RF && j != NS - 1;  // one slice per workgroup: uniform
   const float pen = o.repetition_penalty;
+  // PB: the phrase table (DecOpts::bias, one record per thread).  Entry e fires when its id
+  // is a text id of this slice and either k = 0 with a positive bonus, or the last k sampled
+  // tokens equal the k record ids before it (the ids are staged in LDS); a firing entry sets
+  // its element's bit in `rf_pb` and its own bit in `pb_hit`.  Step 3, for an element whose
+  // bit is set, walks the set bits of pb_hit and adds the largest bonus of the entries that
+  // name it, after the penalty and before the ban.  The bonus of a matching entry is read
+  // from the table itself (its line was loaded above): an LDS copy of the bonuses or a
+  // (element, bonus) hit list would take the MERGE instantiations past 40 KB of LDS, from
+  // four resident workgroups per CU to three.
+  constexpr int PB_N = RF ? BIAS_MAX_ENTRIES : 1;
+  static_assert(BIAS_MAX_ENTRIES <= LP_THREADS, "one table entry per thread");
+  __shared__ unsigned rf_pb[RF_WORDS], pb_hit[(PB_N + 31) / 32];
+  __shared__ int pb_id[PB_N];
+  const int nb = RF ? min(o.n_bias, PB_N) : 0;  // a kernel argument: uniform
   if constexpr (RF) {
     if (rf) {
+      BiasRec pr = {-1, 0, 0.f, 0};
+      if (tid < nb) pr = o.bias[tid];
       rf_hist[tid] = hp;
       for (int k = tid; k < RF_WORDS; k += LP_THREADS) { rf_seen[k] = 0u; rf_ban[k] = 0u; }
+      if (nb > 0) {
+        for (int k = tid; k < RF_WORDS; k += LP_THREADS) rf_pb[k] = 0u;
+        if (tid < PB_N) pb_id[tid] = pr.id;
+        if (tid < (PB_N + 31) / 32) pb_hit[tid] = 0u;
+      }
       wh_lds_barrier();
+      if (tid < nb && pr.id >= lo && pr.id < hi && pr.id < o.eot && pr.k >= 0 && pr.k <= tid && pr.k <= len - sb) {
+        bool hit = pr.k > 0 || pr.bonus > 0.f;
+        for (int q = 1; q <= pr.k; ++q) hit &= rf_hist[len - q] == pb_id[tid - q];
+        if (hit) {
+          const int b = pr.id - lo;
+          __hip_atomic_fetch_or(&rf_pb[b >> 5], 1u << (b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_fetch_or(&pb_hit[tid >> 5], 1u << (tid & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
       if (tid >= sb && tid < len && hp >= lo && hp < hi && hp < o.eot) {
         const int b = hp - lo;
         if (pen != 1.f) __hip_atomic_fetch_or(&rf_seen[b >> 5], 1u << (b & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -768,6 +800,17 @@ __global__ __launch_bounds__(LP_THREADS) WH_LP_ATTR void k_logit_part(float* __r
           // the correctly rounded division (no reciprocal multiply: tokens are compared
           // with a host restatement), once per id
           xv[u] = xv[u] > 0.f ? xv[u] / pen : xv[u] * pen;
+          row[i] = xv[u];
+        }
+        if (nb > 0 && ((rf_pb[b >> 5] >> (b & 31)) & 1u)) {
+          // B(t): the largest bonus among the firing entries that name this id, one fp32 add
+          float bonus = 0.f;
+          for (int wd = 0; wd < (nb + 31) / 32; ++wd)
+            for (unsigned m = pb_hit[wd]; m; m &= m - 1) {
+              const int e = wd * 32 + __builtin_ctz(m);
+              if (pb_id[e] == i) bonus = fmaxf(bonus, o.bias[e].bonus);
+            }
+          xv[u] += bonus;
           row[i] = xv[u];
         }
         kill |= (rf_ban[b >> 5] >> (b & 31)) & 1u;
@@ -1053,7 +1096,7 @@ static bool select_rows(float* logits, int ldl, const DecState& s, const DecOpts
                         const MergeEmbed* em) {
   const int rows = nwin * s.G;
   const bool merge = em && s.lpw_cnt && s.G <= MG_MAXG;  // the window's merge in the selection launch
-  const bool rfo = repeat_filter_on(o);
+  const bool rfo = history_filter_on(o);
   const MergeEmbed none;
   const MergeEmbed& e = em ? *em : none;
 #define LP(NS_, EPT_)                                                                                                  \
@@ -1077,8 +1120,8 @@ static bool select_rows(float* logits, int ldl, const DecState& s, const DecOpts
   if (ns == 32) LP(32, 4);
   if (ns == 8) LP(8, 16);
 #undef LP
-  // the repetition filter has no single-workgroup form: wh_decode_begin refuses the options
-  // wherever logit_slices gives 0, so this launch never drops them
+  // the history filters (repetition controls, phrase bias) have no single-workgroup form:
+  // wh_decode_begin refuses them wherever logit_slices gives 0, so this launch never drops them
   k_logit_rows<<<nwin * s.G, LR_THREADS, 0, st>>>(logits, ldl, s, o), wh_launched("k_logit_rows");
   return false;
 }

@@ -128,6 +128,17 @@ struct DecState {
   int nw, G, ctx, hctx, maxc;
 };
 
+// One token of the phrase table: phrase token k of its phrase, so the k records before it
+// hold the prefix ids.  bonus is fl32(boost * start) at k = 0 and the boost elsewhere.
+struct BiasRec {
+  int id, k;
+  float bonus;
+  int pad;
+};
+constexpr int BIAS_MAX_ENTRIES = 512;  // one record per thread of k_logit_part's workgroup
+constexpr int BIAS_MAX_PHRASES = 128;
+constexpr int BIAS_MAX_LEN = 16;
+
 struct DecOpts {
   int V, eot, ts_begin, no_ts;       // vocabulary facts
   int blank[4], n_blank;             // SuppressBlank ids (tokenizer.encode(" ") + eot)
@@ -143,10 +154,18 @@ struct DecOpts {
   int no_repeat_ngram;               // 0 = off, 1..16: ban the text ids that would repeat an n-gram
   float repetition_penalty;          // 1 = off (set_opts stores 1 for 0): x > 0 ? x / p : x * p for
                                      // every text id sampled so far
+  // phrase bias (include/whisper_hip.h, wh_set_phrase_bias): after the penalty, before the ban.
+  // The table's contents are device memory, not part of this struct: a new table of the same
+  // size leaves the step graph's key (the bytes of DecOpts) as it was
+  int n_bias;                        // table entries (0 = off, <= BIAS_MAX_ENTRIES)
+  const BiasRec* bias;               // [n_bias] one record per phrase token, phrases back to back
 };
 inline bool repeat_filter_on(const DecOpts& o) {
   return o.no_repeat_ngram > 0 || (o.repetition_penalty != 1.f && o.repetition_penalty != 0.f);
 }
+// the history-filter instantiations of k_logit_part (RF) serve the repetition controls and
+// the phrase table alike
+inline bool history_filter_on(const DecOpts& o) { return repeat_filter_on(o) || o.n_bias > 0; }
 
 constexpr int LP_SLICES = 32;  // vocabulary slices per row: 31 text slices + [timestamp_begin, V)
 constexpr int LP_REC = 32;    // words per slice record

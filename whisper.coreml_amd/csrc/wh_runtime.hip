@@ -110,6 +110,10 @@ struct wh_ctx {
   double stats[WH_N_STATS] = {0};  // WH_STAT_*
   AudioFront audio;  // waveforms and the log-mel (csrc/wh_audio.h)
   int n_mels = 0;    // the model's
+  int n_vocab = 0;   // the model's
+  // the phrase table of wh_set_phrase_bias, kept on the host; the next wh_decode_begin
+  // uploads it (a decode in progress keeps the table it began with)
+  std::vector<wh::BiasRec> bias_tab;
   int maxc = 5;
   int maxc_stride = 1;
   int device = 0;
@@ -177,6 +181,7 @@ struct Ctx : public wh_ctx {
   }
   int* qk_map;  // [Ld][nh]
   unsigned* suppress;
+  BiasRec* bias_dev = nullptr;  // [BIAS_MAX_ENTRIES], allocated once: DecOpts::bias never changes
   DecState S;
   DecOpts O;
   int cur_nwin = 0, cur_G = 1;
@@ -235,6 +240,7 @@ struct Ctx : public wh_ctx {
     La = d.n_audio_layer;
     Ld = d.n_text_layer;
     V = d.n_vocab;
+    n_vocab = V;
     n_mels = d.n_mels;
     if (d.n_audio_state != ns || d.n_audio_head != nh) return fail(-2, "audio/text state or head mismatch unsupported");
     if (ns != nh * 64) return fail(-2, "head dim must be 64 (decoder.py:62-64)");
@@ -342,6 +348,7 @@ struct Ctx : public wh_ctx {
     addA((size_t)Wcap * nh * XS_NSP * XREC * 4); addA((size_t)Wcap * nh * 4);  // cross-attention segment records
     addA((size_t)8 * n * 4);  // k_proj1 path (<= 8 rows, wh_proj.h P1_RMAX): the second residual buffer
     addA((size_t)EKZ_TILES(n) * 65536); addA((size_t)EKZ_TILES(n) * 4 * 4);  // single-window encoder K halves
+    addA((size_t)BIAS_MAX_ENTRIES * sizeof(BiasRec));  // the phrase table, at its capacity
     HIPCHK(hipMalloc(&abase, ab));
     HIPCHK(hipMemset(abase, 0, ab));
     aa.base = (char*)abase;
@@ -380,7 +387,8 @@ struct Ctx : public wh_ctx {
     xs_rec = fa((size_t)Wcap * nh * XS_NSP * XREC); xs_cnt = ia((size_t)Wcap * nh);
     x2_d = fa((size_t)8 * n);
     ekz_slab = fa((size_t)EKZ_TILES(n) * 16384); ekz_cnt = ia((size_t)EKZ_TILES(n) * 4);  // zeroed with the arena
-    if (!fp_anc || !S.seed || !S.cand_idx || !S.lp_cnt || !S.lpw_cnt || !p1_cnt || !xs_cnt || !x2_d || !ekz_cnt)
+    bias_dev = (BiasRec*)aa.take((size_t)BIAS_MAX_ENTRIES * sizeof(BiasRec));
+    if (!bias_dev || !fp_anc || !S.seed || !S.cand_idx || !S.lp_cnt || !S.lpw_cnt || !p1_cnt || !xs_cnt || !x2_d || !ekz_cnt)
       return fail(-3, "activation arena overflow");
     S.nw = Wcap; S.G = 1; S.ctx = CTX; S.hctx = HCTX; S.maxc = 16;
     return audio.init(st, stats);
@@ -969,15 +977,32 @@ struct Ctx : public wh_ctx {
     if (!(o->repetition_penalty >= 0.f) || std::isinf(o->repetition_penalty))
       return fail(-11, "repetition_penalty must be finite and not negative (0 or 1: off)");
     const float pen = o->repetition_penalty == 0.f ? 1.f : o->repetition_penalty;
-    if (o->no_repeat_ngram > 0 || pen != 1.f) {
+    const bool rep_on = o->no_repeat_ngram > 0 || pen != 1.f;
+    if (rep_on || !bias_tab.empty()) {
+      // the history filters exist in the sliced selection only
       DecOpts q = DecOpts();
       q.V = V; q.ts_begin = o->timestamp_begin;
       if (!logit_slices(S, q, n_win))
-        return fail(-11, "no_repeat_ngram / repetition_penalty need the sliced selection (k_logit_part): "
-                         "not with this vocabulary or WHISPER_HIP_LOGIT_SPLIT=0");
+        return fail(-11, std::string(!rep_on ? "phrase_bias" : bias_tab.empty() ? "no_repeat_ngram / repetition_penalty"
+                                                                  : "no_repeat_ngram / repetition_penalty / phrase_bias") +
+                             " need the sliced selection (k_logit_part): not with this vocabulary or "
+                             "WHISPER_HIP_LOGIT_SPLIT=0");
+    }
+    if (!bias_tab.empty()) {
+      for (size_t e = 0; e < bias_tab.size(); ++e)
+        if (bias_tab[e].id >= o->eot) {
+          const int j = (int)std::count_if(bias_tab.begin(), bias_tab.begin() + e + 1, [](const BiasRec& r) { return r.k == 0; }) - 1;
+          return fail(-11, "phrase_bias: phrase " + std::to_string(j) + " names id " + std::to_string(bias_tab[e].id) +
+                               ", not a text id (eot " + std::to_string(o->eot) + ")");
+        }
     }
     O = DecOpts();
     O.no_repeat_ngram = o->no_repeat_ngram; O.repetition_penalty = pen;
+    // the table as it is now, for this decode; the pointer and the count are all DecOpts sees
+    O.n_bias = (int)bias_tab.size();
+    O.bias = O.n_bias ? bias_dev : nullptr;
+    if (O.n_bias)
+      HIPCHK(hipMemcpyAsync(bias_dev, bias_tab.data(), bias_tab.size() * sizeof(BiasRec), hipMemcpyHostToDevice, st));
     O.V = V; O.eot = o->eot; O.ts_begin = o->timestamp_begin; O.no_ts = o->no_timestamps;
     O.n_blank = std::min(o->n_blank, 3);
     for (int i = 0; i < O.n_blank; ++i) O.blank[i] = o->blank[i];
@@ -1742,7 +1767,8 @@ int create(int device, const wh_dims& dims, int max_windows, int max_group, wh_c
 extern "C" {
 
 const char* wh_last_error(void) { return wh_error().c_str(); }
-int wh_version(void) { return 2; }  // 2: wh_decode_opts.no_repeat_ngram / repetition_penalty
+// 2: wh_decode_opts.no_repeat_ngram / repetition_penalty, 3: wh_set_phrase_bias
+int wh_version(void) { return 3; }
 
 int wh_create(int device, const wh_dims* dims, int compute_dtype, int max_windows, int max_group, wh_ctx** out) {
   if (!dims || !out) return fail(-1, "null argument");
@@ -1788,6 +1814,39 @@ static int enter(wh_ctx* ctx, const char* entry) {
 int wh_set_mel_filters(wh_ctx* ctx, int n_mels, const float* filters) {
   if (!ctx || !filters) return fail(-1, "null argument");
   CTXCALL(ctx->audio.set_mel_filters(n_mels, filters));
+}
+int wh_set_phrase_bias(wh_ctx* ctx, int n_phrases, const int* tokens, const int* offsets, const float* boost,
+                       float start) {
+  if (!ctx) return fail(-1, "null context");
+  // host state only: no device call, so a decode in progress is not disturbed.  Every check
+  // comes before the first write: a refused call leaves the previous table in place
+  if (n_phrases == 0) { ctx->bias_tab.clear(); return 0; }
+  if (n_phrases < 0 || n_phrases > wh::BIAS_MAX_PHRASES)
+    return fail(-11, "phrase_bias: " + std::to_string(n_phrases) + " phrases (0.." + std::to_string(wh::BIAS_MAX_PHRASES) + ")");
+  if (!tokens || !offsets || !boost) return fail(-1, "phrase_bias: null argument with n_phrases > 0");
+  if (!(start >= 0.f && start <= 1.f)) return fail(-11, "phrase_bias: start must lie in [0, 1]");
+  if (offsets[0] != 0) return fail(-11, "phrase_bias: phrase 0: offsets must start at 0");
+  std::vector<wh::BiasRec> tab;
+  for (int j = 0; j < n_phrases; ++j) {
+    const std::string ph = "phrase_bias: phrase " + std::to_string(j);
+    // compared before subtracting: hostile offsets must not overflow
+    if (offsets[j + 1] <= offsets[j]) return fail(-11, ph + ": offsets must increase (1 to 16 tokens per phrase)");
+    if (offsets[j + 1] > offsets[j] + wh::BIAS_MAX_LEN)
+      return fail(-11, ph + " is longer than " + std::to_string(wh::BIAS_MAX_LEN) + " tokens");
+    if (offsets[j + 1] > wh::BIAS_MAX_ENTRIES)
+      return fail(-11, ph + ": more than " + std::to_string(wh::BIAS_MAX_ENTRIES) + " tokens in total");
+    if (!(boost[j] > 0.f) || std::isinf(boost[j])) return fail(-11, ph + ": boost must be finite and greater than 0");
+    for (int i = offsets[j]; i < offsets[j + 1]; ++i) {
+      if (tokens[i] < 0 || tokens[i] >= ctx->n_vocab)
+        return fail(-11, ph + ": id " + std::to_string(tokens[i]) + " outside the vocabulary [0, " +
+                             std::to_string(ctx->n_vocab) + ")");
+      const int k = i - offsets[j];
+      const float start_bonus = boost[j] * start;  // fl32(b * start): one fp32 multiply
+      tab.push_back({tokens[i], k, k == 0 ? start_bonus : boost[j], 0});
+    }
+  }
+  ctx->bias_tab.swap(tab);
+  return 0;
 }
 int wh_load_tensor(wh_ctx* ctx, const char* name, const float* data, const int64_t* shape, int ndim) {
   if (!name || !data || !shape) return fail(-1, "null argument");

@@ -72,6 +72,7 @@ _EXPORTS = {
     "wh_load_tensor": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
     "wh_finalize": (c_int, [c_void_p]),
     "wh_set_mel_filters": (c_int, [c_void_p, c_int, c_void_p]),
+    "wh_set_phrase_bias": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_float]),
     "wh_log_mel": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, POINTER(c_int64)]),
     "wh_log_mel_frames": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_int64, c_int,
                                   POINTER(c_int64)]),
@@ -276,6 +277,7 @@ class HipContext:
         self._check(self.lib.wh_create(device, ctypes.byref(d), code, max_windows, max_group, ctypes.byref(h)),
                     "wh_create")
         self.h = h
+        self.phrase_bias = None  # what set_phrase_bias installed: (phrases, boosts, start)
 
     # -- errors
     def _check(self, rc: int, what: str):
@@ -317,6 +319,28 @@ class HipContext:
         f = np.ascontiguousarray(filters, dtype=np.float32)
         assert f.shape == (n_mels, 201)
         self._check(self.lib.wh_set_mel_filters(self.h, n_mels, _ptr(f)), "wh_set_mel_filters")
+
+    def set_phrase_bias(self, phrases: Optional[Sequence[Sequence[int]]] = None,
+                        boosts: Optional[Sequence[float]] = None, start: float = 0.5):
+        """Install the phrase table of the device decode loop (wh_set_phrase_bias,
+        include/whisper_hip.h): ``phrases[j]`` are token ids, ``boosts[j]`` its boost, ``start``
+        the share of a boost the first token gets.  No phrases: the table is cleared.  The next
+        ``decode_begin`` uploads it; the library checks the limits and a refused call
+        (HipBackendError) leaves the previous table, and ``self.phrase_bias``, as they were."""
+        ph = tuple(tuple(int(t) for t in p) for p in (phrases or ()))
+        if not ph:
+            self._check(self.lib.wh_set_phrase_bias(self.h, 0, None, None, None, 0.0), "wh_set_phrase_bias")
+            self.phrase_bias = None
+            return
+        bo = tuple(float(b) for b in boosts)
+        if len(bo) != len(ph):
+            raise ValueError("set_phrase_bias: one boost per phrase")
+        tok = np.asarray([t for p in ph for t in p] or [0], dtype=np.int32)
+        off = np.cumsum([0] + [len(p) for p in ph]).astype(np.int32)
+        b = np.asarray(bo, dtype=np.float32)
+        self._check(self.lib.wh_set_phrase_bias(self.h, len(ph), _ptr(tok), _ptr(off), _ptr(b), float(start)),
+                    "wh_set_phrase_bias")
+        self.phrase_bias = (ph, bo, float(start))
 
     # -- mel
     def log_mel(self, audio: np.ndarray, n_mels: int, padding: int = 0, normalize: bool = True) -> int:

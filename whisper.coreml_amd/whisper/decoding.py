@@ -61,6 +61,67 @@ class DecodingOptions:
     # wh_decode_opts): over the sampled tokens of each row, ahead of the other logit filters
     no_repeat_ngram_size: int = 0      # 0 = off, 1..16: no n-gram ending in a text token repeats
     repetition_penalty: float = 1.0    # 1 (or 0) = off: x > 0 ? x / p : x * p for sampled text ids
+    # phrase biasing of the device loop (not in the reference; include/whisper_hip.h,
+    # wh_set_phrase_bias): each phrase is text (encoded as " " + text.strip(), the form text
+    # takes after a timestamp; list other casings yourself) or token ids.  A phrase's first
+    # token gets hotword_start * boost added to its logit at every step, and the token that
+    # continues a phrase begun in the sampled tokens gets the whole boost.  hotword_boost has no
+    # default: one value, or one per phrase.  avg_logprob is that of the biased distribution.
+    hotwords: Optional[Sequence[Union[str, Sequence[int]]]] = None
+    hotword_boost: Union[None, float, Sequence[float]] = None
+    hotword_start: float = 0.5
+
+
+HOTWORD_MAX_PHRASES, HOTWORD_MAX_LEN, HOTWORD_MAX_TOKENS = 128, 16, 512  # wh_set_phrase_bias's limits
+
+
+def _check_hotword_options(o: DecodingOptions):
+    """What can be checked of the hotword options without a tokenizer; the boosts, one per
+    phrase, or None without hotwords."""
+    if o.hotwords is None or (not isinstance(o.hotwords, str) and len(o.hotwords) == 0):
+        return None
+    if isinstance(o.hotwords, str):
+        raise ValueError("hotwords should be a sequence of phrases, not one string")
+    n = len(o.hotwords)
+    if n > HOTWORD_MAX_PHRASES:
+        raise ValueError(f"hotwords: {n} phrases, at most {HOTWORD_MAX_PHRASES}")
+    b = o.hotword_boost
+    if b is None:
+        raise ValueError("hotword_boost is required with hotwords (one value, or one per phrase): there is no default")
+    boosts = [float(b)] * n if isinstance(b, (int, float, np.integer, np.floating)) else [float(x) for x in b]
+    if len(boosts) != n:
+        raise ValueError(f"hotword_boost: {len(boosts)} values for {n} hotwords")
+    for j, x in enumerate(boosts):
+        if not (x > 0) or np.isinf(x):  # NaN fails the comparison
+            raise ValueError(f"hotword_boost of phrase {j} should be finite and greater than 0")
+    if not (0 <= float(o.hotword_start) <= 1):
+        raise ValueError("hotword_start should be a value between 0 and 1")
+    return boosts
+
+
+def resolve_hotwords(o: DecodingOptions, tokenizer: Tokenizer):
+    """The phrase table of ``o``: None without hotwords, else (phrases as tuples of ids,
+    boosts, start), checked against the limits of wh_set_phrase_bias."""
+    boosts = _check_hotword_options(o)
+    if boosts is None:
+        return None
+    phrases, total = [], 0
+    for j, h in enumerate(o.hotwords):
+        if isinstance(h, str):
+            if not h.strip():
+                raise ValueError(f"hotwords[{j}] is empty")
+            ids = tokenizer.encode(" " + h.strip())
+        else:
+            ids = [int(t) for t in h]
+        if not (1 <= len(ids) <= HOTWORD_MAX_LEN):
+            raise ValueError(f"hotwords[{j}] ({h!r}) is {len(ids)} tokens long, it should be 1 to {HOTWORD_MAX_LEN}")
+        if any(t < 0 or t >= tokenizer.eot for t in ids):
+            raise ValueError(f"hotwords[{j}] ({h!r}) names an id that is not a text token (0 <= id < {tokenizer.eot})")
+        total += len(ids)
+        phrases.append(tuple(ids))
+    if total > HOTWORD_MAX_TOKENS:
+        raise ValueError(f"hotwords: {total} tokens in total, at most {HOTWORD_MAX_TOKENS}")
+    return tuple(phrases), tuple(boosts), float(o.hotword_start)
 
 
 @dataclass(frozen=True)
@@ -85,6 +146,7 @@ class DecodingTask:
         self.tokenizer: Tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages,
                                                   language=language, task=options.task)
         self.options = self._verify_options(options)
+        self.phrase_bias = resolve_hotwords(options, self.tokenizer)  # None, or (phrases, boosts, start)
         self.n_group = options.beam_size or options.best_of or 1
         self.n_ctx = model.dims.n_text_ctx
         self.sample_len = options.sample_len or model.dims.n_text_ctx // 2
@@ -110,6 +172,7 @@ class DecodingTask:
             raise ValueError("no_repeat_ngram_size should be an integer between 0 and 16")
         if not (p >= 0) or np.isinf(p):  # NaN fails the comparison
             raise ValueError("repetition_penalty should be a finite value, not negative (1 = off)")
+        _check_hotword_options(o)  # the token limits: resolve_hotwords, once the text is encoded
         return o
 
     def _text_ids(self, v) -> List[int]:
@@ -226,7 +289,18 @@ def run_windows(model: "Whisper", options: DecodingOptions, prompts: Sequence[Op
     t0 = tasks[0]
     opts = t0.wh_opts(seed)
     ctx = model.ctx
-    ctx.decode_begin(opts, [t.initial_tokens for t in tasks], [t.sot_index for t in tasks], slots=slots)
+    # the phrase table is context state that decode_begin uploads: install this call's (one
+    # table for all windows), or clear what an earlier caller left, and leave none behind, so
+    # nothing leaks into the next decode, whoever begins it
+    if t0.phrase_bias is not None:
+        ctx.set_phrase_bias(*t0.phrase_bias)
+    elif ctx.phrase_bias is not None:
+        ctx.set_phrase_bias(None)
+    try:
+        ctx.decode_begin(opts, [t.initial_tokens for t in tasks], [t.sot_index for t in tasks], slots=slots)
+    finally:
+        if ctx.phrase_bias is not None:
+            ctx.set_phrase_bias(None)
     # every window stops on the device (completion, n_ctx or sample_len updates);
     # decode_steps returns once all of them are done
     ctx.decode_steps(t0.sample_len)

@@ -151,7 +151,8 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     spans of all files of a group come from one detector call after the group's ingest and
     become the files' clips; a file without speech takes no lane.  The other keywords are
     transcribe()'s; the decoding options among them (``no_repeat_ngram_size`` and
-    ``repetition_penalty`` included) are one value for all files."""
+    ``repetition_penalty`` included) are one value for all files, and ``hotwords`` with
+    ``hotword_boost`` / ``hotword_start`` are one phrase table for all files."""
     for k in ("schedule", "mel_max_reduce", "_mel_prepared"):
         if k in decode_options:
             raise TypeError(f"transcribe_batch() does not take {k!r}")

@@ -233,7 +233,10 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
     only they are encoded and decoded; the result gains ``"speech_spans"`` in seconds.
     ``no_repeat_ngram_size`` and ``repetition_penalty`` are decoding options like the
     others (``DecodingOptions``): they hold for every window and every rung of the
-    temperature ladder."""
+    temperature ladder.  So do ``hotwords``, ``hotword_boost`` and ``hotword_start`` (phrase
+    biasing): the table is installed for every window, also with ``skip_silence`` and
+    ``condition_on_previous_text=False``; ``avg_logprob`` is then that of the biased
+    distribution, which the ``logprob_threshold`` fallback compares."""
     _check_fp16(model, decode_options.pop("fp16", True))
     ctx = model.ctx
     n_mels = model.dims.n_mels
