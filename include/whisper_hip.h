@@ -468,6 +468,42 @@ const char* wh_wav_last_error(void);
 int wh_wav_ingest(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int down, const double* taps,
                   int n_taps, int64_t dst_offset, int64_t reserve, int64_t* n_out);
 
+/* ---- Channels as files: the three ingest calls with the channels kept apart, for recordings
+   that hold one party per channel.  select[0 .. n_select) are distinct channel ids of the file;
+   on success n_select resident segments are appended at dst_offset, each *n_out samples long,
+   segment s holding channel select[s] (selection order), lying back to back: segment s starts
+   at dst_offset + s * *n_out.  There is no mix.  For selected channel c, in fp64,
+     x_c[m] = sample(m, c) * 2^-(bits-1)            integer encodings (exact)
+     x_c[m] = float_sample(sample(m, c))            F32 / F64 (non-finite -> 0, clamp to +-256)
+   frames outside [0, n_frames) are zeros, and from x_c[m] on y[k] and out[k] are
+   wh_audio_ingest's.  This is what the non-split call computes for a mono file that holds only
+   that channel, bit for bit; whisper/audio.py load_audio_channels restates it on the host.
+   The dst_offset rule is wh_audio_ingest's (0, or the end of the last segment); reserve is the
+   total the caller will hold.  wh_log_mel(ctx, NULL, n, ...) works afterwards only if exactly one
+   segment is resident (n_select == 1 at dst_offset 0); wh_log_mel_batch(ctx, NULL, ...) and
+   wh_speech_spans take the segments as their files.
+   One upload and one resampling launch whatever n_select is (k_pcm_resample_split,
+   csrc/wh_ingest.hip).  wh_flac_ingest_split decodes on the device exactly as wh_flac_ingest
+   does and differs only in that launch; on the host path it calls wh_flac_decode and
+   wh_audio_ingest_split.  *path_out = 0 device, 1 host, as for wh_flac_ingest.
+   Refused before the first HIP call, wh_last_error naming the field, the resident segments and
+   the mel left as they were: everything the non-split call refuses; a null select; n_select < 1
+   or > channels; an id outside [0, channels); a repeated id; WH_PCM_F32 (a mono waveform has
+   nothing to split).
+   Counters: the PCM and WAV forms move WH_STAT_INGEST_COPY_MS and WH_STAT_INGEST_KERNEL_MS, the
+   FLAC device path its own (WH_STAT_FLAC_*, the launch in WH_STAT_FLAC_RESAMPLE_MS).
+   wh_version() does not change with these three: a caller detects them by the presence of the
+   symbols. */
+int wh_audio_ingest_split(wh_ctx* ctx, const void* pcm, int format, int64_t n_frames, int channels, int bits,
+                          int up, int down, const double* taps, int n_taps, const int* select, int n_select,
+                          int64_t dst_offset, int64_t reserve, int64_t* n_out);
+int wh_flac_ingest_split(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int down, const double* taps,
+                         int n_taps, const int* select, int n_select, int64_t dst_offset, int64_t reserve,
+                         int64_t* n_out, int* path_out);
+int wh_wav_ingest_split(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int down, const double* taps,
+                        int n_taps, const int* select, int n_select, int64_t dst_offset, int64_t reserve,
+                        int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,14 @@ struct AudioFront {
                   int64_t reserve, int64_t* n_out, int* path);
   int wav_ingest(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps, int64_t dst,
                  int64_t reserve, int64_t* n_out);
+  // the same three with the channels kept apart: n_select segments, one per select[s]
+  int audio_ingest_split(const void* pcm, int format, int64_t n, int channels, int bits, int up, int down,
+                         const double* taps, int n_taps, const int* select, int n_select, int64_t dst,
+                         int64_t reserve, int64_t* n_out);
+  int flac_ingest_split(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps,
+                        const int* select, int n_select, int64_t dst, int64_t reserve, int64_t* n_out, int* path);
+  int wav_ingest_split(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps,
+                       const int* select, int n_select, int64_t dst, int64_t reserve, int64_t* n_out);
   // audio == nullptr: use the resident buffer of wh_audio_upload (n must match)
   int log_mel(const float* audio, int64_t n, int64_t pad, int n_mels, int normalize, int64_t* nf) {
     return log_mel_frames(audio, n, pad, n_mels, 0, -1, normalize, nf);
@@ -106,7 +114,8 @@ struct AudioFront {
                    const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out);
   int ingest_run(const std::string& who, const void* pcm, int format, int64_t n, int channels, int bits, int up,
                  int down, const double* taps, int n_taps, int64_t dst, int64_t reserve, int64_t* n_out,
-                 int wav_encoding = -1, int frame_bytes = 0);
+                 int wav_encoding = -1, int frame_bytes = 0, const int* select = nullptr, int n_select = 0);
+  int select_check(const std::string& who, int format, int channels, const int* select, int n_select);
   int flac_device(const uint8_t* data, int64_t n, const whflac::Plan& plan, bool s32, bool* ran);
   int flac_plan_timed(const uint8_t* data, int64_t n, whflac::Plan* plan);
 };

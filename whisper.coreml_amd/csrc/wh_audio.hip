@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstring>
 
+#include "wh_select.h"
 #include "whisper_hip.h"
 
 using namespace wh;
@@ -110,11 +111,14 @@ int AudioFront::ingest_check(const std::string& who, int format, int64_t n, int 
 // pcm: the host PCM to upload, or null when the device PCM buffer (d_pcm) already holds it
 // (wh_flac_ingest's device path; its resampling time goes to WH_STAT_FLAC_RESAMPLE_MS).
 // wav_encoding >= 0 (wh_wav_ingest): pcm is a WAV data chunk in that WH_WAV_* encoding,
-// frame_bytes per frame; otherwise the encoding is the format's, int16 or int32
+// frame_bytes per frame; otherwise the encoding is the format's, int16 or int32.
+// select (the _split forms, never WH_PCM_F32): the n_select channels go to segments of their
+// own, back to back from dst, by one launch of the split kernel instead of the mixing one
 int AudioFront::ingest_run(const std::string& who, const void* pcm, int format, int64_t n, int channels, int bits,
                            int up, int down, const double* taps, int n_taps, int64_t dst, int64_t reserve,
-                           int64_t* n_out, int wav_encoding, int frame_bytes) {
+                           int64_t* n_out, int wav_encoding, int frame_bytes, const int* select, int n_select) {
   const bool f32 = format == WH_PCM_F32;
+  const int n_seg = select ? n_select : 1;  // the split forms: one segment per selected channel
   const int encoding = wav_encoding >= 0 ? wav_encoding : format == WH_PCM_S32 ? WH_WAV_S32 : WH_WAV_S16;
   if (wav_encoding < 0) frame_bytes = channels * (format == WH_PCM_S32 ? 4 : 2);
   const bool filt = !f32 && up != down;
@@ -135,7 +139,7 @@ int AudioFront::ingest_run(const std::string& who, const void* pcm, int format, 
     }
   }
   // room for the new end (or the caller's reserve); the segments before dst survive a move
-  TRY(d_audio.reserve(std::max<size_t>(std::max(dst + no, reserve), 16000) * 4, (size_t)dst * 4, st));
+  TRY(d_audio.reserve(std::max<size_t>(std::max(dst + n_seg * no, reserve), 16000) * 4, (size_t)dst * 4, st));
   if (f32) {
     TRY(tm.mark(0, st));
     HIPCHK(hipMemcpyAsync(d_audio.p + dst, pcm, (size_t)n * 4, hipMemcpyHostToDevice, st));
@@ -146,7 +150,8 @@ int AudioFront::ingest_run(const std::string& who, const void* pcm, int format, 
     TRY(tm.mark(0, st));
     if (pcm) HIPCHK(hipMemcpyAsync(d_pcm.p, pcm, bytes, hipMemcpyHostToDevice, st));
     TRY(tm.mark(1, st));
-    launch_pcm_resample(d_pcm.p, encoding, n, channels, bits, up, down, dt, d_audio.p + dst, no, st);
+    if (select) launch_pcm_resample_split(d_pcm.p, encoding, n, channels, bits, up, down, dt, select, n_select, d_audio.p + dst, no, st);
+    else launch_pcm_resample(d_pcm.p, encoding, n, channels, bits, up, down, dt, d_audio.p + dst, no, st);
     TRY(tm.mark(2, st));
     HIPCHK(hipStreamSynchronize(st));
     TRY(launch_status("audio_ingest"));
@@ -154,7 +159,7 @@ int AudioFront::ingest_run(const std::string& who, const void* pcm, int format, 
     TRY(tm.charge(1, stats[pcm ? WH_STAT_INGEST_KERNEL_MS : WH_STAT_FLAC_RESAMPLE_MS]));
   }
   if (dst == 0) audio_segs.clear();
-  audio_segs.emplace_back(dst, no);
+  for (int s = 0; s < n_seg; ++s) audio_segs.emplace_back(dst + s * no, no);
   audio_n = audio_segs.size() == 1 ? no : -1;
   *n_out = no;
   return 0;
@@ -292,6 +297,76 @@ int AudioFront::wav_ingest(const uint8_t* data, int64_t n, int up, int down, con
   TRY(ingest_check(who, WH_PCM_S32, f.n_frames, f.channels, 32, up, down, taps, n_taps, dst, reserve, n_out));
   return ingest_run(who, data + f.data_offset, WH_PCM_S32, f.n_frames, f.channels, bits[f.encoding], up, down, taps,
                     n_taps, dst, reserve, n_out, f.encoding, container[f.encoding] * f.channels);
+}
+// ------------------------------------------------------------ channels apart
+// (include/whisper_hip.h).  The non-split call's checks, then the selection's, all before the
+// first HIP call; then the same upload and one launch of the split kernel.
+int AudioFront::select_check(const std::string& who, int format, int channels, const int* select, int n_select) {
+  if (format == WH_PCM_F32)
+    return fail(-7, who + "format WH_PCM_F32 is a mono waveform: there are no channels to split");
+  const std::string why = select_error(channels, select, n_select);
+  return why.empty() ? 0 : fail(why == "null select" ? -1 : -7, who + why);
+}
+int AudioFront::audio_ingest_split(const void* pcm, int format, int64_t n, int channels, int bits, int up, int down,
+                                   const double* taps, int n_taps, const int* select, int n_select, int64_t dst,
+                                   int64_t reserve, int64_t* n_out) {
+  const std::string who = "audio_ingest_split: ";
+  if (!pcm) return fail(-1, who + "null pcm");
+  TRY(ingest_check(who, format, n, channels, bits, up, down, taps, n_taps, dst, reserve, n_out));
+  TRY(select_check(who, format, channels, select, n_select));
+  return ingest_run(who, pcm, format, n, channels, bits, up, down, taps, n_taps, dst, reserve, n_out, -1, 0, select,
+                    n_select);
+}
+int AudioFront::flac_ingest_split(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps,
+                                  const int* select, int n_select, int64_t dst, int64_t reserve, int64_t* n_out,
+                                  int* path) {
+  const std::string who = "flac_ingest_split: ";
+  if (!data) return fail(-1, who + "null data");
+  if (!path) return fail(-1, who + "null path_out");
+  whflac::Plan plan;
+  const int rc = flac_plan_timed(data, n, &plan);
+  if (rc < 0) return rc;
+  const whflac::Info& si = plan.si;
+  const int format = si.bps <= 16 ? WH_PCM_S16 : WH_PCM_S32;
+  // the selection is checked here on both paths: the host decoder below is not run for a call
+  // that will be refused
+  TRY(select_check(who, format, si.channels, select, n_select));
+  if (rc == 0) {
+    TRY(ingest_check(who, format, si.total, si.channels, si.bps, up, down, taps, n_taps, dst, reserve, n_out));
+    bool ran = false;
+    TRY(flac_device(data, n, plan, format == WH_PCM_S32, &ran));
+    if (ran) {
+      *path = 0;
+      return ingest_run(who, nullptr, format, si.total, si.channels, si.bps, up, down, taps, n_taps, dst, reserve,
+                        n_out, -1, 0, select, n_select);
+    }
+  }
+  *path = 1;
+  const int64_t cap = si.total > 0 ? si.total : n * 8;
+  std::vector<int32_t> pcm((size_t)cap * si.channels);
+  int64_t got = 0;
+  const int hrc = wh_flac_decode(data, n, pcm.data(), cap, &got);
+  if (hrc) return fail(hrc, wh_flac_last_error());
+  if (format == WH_PCM_S32)
+    return audio_ingest_split(pcm.data(), format, got, si.channels, si.bps, up, down, taps, n_taps, select, n_select,
+                              dst, reserve, n_out);
+  std::vector<int16_t> pcm16(pcm.begin(), pcm.begin() + (size_t)got * si.channels);
+  return audio_ingest_split(pcm16.data(), format, got, si.channels, si.bps, up, down, taps, n_taps, select, n_select,
+                            dst, reserve, n_out);
+}
+int AudioFront::wav_ingest_split(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps,
+                                 const int* select, int n_select, int64_t dst, int64_t reserve, int64_t* n_out) {
+  const std::string who = "wav_ingest_split: ";
+  if (!data) return fail(-1, who + "null data");
+  wh_wav_fmt f;
+  if (wh_wav_info(data, n, &f) != 0) return fail(-7, who + wh_wav_last_error());
+  //                         U8 S16 S24 S32 F32 F64 ALAW ULAW
+  static const int container[8] = {1, 2, 3, 4, 4, 8, 1, 1};
+  static const int bits[8] = {8, 16, 24, 32, 1, 1, 16, 16};  // as in wav_ingest
+  TRY(ingest_check(who, WH_PCM_S32, f.n_frames, f.channels, 32, up, down, taps, n_taps, dst, reserve, n_out));
+  TRY(select_check(who, WH_PCM_S32, f.channels, select, n_select));
+  return ingest_run(who, data + f.data_offset, WH_PCM_S32, f.n_frames, f.channels, bits[f.encoding], up, down, taps,
+                    n_taps, dst, reserve, n_out, f.encoding, container[f.encoding] * f.channels, select, n_select);
 }
 int AudioFront::audio_read(float* out, int64_t offset, int64_t n) {
   if (!out) return fail(-1, "audio_read: null out");

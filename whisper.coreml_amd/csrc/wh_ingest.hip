@@ -1,4 +1,5 @@
-// PCM ingest kernel of libwhisper_hip (wh_audio_ingest, wh_flac_ingest, wh_wav_ingest).  A
+// PCM ingest kernels of libwhisper_hip (wh_audio_ingest, wh_flac_ingest, wh_wav_ingest and their
+// _split forms, which keep the channels apart).  A
 // translation unit of its own: the code object of wh_kernels.hip, whose kernels run in every
 // decoder step, stays as it is.
 #include "wh_kernels.h"
@@ -185,6 +186,205 @@ void launch_pcm_resample(const void* pcm, int encoding, int64_t n_frames, int ch
   else LAUNCH_RESAMPLE(0);
 #undef LAUNCH_RESAMPLE
 #undef LAUNCH_RESAMPLE_AS
+}
+
+// ---------------------------------------------------------------- PCM ingest, channels apart
+// The sibling of k_pcm_resample for wh_*_ingest_split: no mix, selected channel s (the file's
+// channel select[s]) becomes a waveform of its own at out + s * n_out.  Its input is that
+// channel alone,
+//   x_c[m] = sample(m, c) * 2^-(bits-1)      (integers: exact;  floats: float_sample, scale 1)
+// zero outside [0, n), and from x_c[m] on the arithmetic is k_pcm_resample's: the same tap
+// walk with fma in the same order, rint, clip, /32768.  pcm_frame of a one-channel file is
+// sample * scale / 1.0, so by construction channel c here equals what k_pcm_resample computes
+// for a mono file that holds only that channel (tests/test_gpu_channel_split.py pins it).
+//
+// A workgroup (blockIdx.x, blockIdx.y) owns `block` consecutive outputs of a group of up to
+// `group` selected channels, select[blockIdx.y * group ...].  It stages the span of frames
+// once: element i of the walk is (frame i / G, selected channel i % G), so with all channels
+// selected neighbouring threads read neighbouring samples of the interleaved bytes, and a
+// sparse selection reads only its own samples; every byte is read once per workgroup, not once
+// per channel.  Each channel has a plane of span_cap doubles in LDS (plane g at g * span_cap),
+// which keeps a thread's tap walk stride-1 as in k_pcm_resample; the taps lie behind the last
+// plane in MODE 2.  Then the block x G outputs: a thread walks the taps of its phase once for
+// up to 4 channels, one accumulator each (two launches with one channel each were measured
+// faster than one launch that walked the taps per channel: DESIGN.md).  MODE 0 stages nothing:
+// ratios whose span does not fit, and the no-filter case, which is a de-interleave and
+// quantise.
+struct SplitArgs {
+  const void* pcm;
+  int64_t n, n_out;
+  int channels, up, down, half, block, span_cap, n_select, group;
+  double scale;
+  const double* taps;
+  float* out;
+  uint8_t select[256];  // channel ids (channels <= 256)
+};
+
+template <typename R>
+__device__ inline double pcm_channel(const uint8_t* __restrict__ pcm, int64_t m, int64_t n, int channels, int c,
+                                     double scale) {
+  if (m < 0 || m >= n) return 0.0;
+  return (double)R::at(pcm, m * channels + c) * scale;
+}
+
+// what the output phase of a workgroup needs for NG of its channels: their planes start at
+// `planes` (span_cap doubles apart), their outputs at `out` (n_out apart)
+struct SplitWalk {
+  const uint8_t* __restrict__ pcm;
+  int64_t n, n_out;
+  int channels, up, down, half;
+  double scale;
+  const double* taps;      // global
+  const double* taps_lds;  // MODE 2
+  const double* planes;
+  int span_cap;
+  int64_t m_lo, k0, k1;
+  int ch[4];  // the channels' ids
+  float* out;
+};
+
+// outputs [k0, k1) of NG channels.  Per channel this is k_pcm_resample's walk: the same taps in
+// the same order into an accumulator of its own
+template <typename R, int MODE, int NG>
+__device__ inline void split_outputs(const SplitWalk& w) {
+  constexpr bool STAGED = MODE != 0;
+  const int last_tap = 2 * w.half;
+  for (int64_t k = w.k0 + threadIdx.x; k < w.k1; k += 256) {
+    double y[NG];
+    if (!w.taps) {
+#pragma unroll
+      for (int j = 0; j < NG; ++j) y[j] = pcm_channel<R>(w.pcm, k, w.n, w.channels, w.ch[j], w.scale);
+    } else {
+      const int64_t c = k * w.down + w.half;
+      int64_t m = c / w.up;         // the newest frame that reaches output k
+      int t = (int)(c - m * w.up);  // and its tap: the thread's phase
+#pragma unroll
+      for (int j = 0; j < NG; ++j) y[j] = 0.0;
+      int i = (int)(m - w.m_lo);  // the frame's place in the planes
+      for (; t <= last_tap; t += w.up, --m, --i) {
+        const double tap = MODE == 2 ? w.taps_lds[t] : w.taps[t];
+#pragma unroll
+        for (int j = 0; j < NG; ++j) {
+          const double x = STAGED ? w.planes[j * w.span_cap + i]
+                                  : pcm_channel<R>(w.pcm, m, w.n, w.channels, w.ch[j], w.scale);
+          y[j] = fma(x, tap, y[j]);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+      double r = rint(y[j] * 32768.0);  // round half to even, as np.round
+      r = fmin(fmax(r, -32768.0), 32767.0);
+      w.out[(int64_t)j * w.n_out + k] = (float)r * (1.0f / 32768.0f);
+    }
+  }
+}
+
+template <typename R, int MODE>
+__global__ __launch_bounds__(256) void k_pcm_resample_split(SplitArgs a) {
+  extern __shared__ __align__(16) double pcm_planes[];
+  const uint8_t* __restrict__ pcm = (const uint8_t*)a.pcm;
+  const int64_t k0 = (int64_t)blockIdx.x * a.block;
+  const int64_t k1 = k0 + a.block < a.n_out ? k0 + a.block : a.n_out;
+  const int s0 = blockIdx.y * a.group;
+  const int G = a.n_select - s0 < a.group ? a.n_select - s0 : a.group;
+  if (k0 >= k1 || G < 1) return;
+  const int last_tap = 2 * a.half;
+  int64_t m_lo = 0;
+  constexpr bool STAGED = MODE != 0;
+  const double* taps_lds = pcm_planes + (size_t)a.group * a.span_cap;
+  if (STAGED) {
+    const int64_t m_hi = ((k1 - 1) * a.down + a.half) / a.up;
+    m_lo = (k0 * a.down + a.half) / a.up - last_tap / a.up;
+    const int64_t len = m_hi - m_lo + 1;
+    if (len > a.span_cap) return;  // cannot happen for the block the launcher chose
+    const int total = (int)len * G;  // group * span_cap doubles fit the LDS budget
+    for (int i = threadIdx.x; i < total; i += 256) {
+      const int f = i / G, g = i - f * G;
+      pcm_planes[g * a.span_cap + f] = pcm_channel<R>(pcm, m_lo + f, a.n, a.channels, a.select[s0 + g], a.scale);
+    }
+    if (MODE == 2)
+      for (int i = threadIdx.x; i <= last_tap; i += 256) pcm_planes[(size_t)a.group * a.span_cap + i] = a.taps[i];
+    __syncthreads();
+  }
+  // up to 4 channels share one tap walk: a tap is loaded once for all of them and their fma
+  // chains are independent
+  for (int g = 0; g < G; g += 4) {
+    const int ng = G - g < 4 ? G - g : 4;
+    SplitWalk w{pcm, a.n, a.n_out, a.channels, a.up, a.down, a.half, a.scale, a.taps, taps_lds,
+                pcm_planes + g * a.span_cap, a.span_cap, m_lo, k0, k1, {0, 0, 0, 0},
+                a.out + (int64_t)(s0 + g) * a.n_out};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w.ch[j] = j < ng ? a.select[s0 + g + j] : 0;
+    if (ng == 1) split_outputs<R, MODE, 1>(w);
+    else if (ng == 2) split_outputs<R, MODE, 2>(w);
+    else if (ng == 3) split_outputs<R, MODE, 3>(w);
+    else split_outputs<R, MODE, 4>(w);
+  }
+}
+
+// block and group: the largest block (1024, 512, 256) at which the planes of all selected
+// channels fit 20 KiB, one group then; failing that the largest at which they fit the 64 KiB of
+// k_pcm_resample's launcher; if not even 256 does, block 256 and the fewest groups whose planes
+// fit 64 KiB, of equal size (gridDim.y of them).  20 KiB first: a CU's 160 KiB then hold the 8
+// workgroups its wave slots allow, and the tap walk is bound by latency: on 600 s of 44.1 kHz
+// stereo, blocks of 256 (12 KiB of planes) ran in 0.62 ms, 512 (23 KiB) in 0.68 and 1024
+// (46 KiB) in 0.85.  Where the planes are small anyway (8 kHz) the largest block
+// stays the fastest.  The taps go behind the planes when they still fit 64 KiB.  No block at
+// which one plane fits, or no filter: unstaged, block 1024 and up to 4 channels (one tap walk)
+// per group.
+void launch_pcm_resample_split(const void* pcm, int encoding, int64_t n_frames, int channels, int bits, int up,
+                               int down, const double* taps, const int* select, int n_select, float* out,
+                               int64_t n_out, hipStream_t st) {
+  if (n_out < 1 || n_select < 1 || n_select > 256) return;
+  SplitArgs a;
+  a.pcm = pcm; a.n = n_frames; a.n_out = n_out; a.channels = channels; a.up = up; a.down = down;
+  a.half = taps ? 10 * (up > down ? up : down) : 0;
+  a.scale = ldexp(1.0, -(bits - 1));
+  a.taps = taps; a.out = out; a.n_select = n_select;
+  for (int s = 0; s < 256; ++s) a.select[s] = s < n_select ? (uint8_t)select[s] : 0;
+  const int64_t budget = 65536 / 8;  // doubles
+  a.block = 0;
+  a.span_cap = 0;
+  a.group = n_select < 4 ? n_select : 4;  // unstaged: the channels of one tap walk
+  if (taps) {
+    auto span_of = [&](int b) { return (int64_t)(b - 1) * down / up + 2 * a.half / up + 2; };
+    for (const int64_t room : {(int64_t)20480 / 8, budget})
+      for (int b = 1024; b >= 256 && !a.block; b /= 2)
+        if (span_of(b) * n_select <= room) a.block = b, a.span_cap = (int)span_of(b), a.group = n_select;
+    if (!a.block && span_of(256) <= budget) {
+      const int fit = (int)(budget / span_of(256));
+      const int groups = (n_select + fit - 1) / fit;
+      a.block = 256, a.span_cap = (int)span_of(256), a.group = (n_select + groups - 1) / groups;
+    }
+  }
+  const bool staged = a.block != 0;
+  if (!staged) a.block = 1024;
+  const size_t planes = (size_t)a.span_cap * a.group;
+  const bool taps_in_lds = staged && (int64_t)(planes + 2 * a.half + 1) <= budget;
+  const dim3 grid((unsigned)((n_out + a.block - 1) / a.block), (unsigned)((n_select + a.group - 1) / a.group));
+  const size_t lds = (planes + (taps_in_lds ? 2 * a.half + 1 : 0)) * 8;
+#define LAUNCH_SPLIT_AS(R_, MODE_) \
+  k_pcm_resample_split<R_, MODE_><<<grid, 256, lds, st>>>(a), wh_launched("k_pcm_resample_split")
+#define LAUNCH_SPLIT(MODE_)                                       \
+  do {                                                            \
+    switch (encoding) {                                           \
+      case WH_WAV_U8: LAUNCH_SPLIT_AS(ReadU8, MODE_); break;     \
+      case WH_WAV_S16: LAUNCH_SPLIT_AS(ReadS16, MODE_); break;   \
+      case WH_WAV_S24: LAUNCH_SPLIT_AS(ReadS24, MODE_); break;   \
+      case WH_WAV_S32: LAUNCH_SPLIT_AS(ReadS32, MODE_); break;   \
+      case WH_WAV_F32: LAUNCH_SPLIT_AS(ReadF32, MODE_); break;   \
+      case WH_WAV_F64: LAUNCH_SPLIT_AS(ReadF64, MODE_); break;   \
+      case WH_WAV_ALAW: LAUNCH_SPLIT_AS(ReadAlaw, MODE_); break; \
+      case WH_WAV_ULAW: LAUNCH_SPLIT_AS(ReadUlaw, MODE_); break; \
+      default: break; /* the callers pass one of the eight */    \
+    }                                                             \
+  } while (0)
+  if (taps_in_lds) LAUNCH_SPLIT(2);
+  else if (staged) LAUNCH_SPLIT(1);
+  else LAUNCH_SPLIT(0);
+#undef LAUNCH_SPLIT
+#undef LAUNCH_SPLIT_AS
 }
 
 }  // namespace wh

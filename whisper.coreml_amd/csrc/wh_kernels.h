@@ -104,6 +104,13 @@ void launch_mel_seg(const float* audio, const MelFile* files, int n_files, int64
 // allocated 8 bytes past the samples (24-bit samples are read as aligned dwords).  One launch.
 void launch_pcm_resample(const void* pcm, int encoding, int64_t n_frames, int channels, int bits, int up, int down,
                          const double* taps, float* out, int64_t n_out, hipStream_t st);
+// wh_*_ingest_split's kernel: the same input, but no mix: selected channel s (select[s], n_select
+// distinct ids in [0, channels), at most 256) becomes a waveform of its own, n_out samples at
+// out + s * n_out, with the arithmetic the kernel above has for a mono file of that channel.
+// One launch for all selected channels.
+void launch_pcm_resample_split(const void* pcm, int encoding, int64_t n_frames, int channels, int bits, int up,
+                               int down, const double* taps, const int* select, int n_select, float* out,
+                               int64_t n_out, hipStream_t st);
 
 // ------------------------------------------------------------ decode state (device)
 // Per window slot w (capacity nw) with G rows (beams / samples) each.

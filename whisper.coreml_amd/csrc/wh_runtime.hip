@@ -1890,6 +1890,24 @@ int wh_wav_ingest(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int
                   int64_t dst_offset, int64_t reserve, int64_t* n_out) {
   CTXCALL(ctx->audio.wav_ingest(data, n_bytes, up, down, taps, n_taps, dst_offset, reserve, n_out));
 }
+int wh_audio_ingest_split(wh_ctx* ctx, const void* pcm, int format, int64_t n_frames, int channels, int bits, int up,
+                          int down, const double* taps, int n_taps, const int* select, int n_select,
+                          int64_t dst_offset, int64_t reserve, int64_t* n_out) {
+  CTXCALL(ctx->audio.audio_ingest_split(pcm, format, n_frames, channels, bits, up, down, taps, n_taps, select, n_select,
+                                        dst_offset, reserve, n_out));
+}
+int wh_flac_ingest_split(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int down, const double* taps,
+                         int n_taps, const int* select, int n_select, int64_t dst_offset, int64_t reserve,
+                         int64_t* n_out, int* path_out) {
+  CTXCALL(ctx->audio.flac_ingest_split(data, n_bytes, up, down, taps, n_taps, select, n_select, dst_offset, reserve,
+                                       n_out, path_out));
+}
+int wh_wav_ingest_split(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int up, int down, const double* taps,
+                        int n_taps, const int* select, int n_select, int64_t dst_offset, int64_t reserve,
+                        int64_t* n_out) {
+  CTXCALL(ctx->audio.wav_ingest_split(data, n_bytes, up, down, taps, n_taps, select, n_select, dst_offset, reserve,
+                                      n_out));
+}
 int wh_speech_spans(wh_ctx* ctx, const wh_vad_opts* opts, int n_files, int32_t* spans, int cap, int32_t* n_spans,
                     uint64_t* thresholds) {
   CTXCALL(ctx->audio.speech_spans(opts, n_files, spans, cap, n_spans, thresholds));

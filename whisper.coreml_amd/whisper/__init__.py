@@ -19,13 +19,13 @@ from typing import List, Optional, Union
 
 import numpy as np
 
-from .audio import load_audio, load_audio_device, log_mel_spectrogram, pad_or_trim
+from .audio import load_audio, load_audio_channels, load_audio_device, log_mel_spectrogram, pad_or_trim
 from .backend_hip import HipBackendError
 from .decoding import DecodingOptions, DecodingResult, decode, detect_language
 from .model import ModelDimensions, Whisper
 from .synthetic import MODEL_DIMS, synthetic_state_dict
 from .transcribe import transcribe
-from .multifile import transcribe_batch
+from .multifile import merge_channels, transcribe_batch
 from .vad import speech_spans, speech_spans_host
 
 __version__ = "20240930+hip1"
@@ -113,6 +113,6 @@ def load_model(name: str, device: Optional[Union[str, int]] = None, download_roo
     return model
 
 
-__all__ = ["available_models", "load_model", "transcribe", "transcribe_batch", "speech_spans", "speech_spans_host", "decode", "detect_language", "DecodingOptions",
+__all__ = ["available_models", "load_model", "transcribe", "transcribe_batch", "merge_channels", "load_audio_channels", "speech_spans", "speech_spans_host", "decode", "detect_language", "DecodingOptions",
            "DecodingResult", "log_mel_spectrogram", "pad_or_trim", "load_audio", "load_audio_device", "ModelDimensions",
            "Whisper", "HipBackendError"]

@@ -41,6 +41,37 @@ def load_audio(file: str, sr: int = SAMPLE_RATE) -> np.ndarray:
     return pcm_to_waveform(*read_pcm(file), sr)
 
 
+def select_channels(channels, n_channels: int) -> list:
+    """The channel indices a selection names in a file of ``n_channels`` channels: None or
+    "split" is all of them, a sequence is itself (distinct ints in [0, n_channels), else
+    ValueError)."""
+    if channels is None or (isinstance(channels, str) and channels == "split"):
+        return list(range(n_channels))
+    if isinstance(channels, str):
+        raise ValueError(f"channels: {channels!r} is not a selection")
+    sel = [int(c) for c in channels]
+    if not sel:
+        raise ValueError("channels: the selection is empty")
+    for c in sel:
+        if c < 0 or c >= n_channels:
+            raise ValueError(f"channels: {c} is not a channel of a file with {n_channels}")
+    if len(set(sel)) != len(sel):
+        raise ValueError(f"channels: {sel} repeats a channel")
+    return sel
+
+
+def load_audio_channels(file: str, channels=None) -> np.ndarray:
+    """The file's channels as waveforms of their own, float32 ``[C][n]`` at 16 kHz: row k is
+    ``pcm_to_waveform(pcm[:, [channels[k]]], rate, bits)`` of ``read_pcm(file)``, that is
+    ``load_audio`` of a mono file holding only that channel.  ``channels``: a sequence of
+    channel indices, None for all.  The device paths (``HipContext.*_ingest(channels=...)``)
+    give the same samples bit for bit."""
+    pcm, rate, bits = read_pcm(file)
+    pcm = np.asarray(pcm).reshape(len(pcm), -1)
+    sel = select_channels(channels, pcm.shape[1])
+    return np.stack([pcm_to_waveform(pcm[:, [c]], rate, bits) for c in sel])
+
+
 def read_pcm(file: str):
     """The file's samples as stored: (pcm [frames][channels], sample rate, bits per sample).
     FLAC gives int32 (``wh_flac_decode``), a plain 16-bit PCM WAV gives int16 (read with
@@ -268,7 +299,20 @@ def device_filter_taps(rate: int, sr: int = SAMPLE_RATE) -> int:
     return 0 if up == down else 2 * 10 * max(up, down) + 1
 
 
-def ingest_source(file: str, need_length: bool = False):
+def source_channels(source) -> int:
+    """How many channels the file behind an ``ingest_source`` source has."""
+    if isinstance(source, np.ndarray):
+        return 1 if source.ndim == 1 else source.shape[0]
+    if len(source) == 1:
+        from .backend_hip import flac_info
+        return flac_info(source[0])[1]
+    if len(source) == 2:
+        return source[1].channels
+    pcm = np.asarray(source[0])
+    return 1 if pcm.ndim == 1 else int(np.prod(pcm.shape[1:]))
+
+
+def ingest_source(file: str, need_length: bool = False, channels=None):
     """How a file's audio reaches the device, decided in one place: (source, length).
     ``source`` is ``(flac bytes,)`` for ``HipContext.flac_ingest`` (the frames are decoded
     on the device), ``(wav bytes, wav_info)`` for ``HipContext.wav_ingest`` (every WAV but the
@@ -278,7 +322,10 @@ def ingest_source(file: str, need_length: bool = False):
     16 kHz waveform as an array when the rate's filter would exceed ``MAX_DEVICE_TAPS`` and
     the host resampled it.  ``length`` is the 16 kHz
     sample count the source gives; None for a FLAC whose STREAMINFO has no total, unless
-    ``need_length``: then such a file is decoded on the host instead."""
+    ``need_length``: then such a file is decoded on the host instead.  ``channels`` ("split"
+    or a sequence of indices) does not change a tuple source, which holds all channels and
+    answers ``source_channels``; only the host-resampled form differs: it is then the rows
+    ``[C][n]`` of the selected channels (``load_audio_channels``)."""
     if file.lower().endswith(".flac"):
         from .backend_hip import flac_info
         with open(file, "rb") as f:
@@ -297,22 +344,38 @@ def ingest_source(file: str, need_length: bool = False):
             return (data, info), (info.n_frames * up + down - 1) // down
     pcm, rate, bits = plain if plain is not None else read_pcm(file)
     if device_filter_taps(rate) > MAX_DEVICE_TAPS:
+        if channels is not None:
+            pcm = np.asarray(pcm).reshape(len(pcm), -1)
+            rows = np.stack([pcm_to_waveform(pcm[:, [c]], rate, bits) for c in select_channels(channels, pcm.shape[1])])
+            return rows, rows.shape[1]
         waveform = pcm_to_waveform(pcm, rate, bits)
         return waveform, len(waveform)
     up, down = _ratio(rate)
     return (pcm, rate, bits), (len(pcm) * up + down - 1) // down
 
 
-def ingest(ctx, source, dst_offset: int = 0, reserve: int = 0):
-    """A tuple ``ingest_source`` returned, sent to the context call its shape names."""
+def ingest(ctx, source, dst_offset: int = 0, reserve: int = 0, channels=None):
+    """A tuple ``ingest_source`` returned, sent to the context call its shape names.
+    ``channels`` (a sequence of indices) is forwarded: the result is then the list of
+    ``DeviceAudio`` of the split call.  Rows ``[C][n]`` (a 2-D array: channels already at
+    16 kHz) are copied one behind the other, ``channels`` selecting among them."""
+    if isinstance(source, np.ndarray):
+        rows = source if channels is None else source[list(channels)]
+        out = []
+        for row in rows:
+            out.append(ctx.audio_ingest(np.ascontiguousarray(row, dtype=np.float32), SAMPLE_RATE, 32,
+                                        dst_offset=dst_offset, reserve=reserve))
+            dst_offset += out[-1].n_samples
+        return out
+    kw = {} if channels is None else dict(channels=list(channels))
     if len(source) == 1:
-        return ctx.flac_ingest(source[0], dst_offset=dst_offset, reserve=reserve)
+        return ctx.flac_ingest(source[0], dst_offset=dst_offset, reserve=reserve, **kw)
     if len(source) == 2:
-        return ctx.wav_ingest(source[0], dst_offset=dst_offset, reserve=reserve)
-    return ctx.audio_ingest(*source, dst_offset=dst_offset, reserve=reserve)
+        return ctx.wav_ingest(source[0], dst_offset=dst_offset, reserve=reserve, **kw)
+    return ctx.audio_ingest(*source, dst_offset=dst_offset, reserve=reserve, **kw)
 
 
-def load_audio_device(model, file: str):
+def load_audio_device(model, file: str, channels=None):
     """``load_audio`` whose mixing, resampling and quantisation run on the GPU: the file's
     PCM is uploaded (int16 or int32) and the 16 kHz waveform is made in the context's
     resident audio buffer (``HipContext.audio_ingest``), the same samples bit for bit.
@@ -325,10 +388,18 @@ def load_audio_device(model, file: str):
     extensible headers) is not unpacked on the host either: its data chunk is uploaded as it
     is and the kernel reads the encoding (``HipContext.wav_ingest``).
     A rate whose filter would exceed ``MAX_DEVICE_TAPS`` is resampled on the host and
-    uploaded instead (``ingest_source`` decides)."""
+    uploaded instead (``ingest_source`` decides).
+    ``channels`` ("split" for all, or a sequence of channel indices): no mix, the result is a
+    list of ``DeviceAudio``, one resident segment per selected channel (the rows of
+    ``load_audio_channels``, made by one upload and one launch)."""
     ctx = getattr(model, "ctx", model)
     if ctx is None or isinstance(ctx, (int, str)):
         ctx = _mel_context(_device_index(ctx))
+    if channels is not None:
+        source, _ = ingest_source(file, channels=channels)
+        if isinstance(source, np.ndarray):
+            return ingest(ctx, source)
+        return ingest(ctx, source, channels=select_channels(channels, source_channels(source)))
     source, _ = ingest_source(file)
     if isinstance(source, np.ndarray):
         return ctx.audio_upload(source)

@@ -126,6 +126,12 @@ _EXPORTS = {
     "wh_wav_last_error": (c_char_p, []),
     "wh_wav_ingest": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_int64,
                               POINTER(c_int64)]),
+    "wh_audio_ingest_split": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                      c_void_p, c_int, c_int64, c_int64, POINTER(c_int64)]),
+    "wh_flac_ingest_split": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                     c_int64, c_int64, POINTER(c_int64), POINTER(c_int)]),
+    "wh_wav_ingest_split": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                    c_int64, c_int64, POINTER(c_int64)]),
 }
 N_STATS = 16  # WH_N_STATS
 FLAC_PATHS = ("device", "host")
@@ -355,14 +361,21 @@ class HipContext:
         self._check(self.lib.wh_audio_upload(self.h, _ptr(a), a.shape[0]), "wh_audio_upload")
         return DeviceAudio(self, a.shape[0])
 
+    def _split_segments(self, n: int, count: int, dst_offset: int, decoded_on: Optional[str] = None):
+        """What a split ingest returns: ``count`` segments of ``n`` samples back to back."""
+        return [DeviceAudio(self, n, int(dst_offset) + k * n, decoded_on) for k in range(count)]
+
     def audio_ingest(self, pcm: np.ndarray, rate: int, bits: int, dst_offset: int = 0,
-                     reserve: int = 0) -> "DeviceAudio":
+                     reserve: int = 0, channels: Optional[Sequence[int]] = None):
         """A decoded file's PCM ([frames][channels] integers of ``bits`` bits at ``rate`` Hz)
         -> the mono 16 kHz float32 waveform of ``audio.pcm_to_waveform``, computed on the
         device (wh_audio_ingest) into the resident buffer at sample ``dst_offset`` (0: a new
         list of segments; the end of the last one: appended).  int16 is uploaded when
         ``bits <= 16``, else int32.  A 1-D float32 array with ``rate == 16000`` is a
-        waveform: copied unchanged."""
+        waveform: copied unchanged.  ``channels`` (a sequence of channel indices): no mix, every
+        selected channel becomes a segment of its own (wh_audio_ingest_split, the rows of
+        ``audio.load_audio_channels``); the result is then a list of ``DeviceAudio`` in
+        selection order, at consecutive offsets."""
         from .audio import SAMPLE_RATE, resample_filter
         a = np.asarray(pcm)
         n_out = c_int64()
@@ -379,34 +392,57 @@ class HipContext:
             up, down, taps = resample_filter(int(rate))
             args = (_ptr(a), fmt, a.shape[0], a.shape[1], int(bits), up, down,
                     None if taps is None else _ptr(taps), 0 if taps is None else taps.shape[0])
+        if channels is not None:
+            sel = np.asarray(list(channels), dtype=np.int32)
+            self._check(self.lib.wh_audio_ingest_split(self.h, *args, _ptr(sel), len(sel), int(dst_offset), int(reserve),
+                                                       ctypes.byref(n_out)), "wh_audio_ingest_split")
+            return self._split_segments(n_out.value, len(sel), dst_offset)
         self._check(self.lib.wh_audio_ingest(self.h, *args, int(dst_offset), int(reserve), ctypes.byref(n_out)),
                     "wh_audio_ingest")
         return DeviceAudio(self, n_out.value, int(dst_offset))
 
-    def flac_ingest(self, data: bytes, dst_offset: int = 0, reserve: int = 0) -> "DeviceAudio":
+    def flac_ingest(self, data: bytes, dst_offset: int = 0, reserve: int = 0,
+                    channels: Optional[Sequence[int]] = None):
         """A FLAC stream -> the waveform of ``audio.load_audio`` in the resident buffer, decoded
         on the device (wh_flac_ingest: frames in parallel, the PCM never on the host) with
         ``audio_ingest``'s segment semantics.  ``decoded_on`` of the result tells which decoder
         ran: "host" means the stream was outside the device path and went through
-        ``decode_flac`` and ``audio_ingest``, with the same samples or the same error."""
+        ``decode_flac`` and ``audio_ingest``, with the same samples or the same error.
+        ``channels``: as for ``audio_ingest`` (wh_flac_ingest_split), a list of ``DeviceAudio``."""
         from .audio import resample_filter
         buf = np.frombuffer(data, np.uint8)
         up, down, taps = resample_filter(flac_info(data)[0])
         n_out, path = c_int64(), c_int(-1)
+        if channels is not None:
+            sel = np.asarray(list(channels), dtype=np.int32)
+            self._check(self.lib.wh_flac_ingest_split(
+                self.h, _ptr(buf), len(buf), up, down, None if taps is None else _ptr(taps),
+                0 if taps is None else taps.shape[0], _ptr(sel), len(sel), int(dst_offset), int(reserve),
+                ctypes.byref(n_out), ctypes.byref(path)), "wh_flac_ingest_split")
+            return self._split_segments(n_out.value, len(sel), dst_offset, FLAC_PATHS[path.value])
         self._check(self.lib.wh_flac_ingest(self.h, _ptr(buf), len(buf), up, down, None if taps is None else _ptr(taps),
                                             0 if taps is None else taps.shape[0], int(dst_offset), int(reserve),
                                             ctypes.byref(n_out), ctypes.byref(path)), "wh_flac_ingest")
         return DeviceAudio(self, n_out.value, int(dst_offset), FLAC_PATHS[path.value])
 
-    def wav_ingest(self, data: bytes, dst_offset: int = 0, reserve: int = 0) -> "DeviceAudio":
+    def wav_ingest(self, data: bytes, dst_offset: int = 0, reserve: int = 0,
+                   channels: Optional[Sequence[int]] = None):
         """A WAV file's bytes -> the waveform of ``audio.load_audio`` in the resident buffer
         (wh_wav_ingest), with ``audio_ingest``'s segment semantics.  Only the data chunk is
         uploaded, in the file's own sample encoding (8 / 16 / 24 / 32-bit PCM, 32 / 64-bit
-        float, A-law, mu-law), and the resampling kernel reads it."""
+        float, A-law, mu-law), and the resampling kernel reads it.  ``channels``: as for
+        ``audio_ingest`` (wh_wav_ingest_split), a list of ``DeviceAudio``."""
         from .audio import resample_filter
         buf = np.frombuffer(data, np.uint8)
         up, down, taps = resample_filter(wav_info(data).sample_rate)
         n_out = c_int64()
+        if channels is not None:
+            sel = np.asarray(list(channels), dtype=np.int32)
+            self._check(self.lib.wh_wav_ingest_split(
+                self.h, _ptr(buf), len(buf), up, down, None if taps is None else _ptr(taps),
+                0 if taps is None else taps.shape[0], _ptr(sel), len(sel), int(dst_offset), int(reserve),
+                ctypes.byref(n_out)), "wh_wav_ingest_split")
+            return self._split_segments(n_out.value, len(sel), dst_offset)
         self._check(self.lib.wh_wav_ingest(self.h, _ptr(buf), len(buf), up, down, None if taps is None else _ptr(taps),
                                            0 if taps is None else taps.shape[0], int(dst_offset), int(reserve),
                                            ctypes.byref(n_out)), "wh_wav_ingest")

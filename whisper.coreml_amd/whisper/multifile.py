@@ -20,13 +20,20 @@ its own max), the files' frames lying back to back in the context mel.  At most
 ``ctx.max_windows`` lanes are live; a lane that ends hands its slot to the next
 pending file of the group.  ``run_files`` is the scheduler alone, with the GPU work
 behind callables, so it can be driven without a device.
+
+A file given with ``channels="split"`` (or a list of channel indices) is not mixed down:
+every selected channel is a lane of its own, as if it were a file (``expand_channels``).
+The channels of a file are ingested by one call (``HipContext.*_ingest(channels=...)``: one
+upload, one launch, the segments back to back), form a unit that ``split_groups`` never cuts,
+and come back as one dict (``merge_channels``).
 """
 
-from typing import TYPE_CHECKING, Callable, List, Optional, Sequence, Tuple, Union
+from typing import TYPE_CHECKING, Callable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .audio import HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, ingest, ingest_source
+from .audio import (HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, ingest, ingest_source, select_channels,
+                    source_channels)
 from .backend_hip import DeviceAudio
 from .decoding import DecodingResult, language_probs, next_seed
 from .tokenizer import LANGUAGES, get_tokenizer
@@ -46,18 +53,109 @@ def file_frames(n_samples: int) -> int:
     return (int(n_samples) + N_SAMPLES) // HOP_LENGTH
 
 
-def split_groups(frames: Sequence[int], mel_budget_frames: int) -> List[List[int]]:
+def split_groups(frames: Sequence[int], mel_budget_frames: int,
+                 units: Optional[Sequence[int]] = None) -> List[List[int]]:
     """Consecutive files whose frames fit the budget; a file larger than the budget is a
-    group of its own (it needs that much mel under transcribe() as well)."""
+    group of its own (it needs that much mel under transcribe() as well).  ``units`` names
+    what must not be cut: ``units[i]`` is the unit of entry i, the entries of a unit are
+    consecutive (the channels of a split file), and a unit goes into a group whole; one larger
+    than the budget is a group of its own.  Without it every entry is its own unit."""
+    if units is None:
+        units = range(len(frames))
+    elif len(units) != len(frames):
+        raise ValueError(f"units: {len(units)} values for {len(frames)} entries")
     groups: List[List[int]] = []
     used = 0
-    for i, f in enumerate(frames):
+    i = 0
+    while i < len(frames):
+        j = i + 1
+        while j < len(frames) and units[j] == units[i]:
+            j += 1
+        f = sum(frames[i:j])
         if not groups or used + f > mel_budget_frames:
             groups.append([])
             used = 0
-        groups[-1].append(i)
+        groups[-1].extend(range(i, j))
         used += f
+        i = j
     return groups
+
+
+def expand_channels(counts: Sequence[Optional[int]]) -> Tuple[List[int], List[int]]:
+    """Files -> lanes.  ``counts[i]`` is None for a file that is mixed down (one lane) or the
+    number of channels selected from it (that many lanes, in selection order).  Returns
+    (file_of, channel_of): per lane the file it belongs to, which is also its unit for
+    ``split_groups``, and its place in the file's selection."""
+    file_of: List[int] = []
+    channel_of: List[int] = []
+    for i, c in enumerate(counts):
+        if c is not None and c < 1:
+            raise ValueError(f"audio {i}: no channel selected")
+        for k in range(1 if c is None else c):
+            file_of.append(i)
+            channel_of.append(k)
+    return file_of, channel_of
+
+
+def merge_channels(results: Sequence[dict], names: Optional[Sequence[str]] = None) -> dict:
+    """The per-channel results of one recording as one two-sided (or C-sided) dialogue; a pure
+    host function.  ``results[k]`` is what ``transcribe`` returns for channel k's waveform;
+    ``names`` default to "0", "1", ... and must be as many.  The dict holds
+    ``"channels"``: the results as given, in order (each keeps its own ``"speech_spans"``);
+    ``"segments"``: copies of all channels' segments with ``"channel"`` (the name) and
+    ``"channel_index"`` (k), sorted by (start, end, channel_index), ``"id"`` renumbered from 0,
+    words carried along;
+    ``"text"``: one line ``"<name>: <text>"`` per merged segment whose stripped text is not empty;
+    ``"language"``: the common one when all channels agree, otherwise that of the channel with
+    the largest summed segment duration (ties: the lowest index)."""
+    results = list(results)
+    if not results:
+        raise ValueError("merge_channels: no channels")
+    names = [str(k) for k in range(len(results))] if names is None else [str(x) for x in names]
+    if len(names) != len(results):
+        raise ValueError(f"merge_channels: {len(names)} names for {len(results)} channels")
+    merged = []
+    for k, r in enumerate(results):
+        for seg in r["segments"]:
+            merged.append(dict(seg, channel=names[k], channel_index=k))
+    merged.sort(key=lambda g: (g["start"], g["end"], g["channel_index"]))  # stable: a channel's order is kept
+    for i, seg in enumerate(merged):
+        seg["id"] = i
+    lines = [f"{seg['channel']}: {seg['text'].strip()}" for seg in merged if seg["text"].strip()]
+    langs = [r.get("language") for r in results]
+    if all(x == langs[0] for x in langs):
+        language = langs[0]
+    else:
+        spoken = [sum(float(g["end"]) - float(g["start"]) for g in r["segments"]) for r in results]
+        language = langs[max(range(len(results)), key=lambda k: (spoken[k], -k))]
+    return dict(text="\n".join(lines), segments=merged, language=language, channels=results)
+
+
+class _SplitSource(NamedTuple):
+    """A split file waiting for its group: what ``audio.ingest`` takes (an ``ingest_source``
+    tuple, or rows ``[C][n]``) and the channels to select (None: all rows)."""
+    source: object
+    channels: Optional[list]
+
+
+def _channel_value(value, what: str):
+    """One ``channels`` value -> None (mix), "split", or a list of ints."""
+    if value is None or (isinstance(value, str) and value == "mix"):
+        return None
+    if isinstance(value, str):
+        if value != "split":
+            raise ValueError(f"{what}: channels={value!r} is none of None, 'mix', 'split' or a list of channel indices")
+        return "split"
+    return [int(c) for c in value]
+
+
+def _is_channel_value(v) -> bool:
+    if v is None or isinstance(v, str):
+        return True
+    try:
+        return len(v) > 0 and all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in v)
+    except TypeError:
+        return False
 
 
 def run_lanes(lanes: Sequence["_Lane"], max_windows: int, decode_round: Callable[[List[Window]], List[DecodingResult]],
@@ -94,11 +192,12 @@ def run_lanes(lanes: Sequence["_Lane"], max_windows: int, decode_round: Callable
 def run_files(n_samples: Sequence[int], *, max_windows: int, mel_budget_frames: int,
               prepare_group: Callable[[List[int]], Sequence[int]],
               make_lanes: Callable[[List[int], Sequence[int]], List["_Lane"]],
-              decode_round, align_round=None) -> List["_Lane"]:
+              decode_round, align_round=None, units: Optional[Sequence[int]] = None) -> List["_Lane"]:
     """The scheduler: checks the lengths, splits the files into mel groups, and runs each
     group's lanes longest-first.  ``prepare_group(indices)`` computes the group's mel and
     returns the files' frame bases; ``make_lanes(indices, bases)`` builds their lanes
-    (language detection sits there).  Returns the finished lanes in input order."""
+    (language detection sits there).  Returns the finished lanes in input order.  ``units``:
+    ``split_groups``'s, for entries that are the channels of one file."""
     for i, n in enumerate(n_samples):
         if int(n) < 1:
             raise ValueError(f"audio {i} is empty")
@@ -106,7 +205,7 @@ def run_files(n_samples: Sequence[int], *, max_windows: int, mel_budget_frames: 
         raise ValueError("mel_budget_frames must be positive")
     frames = [file_frames(n) for n in n_samples]
     out: List[Optional["_Lane"]] = [None] * len(frames)
-    for group in split_groups(frames, mel_budget_frames):
+    for group in split_groups(frames, mel_budget_frames, units):
         bases = prepare_group(group)
         lanes = make_lanes(group, bases)
         for i, lane in zip(group, lanes):
@@ -139,7 +238,8 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
                      initial_prompt=None, carry_initial_prompt: bool = False, word_timestamps: bool = False,
                      prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
                      clip_timestamps="0", hallucination_silence_threshold: Optional[float] = None,
-                     skip_silence: Union[bool, dict] = False, **decode_options) -> List[dict]:
+                     skip_silence: Union[bool, dict] = False, channels=None, channel_names=None,
+                     **decode_options) -> List[dict]:
     """``[transcribe(model, a, **kwargs) for a in audios]`` with the files decoded
     together: ``result[i]`` is what ``transcribe(model, audios[i], ...)`` returns.
 
@@ -152,7 +252,18 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     become the files' clips; a file without speech takes no lane.  The other keywords are
     transcribe()'s; the decoding options among them (``no_repeat_ngram_size`` and
     ``repetition_penalty`` included) are one value for all files, and ``hotwords`` with
-    ``hotword_boost`` / ``hotword_start`` are one phrase table for all files."""
+    ``hotword_boost`` / ``hotword_start`` are one phrase table for all files.
+
+    ``channels``: one value for all files or a list with one per file; None or "mix" is the
+    mix-down above, "split" transcribes every channel of the file on its own, a list of
+    channel indices those channels.  A split file's result is ``merge_channels`` of its
+    channels' results: ``result[i]["channels"][k]`` is what ``transcribe(model,
+    load_audio_channels(audios[i])[k], ...)`` returns.  A 2-D float32 array ``[C][n]`` at 16 kHz
+    is accepted only with a split value; its rows are the channels.  Lengths, language
+    detection, speech spans, plans and sampling seeds are per channel; ``language``,
+    ``initial_prompt`` and ``clip_timestamps`` given per file hold for all its channels.
+    ``channel_names``: the names ``merge_channels`` uses, one list for all split files or a
+    list with one (or None) per file."""
     for k in ("schedule", "mel_max_reduce", "_mel_prepared"):
         if k in decode_options:
             raise TypeError(f"transcribe_batch() does not take {k!r}")
@@ -164,29 +275,70 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
         raise TypeError("audios must be a sequence of paths and/or 1-D arrays")
     # what audio_ingest takes per file, (pcm or waveform, rate, bits), (FLAC bytes,) for
     # flac_ingest or (WAV bytes, its wav_info) for wav_ingest, and the 16 kHz length it gives
-    sources: List[tuple] = []
+    # A split file has one entry per selected channel: the first holds the file's source and the
+    # selection (one ingest call makes all its segments), the others None.
+    audios = list(audios)
+    n_files = len(audios)
+    selections = [_channel_value(v, f"audio {i}") for i, v in
+                  enumerate(_per_file(channels, n_files, "channels", _is_channel_value))]
+    sources: List[Optional[tuple]] = []
     lengths: List[int] = []
+    selected: List[Optional[list]] = [None] * n_files  # per split file, the channel indices
     for i, a in enumerate(audios):
         if isinstance(a, DeviceAudio):
             raise TypeError(f"audio {i}: DeviceAudio is one file resident in the context; pass paths or arrays")
         if isinstance(a, str):
             # FLAC bytes and PCM wait for the group's turn; the length has to be known before
-            a, length = ingest_source(a, need_length=True)
+            a, length = ingest_source(a, need_length=True, channels=selections[i])
             if isinstance(a, tuple):
+                if selections[i] is not None:
+                    selected[i] = select_channels(selections[i], source_channels(a))
+                    sources.extend([_SplitSource(a, selected[i])] + [None] * (len(selected[i]) - 1))
+                    lengths.extend([length] * len(selected[i]))
+                    continue
                 sources.append(a)
                 lengths.append(length)
                 continue
+            if selections[i] is not None:  # resampled on the host: the selected rows already
+                selected[i] = list(range(a.shape[0]))
+                rows = np.ascontiguousarray(a, dtype=np.float32)
+                sources.extend([_SplitSource(rows, None)] + [None] * (a.shape[0] - 1))
+                lengths.extend([a.shape[1]] * a.shape[0])
+                continue
         a = np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32)
+        if selections[i] is not None:
+            if a.ndim == 1:
+                a = a[None, :]
+            if a.ndim != 2:
+                raise ValueError(f"audio {i} is neither 1-D nor [channels][samples] (shape {a.shape})")
+            selected[i] = select_channels(selections[i], a.shape[0])
+            sources.extend([_SplitSource(a, selected[i])] + [None] * (len(selected[i]) - 1))
+            lengths.extend([a.shape[1]] * len(selected[i]))
+            continue
         if a.ndim != 1:
-            raise ValueError(f"audio {i} is not 1-D (shape {a.shape})")
+            raise ValueError(f"audio {i} is not 1-D (shape {a.shape}); a [channels][samples] array needs "
+                             "channels='split' or a list of channel indices")
         sources.append((a, SAMPLE_RATE, 32))
         lengths.append(a.shape[0])
+    file_of, _ = expand_channels([None if sel is None else len(sel) for sel in selected])
     n = len(sources)
-    languages = _per_file(language, n, "language", lambda v: v is None or isinstance(v, str))
-    prompts = _per_file(initial_prompt, n, "initial_prompt",
-                        lambda v: v is None or isinstance(v, str) or all(_is_number(x) for x in v))
-    clips = _per_file(clip_timestamps, n, "clip_timestamps",
-                      lambda v: isinstance(v, str) or all(_is_number(x) for x in v))
+    if channel_names is None or (len(channel_names) > 0 and all(isinstance(x, str) for x in channel_names)):
+        names_of = [channel_names] * n_files
+    else:
+        names_of = _per_file(channel_names, n_files, "channel_names", lambda v: False)
+    for i, sel in enumerate(selected):
+        if sel is not None and names_of[i] is not None and len(names_of[i]) != len(sel):
+            raise ValueError(f"audio {i}: {len(names_of[i])} channel_names for {len(sel)} channels")
+
+    def per_lane(value, name, is_single):
+        per_file = _per_file(value, n_files, name, is_single)
+        return [per_file[i] for i in file_of]
+
+    languages = per_lane(language, "language", lambda v: v is None or isinstance(v, str))
+    prompts = per_lane(initial_prompt, "initial_prompt",
+                       lambda v: v is None or isinstance(v, str) or all(_is_number(x) for x in v))
+    clips = per_lane(clip_timestamps, "clip_timestamps",
+                     lambda v: isinstance(v, str) or all(_is_number(x) for x in v))
     thresholds = (compression_ratio_threshold, logprob_threshold, no_speech_threshold)
     probe = get_tokenizer(model.is_multilingual, num_languages=model.num_languages) if model.is_multilingual else None
 
@@ -196,10 +348,17 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
         total = sum(lengths[i] for i in group)
         offset = 0
         for i in group:
-            seg = ingest(ctx, sources[i], dst_offset=offset, reserve=total)
-            if seg.n_samples != lengths[i]:
-                raise RuntimeError(f"audio {i}: {seg.n_samples} samples ingested, {lengths[i]} planned")
-            offset += seg.n_samples
+            if sources[i] is None:
+                continue  # a further channel of a split file: its first channel's call made the segment
+            if isinstance(sources[i], _SplitSource):
+                segs = ingest(ctx, sources[i].source, dst_offset=offset, reserve=total, channels=sources[i].channels)
+            else:
+                segs = [ingest(ctx, sources[i], dst_offset=offset, reserve=total)]
+            for k, seg in enumerate(segs):
+                if seg.n_samples != lengths[i + k] or seg.offset != offset:
+                    raise RuntimeError(f"audio {file_of[i]}: {seg.n_samples} samples ingested at {seg.offset}, "
+                                       f"{lengths[i + k]} planned at {offset}")
+                offset += seg.n_samples
         if vad_params is not None:
             # one detector call for the group, on the segments that were just ingested
             for i, (sp, _) in zip(group, resident_spans(ctx, len(group), vad_params)):
@@ -233,7 +392,8 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
                     print(f"[{group[k]}] Detected language: {LANGUAGES[languages[group[k]]].title()}")
 
     plans = {}
-    # one sampling seed per file, drawn in input order as a loop of transcribe() calls draws them
+    # one sampling seed per file (per channel of a split file), drawn in input order as a loop of
+    # transcribe() calls over the files and the channel waveforms draws them
     file_seeds = [next_seed() for _ in range(n)]
 
     def make_lanes(group: List[int], bases) -> List[_Lane]:
@@ -263,7 +423,7 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     decode_round, align_round = _device_round(model, per_file=True)
     lanes = run_files(lengths, max_windows=ctx.max_windows, mel_budget_frames=mel_budget_frames,
                       prepare_group=prepare_group, make_lanes=make_lanes, decode_round=decode_round,
-                      align_round=align_round if word_timestamps else None)
+                      align_round=align_round if word_timestamps else None, units=file_of)
     results = []
     for i, lane in enumerate(lanes):
         tokenizer, _, prompt_tokens, _ = plans[i]
@@ -278,4 +438,10 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
                             language=languages[i]))
         if vad_params is not None:
             results[-1]["speech_spans"] = frames_to_seconds(spans[i])
-    return results
+    if all(sel is None for sel in selected):
+        return results
+    out = []
+    for i, sel in enumerate(selected):
+        mine = [results[j] for j in range(n) if file_of[j] == i]
+        out.append(mine[0] if sel is None else merge_channels(mine, names_of[i]))
+    return out

@@ -223,7 +223,8 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
                append_punctuations: str = "\"'.。,，!！?？:：”)]}、", clip_timestamps: Union[str, List[float]] = "0",
                hallucination_silence_threshold: Optional[float] = None, schedule: str = "auto",
                mel_max_reduce=None, _mel_prepared: Optional[Tuple[int, int, int]] = None,
-               skip_silence: Union[bool, dict] = False, **decode_options) -> dict:
+               skip_silence: Union[bool, dict] = False, channels=None, channel_names=None,
+               **decode_options) -> dict:
     """transcribe.py:41-524.  Extra keywords: ``schedule`` ("auto", "sequential",
     "batched"), ``mel_max_reduce`` (callable local max -> global max, used when
     one file is sharded over GPUs: the log-mel floor is a whole-file max,
@@ -236,7 +237,30 @@ def transcribe(model: "Whisper", audio: Union[str, np.ndarray], *, verbose: Opti
     temperature ladder.  So do ``hotwords``, ``hotword_boost`` and ``hotword_start`` (phrase
     biasing): the table is installed for every window, also with ``skip_silence`` and
     ``condition_on_previous_text=False``; ``avg_logprob`` is then that of the biased
-    distribution, which the ``logprob_threshold`` fallback compares."""
+    distribution, which the ``logprob_threshold`` fallback compares.
+    ``channels``: None or "mix" is the mix-down of all channels; "split" or a list of channel
+    indices transcribes each selected channel of the file (a path, or a float32 array
+    ``[C][n]`` at 16 kHz) on its own, through ``transcribe_batch``'s machinery, and returns
+    ``merge_channels`` of the per-channel results under ``channel_names``.  A split value
+    cannot be combined with ``schedule``, ``mel_max_reduce``, ``_mel_prepared`` or a
+    ``DeviceAudio``."""
+    if channels is not None and not (isinstance(channels, str) and channels == "mix"):
+        for name, given in (("schedule", schedule != "auto"), ("mel_max_reduce", mel_max_reduce is not None),
+                            ("_mel_prepared", _mel_prepared is not None),
+                            ("DeviceAudio", isinstance(audio, DeviceAudio))):
+            if given:
+                raise ValueError(f"transcribe(channels={channels!r}) cannot be combined with "
+                                 f"{'a ' if name == 'DeviceAudio' else ''}{name}")
+        from .multifile import transcribe_batch
+        return transcribe_batch(
+            model, [audio], channels=[channels], channel_names=None if channel_names is None else [channel_names],
+            verbose=verbose, temperature=temperature, compression_ratio_threshold=compression_ratio_threshold,
+            logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold,
+            condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt,
+            carry_initial_prompt=carry_initial_prompt, word_timestamps=word_timestamps,
+            prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
+            clip_timestamps=clip_timestamps, hallucination_silence_threshold=hallucination_silence_threshold,
+            skip_silence=skip_silence, **decode_options)[0]
     _check_fp16(model, decode_options.pop("fp16", True))
     ctx = model.ctx
     n_mels = model.dims.n_mels
