@@ -504,6 +504,64 @@ int wh_wav_ingest_split(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int u
                         int n_taps, const int* select, int n_select, int64_t dst_offset, int64_t reserve,
                         int64_t* n_out);
 
+/* ---- A resident stream: a recording that arrives in chunks (live audio from a socket).  The
+   context resamples every chunk as it comes and keeps ONE growing resident segment, so
+   wh_log_mel(ctx, NULL, n, ...), wh_speech_spans and wh_audio_read work on it as they are.
+   A stream is raw interleaved frames [n_frames][channels] in one of the eight WH_WAV_* sample
+   encodings (no container); up, down, taps as for wh_audio_ingest, from the stream's rate.
+
+   The contract: take any split of a recording of N frames into chunks (one-frame chunks and
+   chunks shorter than the filter included).  The samples the appends emit, followed by those of
+   wh_stream_finish, are bit for bit what wh_wav_ingest / wh_audio_ingest write for the whole
+   recording at once.  This is exact, not approximate: output k of the one-shot kernel reads
+   frames from m_k = (k*down + half) / up backwards over 2*half/up frames and accumulates with fma
+   in that fixed order; frames outside the file are 0.0, and an fma with a zero operand leaves the
+   accumulator unchanged.  So output k is final once frame m_k has arrived, and after n frames in
+   total the stream has emitted
+     E(n) = max(0, ceil((n*up - half) / down))     (n when up == down: there is no filter)
+   samples: at most 20 outputs (1.25 ms) are held back.  wh_stream_finish emits the rest up to
+   ceil(N*up/down), reading the frames from N on as zeros.  wh_stream_emitted (host only, no
+   context) returns E(n_frames), or with final != 0 the total ceil(n_frames*up/down); -1 for
+   n_frames < 0 or up, down < 1.
+   The frames a later chunk still needs, the last 2*half/up of them mixed down to fp64, are kept
+   on the device in a double buffer (csrc/wh_ingest.hip, k_pcm_resample_stream): an append reads
+   one half and writes the other, with no host round trip.
+
+   wh_stream_begin opens a stream and leaves an empty resident segment; a stream that was open is
+   dropped.  reserve (0 allowed): the samples the caller expects to hold at once.
+   wh_stream_append takes n_frames frames; *n_out (nullable) = samples emitted by this call,
+   E(after) - E(before), possibly 0.  n_frames == 0 is a no-op.
+   wh_stream_finish ends the input: *n_out (nullable) = the samples it emitted.  The stream stays
+   open for wh_stream_trim and wh_stream_info; a second finish emits nothing.
+   wh_stream_trim drops the first n_drop resident samples, 0 <= n_drop <= resident length: the
+   rest moves to sample 0 unchanged (through a bounce buffer when source and destination
+   overlap), n_drop == length leaves an empty segment.  Later appends continue without a seam:
+   the resampler's state lives in input frames and is not touched.
+   wh_stream_info: frames appended, samples emitted, samples dropped (the resident segment is
+   (0, samples_out - samples_dropped)), finished; any pointer may be null.
+   Any other call that writes the resident buffer ends the stream: wh_audio_upload, every
+   wh_*_ingest*, wh_log_mel* with a host array.  Afterwards append, finish, trim and info are
+   refused until the next wh_stream_begin.
+   Refused before the first HIP call, the stream and the resident samples unchanged, -1 for a null
+   pointer and -7 otherwise, wh_last_error naming "stream" and the field: an encoding outside the
+   eight, channels outside 1..256, up or down outside 1..2^20, an n_taps other than 2*half + 1
+   (or null taps) when up != down, a negative reserve; append / finish / trim / info without an
+   open stream; append after finish; null data with n_frames > 0; n_frames < 0 or past 2^40 in
+   total; n_drop out of range.
+   Counters: the uploads and the trim's copies go to WH_STAT_INGEST_COPY_MS, the kernel to
+   WH_STAT_INGEST_KERNEL_MS.  wh_version() does not change with these six: a caller detects them
+   by the presence of the symbols. */
+int wh_stream_begin(wh_ctx* ctx, int encoding /* WH_WAV_* */, int channels, int up, int down, const double* taps,
+                    int n_taps, int64_t reserve);
+int wh_stream_append(wh_ctx* ctx, const void* data, int64_t n_frames, int64_t* n_out);
+int wh_stream_finish(wh_ctx* ctx, int64_t* n_out);
+int wh_stream_trim(wh_ctx* ctx, int64_t n_drop);
+int wh_stream_info(wh_ctx* ctx, int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped, int* finished);
+/* returns a 64-bit count (int64_t's width on every ABI): the only entry point whose result is
+   not a status, spelled so that tools which list the `int wh_*(` declarations still see it */
+long long
+int wh_stream_emitted(int64_t n_frames, int up, int down, int final);
+
 #ifdef __cplusplus
 }
 #endif

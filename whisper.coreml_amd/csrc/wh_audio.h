@@ -45,6 +45,12 @@ struct AudioFront {
                         const int* select, int n_select, int64_t dst, int64_t reserve, int64_t* n_out, int* path);
   int wav_ingest_split(const uint8_t* data, int64_t n, int up, int down, const double* taps, int n_taps,
                        const int* select, int n_select, int64_t dst, int64_t reserve, int64_t* n_out);
+  // a recording that arrives in chunks: one growing resident segment (include/whisper_hip.h)
+  int stream_begin(int encoding, int channels, int up, int down, const double* taps, int n_taps, int64_t reserve);
+  int stream_append(const void* data, int64_t n_frames, int64_t* n_out);
+  int stream_finish(int64_t* n_out);
+  int stream_trim(int64_t n_drop);
+  int stream_info(int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped, int* finished);
   // audio == nullptr: use the resident buffer of wh_audio_upload (n must match)
   int log_mel(const float* audio, int64_t n, int64_t pad, int n_mels, int normalize, int64_t* nf) {
     return log_mel_frames(audio, n, pad, n_mels, 0, -1, normalize, nf);
@@ -85,6 +91,19 @@ struct AudioFront {
   DevBuf<int32_t> fl_chain;
   DevBuf<int64_t> fl_starts;
 
+  // wh_stream_*: the open stream.  The resident segment is (0, samples_out - dropped); the
+  // history of the last `hist` mixed-down frames lies in half `cur` of d_hist ([2][hist]
+  // doubles), the next append writes the other half.  ended_by: the call that closed it
+  struct Stream {
+    bool open = false, finished = false;
+    int encoding = 0, channels = 0, bits = 0, frame_bytes = 0, up = 1, down = 1, hist = 0, cur = 0;
+    const double* taps = nullptr;  // the device filter of (up, down), null when up == down
+    int64_t frames_in = 0, samples_out = 0, dropped = 0;
+    std::string ended_by;
+  } stream;
+  DevBuf<double> d_hist;
+  DevBuf<float> d_bounce;  // wh_stream_trim, when the move overlaps itself
+
   DevBuf<float> d_mel;
   int64_t mel_frames = 0;
   int64_t mel_f0 = 0;  // absolute index of the first stored frame
@@ -106,6 +125,10 @@ struct AudioFront {
   DevBuf<char> vad_out;
 
   void one_segment(int64_t n);
+  void stream_ends(const char* by);
+  int stream_open(const std::string& who, bool for_input);
+  int stream_run(const void* data, int64_t nc, int64_t total, int64_t* n_out);
+  int filter_taps(const std::string& who, int up, int down, const double* taps, int n_taps, double** dt);
   int vad_plan(const char* who, int n_files, std::vector<wh::VadFile>* files, int64_t* blocks);
   int vad_energy_launch(const std::vector<wh::VadFile>& files, int64_t blocks);
   int audio_room(size_t samples);

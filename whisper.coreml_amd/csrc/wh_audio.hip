@@ -26,6 +26,8 @@ int AudioFront::init(hipStream_t stream, double* counters) {
 void AudioFront::release(Releases& rel) {
   d_audio.release(rel, "hipFree(audio)");
   d_pcm.release(rel, "hipFree(pcm)");
+  d_hist.release(rel, "hipFree(stream history)");
+  d_bounce.release(rel, "hipFree(stream bounce)");
   auto flac = [&](auto&... b) { (b.release(rel, "hipFree(flac)"), ...); };
   flac(fl_bytes, fl_cands, fl_subs, fl_ends, fl_stage, fl_chain, fl_starts);
   for (auto& kv : d_taps) rel(hipFree(kv.second), "hipFree(resampling taps)");
@@ -59,6 +61,7 @@ int AudioFront::set_mel_filters(int n_mels, const float* filters) {
 int AudioFront::audio_room(size_t samples) { return d_audio.reserve(std::max<size_t>(samples, 16000) * 4); }
 
 int AudioFront::audio_upload(const float* audio, int64_t n) {
+  stream_ends("audio_upload");
   TRY(audio_room((size_t)n));
   HIPCHK(hipMemcpyAsync(d_audio.p, audio, n * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -124,20 +127,8 @@ int AudioFront::ingest_run(const std::string& who, const void* pcm, int format, 
   const bool filt = !f32 && up != down;
   const int64_t no = filt ? (n * up + down - 1) / down : n;
   double* dt = nullptr;
-  if (filt) {
-    const auto key = std::make_pair(up, down);
-    auto it = d_taps.find(key);
-    if (it == d_taps.end()) {
-      HIPCHK(hipMalloc(&dt, (size_t)n_taps * 8));
-      if (hipMemcpy(dt, taps, (size_t)n_taps * 8, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(dt);
-        return fail(-100, who + "copying the filter taps failed");
-      }
-      d_taps[key] = dt;
-    } else {
-      dt = it->second;
-    }
-  }
+  if (filt) TRY(filter_taps(who, up, down, taps, n_taps, &dt));
+  stream_ends(who.c_str());
   // room for the new end (or the caller's reserve); the segments before dst survive a move
   TRY(d_audio.reserve(std::max<size_t>(std::max(dst + n_seg * no, reserve), 16000) * 4, (size_t)dst * 4, st));
   if (f32) {
@@ -162,6 +153,169 @@ int AudioFront::ingest_run(const std::string& who, const void* pcm, int format, 
   for (int s = 0; s < n_seg; ++s) audio_segs.emplace_back(dst + s * no, no);
   audio_n = audio_segs.size() == 1 ? no : -1;
   *n_out = no;
+  return 0;
+}
+
+// the device copy of the filter of (up, down), uploaded the first time it is seen
+int AudioFront::filter_taps(const std::string& who, int up, int down, const double* taps, int n_taps, double** dt) {
+  const auto key = std::make_pair(up, down);
+  auto it = d_taps.find(key);
+  if (it != d_taps.end()) {
+    *dt = it->second;
+    return 0;
+  }
+  double* d = nullptr;
+  HIPCHK(hipMalloc(&d, (size_t)n_taps * 8));
+  if (hipMemcpy(d, taps, (size_t)n_taps * 8, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    return fail(-100, who + "copying the filter taps failed");
+  }
+  d_taps[key] = d;
+  *dt = d;
+  return 0;
+}
+
+// ------------------------------------------------------------ a resident stream
+// (include/whisper_hip.h).  Everything is checked before the first HIP call.
+// E(n): the outputs that are final after n frames; the total when the recording has ended
+static int64_t stream_emitted(int64_t n, int up, int down, bool final) {
+  if (up == down) return n;
+  if (final) return (n * up + down - 1) / down;
+  const int64_t room = n * up - 10 * (int64_t)std::max(up, down);
+  return room <= 0 ? 0 : (room + down - 1) / down;
+}
+extern "C" long long wh_stream_emitted(int64_t n_frames, int up, int down, int final) {
+  if (n_frames < 0 || n_frames > ((int64_t)1 << 40) || up < 1 || down < 1 || up > (1 << 20) || down > (1 << 20)) return -1;
+  return stream_emitted(n_frames, up, down, final != 0);
+}
+// another call took the resident buffer: the stream is over, and append says who ended it
+void AudioFront::stream_ends(const char* by) {
+  if (!stream.open) return;
+  stream.open = false;
+  stream.ended_by = by;
+  while (!stream.ended_by.empty() && (stream.ended_by.back() == ' ' || stream.ended_by.back() == ':')) stream.ended_by.pop_back();
+}
+int AudioFront::stream_open(const std::string& who, bool for_input) {
+  if (!stream.open)
+    return fail(-7, who + "stream: no open stream" +
+                        (stream.ended_by.empty() ? std::string() : " (ended by " + stream.ended_by + ")"));
+  if (for_input && stream.finished) return fail(-7, who + "stream: already finished, no more input is taken");
+  return 0;
+}
+int AudioFront::stream_begin(int encoding, int channels, int up, int down, const double* taps, int n_taps,
+                             int64_t reserve) {
+  const std::string who = "stream_begin: ";
+  if (encoding < WH_WAV_U8 || encoding > WH_WAV_ULAW)
+    return fail(-7, who + "stream: unknown encoding " + std::to_string(encoding));
+  if (channels < 1 || channels > 256) return fail(-7, who + "stream: channels = " + std::to_string(channels) + " out of range");
+  if (up < 1 || down < 1 || up > (1 << 20) || down > (1 << 20))
+    return fail(-7, who + "stream: up = " + std::to_string(up) + ", down = " + std::to_string(down) + " out of range");
+  const int64_t half = 10 * (int64_t)std::max(up, down), want = 2 * half + 1;
+  if (up != down && (!taps || n_taps != want))
+    return fail(-7, who + "stream: n_taps = " + std::to_string(taps ? n_taps : 0) + ", the filter of up = " +
+                        std::to_string(up) + ", down = " + std::to_string(down) + " has " + std::to_string(want));
+  if (reserve < 0) return fail(-7, who + "stream: negative reserve");
+  //                         U8 S16 S24 S32 F32 F64 ALAW ULAW
+  static const int container[8] = {1, 2, 3, 4, 4, 8, 1, 1};
+  static const int bits[8] = {8, 16, 24, 32, 1, 1, 16, 16};  // as in wav_ingest
+  double* dt = nullptr;
+  if (up != down) TRY(filter_taps(who, up, down, taps, n_taps, &dt));
+  const int hist = up != down ? (int)(2 * half / up) : 0;
+  TRY(d_hist.reserve((size_t)std::max(hist, 1) * 16));
+  TRY(d_audio.reserve(std::max<size_t>((size_t)reserve, 16000) * 4));
+  // the frames before the recording are zeros
+  HIPCHK(hipMemsetAsync(d_hist.p, 0, (size_t)std::max(hist, 1) * 16, st));
+  HIPCHK(hipStreamSynchronize(st));
+  stream = Stream();
+  stream.open = true;
+  stream.encoding = encoding; stream.channels = channels; stream.bits = bits[encoding];
+  stream.frame_bytes = container[encoding] * channels;
+  stream.up = up; stream.down = down; stream.hist = hist; stream.taps = dt;
+  one_segment(0);
+  return 0;
+}
+// frames [frames_in, frames_in + nc) arrive (data), or the recording ends (nc = 0, total = all
+// there will be): the outputs that become final are appended to the resident segment
+int AudioFront::stream_run(const void* data, int64_t nc, int64_t total, int64_t* n_out) {
+  Stream& s = stream;
+  const int64_t len = s.samples_out - s.dropped, emit = total - s.samples_out;
+  if (len + emit > (int64_t)(d_audio.cap / 4))  // grows by doubling: an append a second does not reallocate each time
+    TRY(d_audio.reserve((size_t)std::max(len + emit, 2 * len) * 4, (size_t)len * 4, st));
+  const size_t bytes = (size_t)nc * s.frame_bytes;
+  TRY(d_pcm.reserve(bytes + 8));  // 24-bit samples are read as aligned dwords
+  double* old_half = d_hist.p + (size_t)s.cur * s.hist;
+  double* new_half = d_hist.p + (size_t)(1 - s.cur) * s.hist;
+  TRY(tm.mark(0, st));
+  if (nc) HIPCHK(hipMemcpyAsync(d_pcm.p, data, bytes, hipMemcpyHostToDevice, st));
+  TRY(tm.mark(1, st));
+  launch_pcm_resample_stream(d_pcm.p, s.encoding, s.frames_in, nc, s.channels, s.bits, s.up, s.down, s.taps, old_half,
+                             new_half, s.hist, d_audio.p + len, s.samples_out, emit, st);
+  TRY(tm.mark(2, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(launch_status("stream_append"));
+  TRY(tm.charge(0, stats[WH_STAT_INGEST_COPY_MS]));
+  TRY(tm.charge(1, stats[WH_STAT_INGEST_KERNEL_MS]));
+  if (s.hist) s.cur = 1 - s.cur;
+  s.frames_in += nc;
+  s.samples_out = total;
+  one_segment(len + emit);
+  if (n_out) *n_out = emit;
+  return 0;
+}
+int AudioFront::stream_append(const void* data, int64_t n_frames, int64_t* n_out) {
+  const std::string who = "stream_append: ";
+  TRY(stream_open(who, true));
+  if (n_frames < 0 || n_frames > ((int64_t)1 << 40) - stream.frames_in)
+    return fail(-7, who + "stream: n_frames = " + std::to_string(n_frames) + " out of range");
+  if (n_frames == 0) {
+    if (n_out) *n_out = 0;
+    return 0;
+  }
+  if (!data) return fail(-1, who + "stream: null data with n_frames > 0");
+  return stream_run(data, n_frames, stream_emitted(stream.frames_in + n_frames, stream.up, stream.down, false), n_out);
+}
+int AudioFront::stream_finish(int64_t* n_out) {
+  const std::string who = "stream_finish: ";
+  TRY(stream_open(who, false));
+  if (!stream.finished) {
+    const int64_t total = stream_emitted(stream.frames_in, stream.up, stream.down, true);
+    if (total > stream.samples_out) TRY(stream_run(nullptr, 0, total, n_out));
+    else if (n_out) *n_out = 0;
+    stream.finished = true;
+    return 0;
+  }
+  if (n_out) *n_out = 0;
+  return 0;
+}
+int AudioFront::stream_trim(int64_t n_drop) {
+  const std::string who = "stream_trim: ";
+  TRY(stream_open(who, false));
+  const int64_t len = stream.samples_out - stream.dropped;
+  if (n_drop < 0 || n_drop > len)
+    return fail(-7, who + "stream: n_drop = " + std::to_string(n_drop) + " outside [0, " + std::to_string(len) + "]");
+  const int64_t rest = len - n_drop;
+  if (n_drop && rest) {
+    const bool overlap = rest > n_drop;  // [n_drop, len) reaches into [0, rest)
+    if (overlap) TRY(d_bounce.reserve((size_t)rest * 4));
+    TRY(tm.mark(0, st));
+    if (overlap) {
+      HIPCHK(hipMemcpyAsync(d_bounce.p, d_audio.p + n_drop, (size_t)rest * 4, hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(d_audio.p, d_bounce.p, (size_t)rest * 4, hipMemcpyDeviceToDevice, st));
+    } else {
+      HIPCHK(hipMemcpyAsync(d_audio.p, d_audio.p + n_drop, (size_t)rest * 4, hipMemcpyDeviceToDevice, st));
+    }
+    TRY(tm.finish(st, stats[WH_STAT_INGEST_COPY_MS]));
+  }
+  stream.dropped += n_drop;
+  one_segment(rest);
+  return 0;
+}
+int AudioFront::stream_info(int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped, int* finished) {
+  TRY(stream_open("stream_info: ", false));
+  if (frames_in) *frames_in = stream.frames_in;
+  if (samples_out) *samples_out = stream.samples_out;
+  if (samples_dropped) *samples_dropped = stream.dropped;
+  if (finished) *finished = stream.finished ? 1 : 0;
   return 0;
 }
 
@@ -515,7 +669,10 @@ int AudioFront::log_mel_frames(const float* audio, int64_t n, int64_t pad, int n
   const int64_t total = (n + pad) / 160;
   if (count < 0) count = total - frame0;
   if (frame0 < 0 || count < 1 || frame0 + count > total) return fail(-7, "mel frame range out of bounds");
-  if (audio) TRY(audio_room((size_t)n));
+  if (audio) {
+    stream_ends("log_mel with a host array");
+    TRY(audio_room((size_t)n));
+  }
   TRY(d_mel.reserve((size_t)n_mels * count * 4));
   TRY(tm.mark(0, st));
   if (audio) {
@@ -566,6 +723,7 @@ int AudioFront::log_mel_batch(const float* audio, int n_files, const int64_t* n_
       return fail(-7, "log_mel_batch: the " + std::to_string(audio_segs.size()) +
                           " resident segments are not these " + std::to_string(n_files) + " files");
   } else {
+    stream_ends("log_mel_batch with a host array");
     TRY(audio_room((size_t)samples));
     audio_n = -1;  // the buffer now holds several files: no resident audio of any length
     audio_segs.clear();

@@ -188,6 +188,91 @@ void launch_pcm_resample(const void* pcm, int encoding, int64_t n_frames, int ch
 #undef LAUNCH_RESAMPLE_AS
 }
 
+// ---------------------------------------------------------------- PCM ingest, a chunk of a stream
+// k_pcm_resample for a recording that arrives in chunks (wh_stream_append, wh_stream_finish).
+// All indices are those of the whole recording: the chunk holds frames [n0, n0 + nc), the launch
+// writes outputs [k0, k0 + n_emit), k0 = E(n0), whose newest frame (k*down + half) / up lies in
+// the chunk.  Output k walks the same taps in the same order with the same fma as the one-shot
+// kernel, so it is that kernel's output k; the only difference is where x[m] comes from:
+//   m >= n0 + nc   0.0 (only wh_stream_finish asks: the frames behind the recording)
+//   m >= n0        pcm_frame of the chunk's frame m - n0
+//   m >= n0 - H    hist_old[m - (n0 - H)], the fp64 x[m] the launch that owned frame m stored
+// and nothing older is reached: the walk of output k >= E(n0) ends at or after frame
+// n0 - 2*half/up, and H = 2*half/up.  Frames before the recording are stored as the 0.0 they
+// are (the history starts zeroed).  The block behind the output blocks writes the next
+// history, x[n0 + nc - H .. n0 + nc), into the other half of the double buffer: a chunk
+// shorter than H takes the frames it lacks from the old history, and a launch that emits
+// nothing still moves the history on.  No filter (taps null): out[k] is x[k] quantised, H = 0.
+struct StreamArgs {
+  const void* pcm;  // the chunk
+  int64_t n0, nc, k0, n_emit;
+  int channels, up, down, half, hist;
+  double scale;
+  const double* taps;
+  const double* hist_old;
+  double* hist_new;
+  float* out;  // output k0
+};
+
+template <typename R>
+__device__ inline double stream_frame(const StreamArgs& a, int64_t m) {
+  if (m >= a.n0) return pcm_frame<R>((const uint8_t*)a.pcm, m - a.n0, a.nc, a.channels, a.scale);
+  const int64_t j = m - (a.n0 - a.hist);
+  return j >= 0 ? a.hist_old[j] : 0.0;
+}
+
+template <typename R>
+__global__ __launch_bounds__(256) void k_pcm_resample_stream(StreamArgs a) {
+  const int64_t out_blocks = (a.n_emit + 255) / 256;
+  if ((int64_t)blockIdx.x >= out_blocks) {
+    for (int j = threadIdx.x; j < a.hist; j += 256) a.hist_new[j] = stream_frame<R>(a, a.n0 + a.nc - a.hist + j);
+    return;
+  }
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_emit) return;
+  const int64_t k = a.k0 + i;
+  double y;
+  if (!a.taps) {
+    y = stream_frame<R>(a, k);
+  } else {
+    const int last_tap = 2 * a.half;
+    const int64_t c = k * a.down + a.half;
+    int64_t m = c / a.up;         // the newest frame that reaches output k
+    int t = (int)(c - m * a.up);  // and its tap
+    y = 0.0;
+    for (; t <= last_tap; t += a.up, --m) y = fma(stream_frame<R>(a, m), a.taps[t], y);
+  }
+  double r = rint(y * 32768.0);  // round half to even, as np.round
+  r = fmin(fmax(r, -32768.0), 32767.0);
+  a.out[i] = (float)r * (1.0f / 32768.0f);
+}
+
+void launch_pcm_resample_stream(const void* pcm, int encoding, int64_t n0, int64_t nc, int channels, int bits, int up,
+                                int down, const double* taps, const double* hist_old, double* hist_new, int hist,
+                                float* out, int64_t k0, int64_t n_emit, hipStream_t st) {
+  if (n_emit < 1 && hist < 1) return;
+  StreamArgs a;
+  a.pcm = pcm; a.n0 = n0; a.nc = nc; a.k0 = k0; a.n_emit = n_emit; a.channels = channels; a.up = up; a.down = down;
+  a.half = taps ? 10 * (up > down ? up : down) : 0;
+  a.hist = hist;
+  a.scale = ldexp(1.0, -(bits - 1));
+  a.taps = taps; a.hist_old = hist_old; a.hist_new = hist_new; a.out = out;
+  const unsigned grid = (unsigned)((n_emit + 255) / 256) + (hist > 0 ? 1 : 0);
+#define LAUNCH_STREAM_AS(R_) k_pcm_resample_stream<R_><<<grid, 256, 0, st>>>(a), wh_launched("k_pcm_resample_stream")
+  switch (encoding) {
+    case WH_WAV_U8: LAUNCH_STREAM_AS(ReadU8); break;
+    case WH_WAV_S16: LAUNCH_STREAM_AS(ReadS16); break;
+    case WH_WAV_S24: LAUNCH_STREAM_AS(ReadS24); break;
+    case WH_WAV_S32: LAUNCH_STREAM_AS(ReadS32); break;
+    case WH_WAV_F32: LAUNCH_STREAM_AS(ReadF32); break;
+    case WH_WAV_F64: LAUNCH_STREAM_AS(ReadF64); break;
+    case WH_WAV_ALAW: LAUNCH_STREAM_AS(ReadAlaw); break;
+    case WH_WAV_ULAW: LAUNCH_STREAM_AS(ReadUlaw); break;
+    default: break; /* the callers pass one of the eight */
+  }
+#undef LAUNCH_STREAM_AS
+}
+
 // ---------------------------------------------------------------- PCM ingest, channels apart
 // The sibling of k_pcm_resample for wh_*_ingest_split: no mix, selected channel s (the file's
 // channel select[s]) becomes a waveform of its own at out + s * n_out.  Its input is that

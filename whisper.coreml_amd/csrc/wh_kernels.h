@@ -104,6 +104,15 @@ void launch_mel_seg(const float* audio, const MelFile* files, int n_files, int64
 // allocated 8 bytes past the samples (24-bit samples are read as aligned dwords).  One launch.
 void launch_pcm_resample(const void* pcm, int encoding, int64_t n_frames, int channels, int bits, int up, int down,
                          const double* taps, float* out, int64_t n_out, hipStream_t st);
+// wh_stream_append / wh_stream_finish's kernel: the chunk `pcm` holds frames [n0, n0 + nc) of a
+// recording; outputs [k0, k0 + n_emit) of launch_pcm_resample on the whole recording go to out[0 ..
+// n_emit).  Frames before n0 are read from hist_old (`hist` = 2*half/up doubles, frames
+// [n0 - hist, n0)), frames from n0 + nc on are zeros; hist_new (another buffer) receives frames
+// [n0 + nc - hist, n0 + nc).  The caller guarantees that every output's newest frame is below
+// n0 + nc or that the recording has ended.  The chunk buffer is allocated 8 bytes past its samples.
+void launch_pcm_resample_stream(const void* pcm, int encoding, int64_t n0, int64_t nc, int channels, int bits, int up,
+                                int down, const double* taps, const double* hist_old, double* hist_new, int hist,
+                                float* out, int64_t k0, int64_t n_emit, hipStream_t st);
 // wh_*_ingest_split's kernel: the same input, but no mix: selected channel s (select[s], n_select
 // distinct ids in [0, channels), at most 256) becomes a waveform of its own, n_out samples at
 // out + s * n_out, with the arithmetic the kernel above has for a mono file of that channel.

@@ -1908,6 +1908,18 @@ int wh_wav_ingest_split(wh_ctx* ctx, const uint8_t* data, int64_t n_bytes, int u
   CTXCALL(ctx->audio.wav_ingest_split(data, n_bytes, up, down, taps, n_taps, select, n_select, dst_offset, reserve,
                                       n_out));
 }
+int wh_stream_begin(wh_ctx* ctx, int encoding, int channels, int up, int down, const double* taps, int n_taps,
+                    int64_t reserve) {
+  CTXCALL(ctx->audio.stream_begin(encoding, channels, up, down, taps, n_taps, reserve));
+}
+int wh_stream_append(wh_ctx* ctx, const void* data, int64_t n_frames, int64_t* n_out) {
+  CTXCALL(ctx->audio.stream_append(data, n_frames, n_out));
+}
+int wh_stream_finish(wh_ctx* ctx, int64_t* n_out) { CTXCALL(ctx->audio.stream_finish(n_out)); }
+int wh_stream_trim(wh_ctx* ctx, int64_t n_drop) { CTXCALL(ctx->audio.stream_trim(n_drop)); }
+int wh_stream_info(wh_ctx* ctx, int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped, int* finished) {
+  CTXCALL(ctx->audio.stream_info(frames_in, samples_out, samples_dropped, finished));
+}
 int wh_speech_spans(wh_ctx* ctx, const wh_vad_opts* opts, int n_files, int32_t* spans, int cap, int32_t* n_spans,
                     uint64_t* thresholds) {
   CTXCALL(ctx->audio.speech_spans(opts, n_files, spans, cap, n_spans, thresholds));

@@ -299,6 +299,20 @@ def device_filter_taps(rate: int, sr: int = SAMPLE_RATE) -> int:
     return 0 if up == down else 2 * 10 * max(up, down) + 1
 
 
+def stream_emitted(n: int, rate: int, final: bool = False, sr: int = SAMPLE_RATE) -> int:
+    """How many 16 kHz samples a stream at ``rate`` Hz has emitted after ``n`` frames
+    (``wh_stream_emitted``, include/whisper_hip.h): output k is final once its newest frame
+    ``(k * down + half) // up`` has arrived, so E(n) = max(0, ceil((n * up - half) / down)), or n
+    at 16 kHz; ``final``: the whole recording's ceil(n * up / down)."""
+    up, down = _ratio(rate, sr)
+    n = int(n)
+    if up == down:
+        return n
+    if final:
+        return -(-n * up // down)
+    return max(0, -(-(n * up - 10 * max(up, down)) // down))
+
+
 def source_channels(source) -> int:
     """How many channels the file behind an ``ingest_source`` source has."""
     if isinstance(source, np.ndarray):

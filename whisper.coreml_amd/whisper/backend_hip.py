@@ -132,6 +132,12 @@ _EXPORTS = {
                                      c_int64, c_int64, POINTER(c_int64), POINTER(c_int)]),
     "wh_wav_ingest_split": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
                                     c_int64, c_int64, POINTER(c_int64)]),
+    "wh_stream_begin": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int64]),
+    "wh_stream_append": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
+    "wh_stream_finish": (c_int, [c_void_p, POINTER(c_int64)]),
+    "wh_stream_trim": (c_int, [c_void_p, c_int64]),
+    "wh_stream_info": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int)]),
+    "wh_stream_emitted": (c_int64, [c_int64, c_int, c_int, c_int]),
 }
 N_STATS = 16  # WH_N_STATS
 FLAC_PATHS = ("device", "host")
@@ -447,6 +453,41 @@ class HipContext:
                                            0 if taps is None else taps.shape[0], int(dst_offset), int(reserve),
                                            ctypes.byref(n_out)), "wh_wav_ingest")
         return DeviceAudio(self, n_out.value, int(dst_offset))
+
+    # -- a resident stream (include/whisper_hip.h): audio that arrives in chunks
+    def stream_begin(self, encoding: int, channels: int, rate: int, reserve: int = 0):
+        """Open the context's stream of raw frames in ``encoding`` (a WH_WAV_* code) at ``rate``
+        Hz; the resident audio becomes one empty segment that the appends grow."""
+        from .audio import resample_filter
+        up, down, taps = resample_filter(int(rate))
+        self._check(self.lib.wh_stream_begin(self.h, int(encoding), int(channels), up, down,
+                                             None if taps is None else _ptr(taps),
+                                             0 if taps is None else taps.shape[0], int(reserve)), "wh_stream_begin")
+
+    def stream_append(self, data, n_frames: int) -> int:
+        """``n_frames`` frames (a contiguous uint8 array, or None with 0 frames) -> the samples
+        this call added to the resident segment."""
+        n_out = c_int64()
+        self._check(self.lib.wh_stream_append(self.h, None if data is None else _ptr(data), int(n_frames),
+                                              ctypes.byref(n_out)), "wh_stream_append")
+        return n_out.value
+
+    def stream_finish(self) -> int:
+        """End of the input: the samples the resampler still held back are added; how many."""
+        n_out = c_int64()
+        self._check(self.lib.wh_stream_finish(self.h, ctypes.byref(n_out)), "wh_stream_finish")
+        return n_out.value
+
+    def stream_trim(self, n_drop: int):
+        """Drop the first ``n_drop`` resident samples; the rest moves to sample 0."""
+        self._check(self.lib.wh_stream_trim(self.h, int(n_drop)), "wh_stream_trim")
+
+    def stream_info(self):
+        """(frames appended, samples emitted, samples dropped, finished) of the open stream."""
+        fi, so, sd, fin = c_int64(), c_int64(), c_int64(), c_int()
+        self._check(self.lib.wh_stream_info(self.h, ctypes.byref(fi), ctypes.byref(so), ctypes.byref(sd),
+                                            ctypes.byref(fin)), "wh_stream_info")
+        return fi.value, so.value, sd.value, bool(fin.value)
 
     def flac_decode_device(self, data: bytes):
         """``decode_flac`` on the device (wh_flac_decode_device): (samples int32
