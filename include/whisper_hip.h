@@ -562,6 +562,63 @@ int wh_stream_info(wh_ctx* ctx, int64_t* frames_in, int64_t* samples_out, int64_
 long long
 int wh_stream_emitted(int64_t n_frames, int up, int down, int final);
 
+/* ---- A pool of streams: many live recordings on one context, fed and decoded together.
+   wh_pool_create gives the context n_slots slots (1..4096); a slot holds one stream with its own
+   format, its own history and its own resident buffer of at most slot_samples 16 kHz samples.  The
+   pool shares nothing with the resident segments or the single stream above: no wh_audio_upload,
+   wh_*_ingest*, wh_log_mel* or wh_stream_* call touches a slot, and no pool call touches the
+   resident segments or the single stream.  wh_pool_destroy frees it (every slot is dropped).
+
+   Each slot obeys the wh_stream_* contract, stream by stream: take any split of a recording into
+   packets and batch them with any packets of other slots; the samples the slot emits, followed by
+   those of wh_pool_finish, are bit for bit what wh_wav_ingest writes for the whole recording
+   (the pool's kernel runs the single stream's device functions, csrc/wh_ingest.hip).
+
+   wh_pool_open: wh_stream_begin's format arguments and refusals, for a slot that is not open.
+   wh_pool_close frees the slot for another open.
+   wh_pool_append: n packets, packet i being n_frames[i] frames at data[i] for slot slots[i];
+   n_out[i] (n_out nullable) = E(after) - E(before) of wh_stream_emitted.  n_frames[i] == 0 is
+   allowed and emits 0 (data[i] may then be null).  One call gathers the packets in pinned memory
+   (each 16-byte aligned, 8 readable bytes behind it) and makes one copy of them, one descriptor
+   copy, one kernel launch and one synchronisation, whatever n is.
+   wh_pool_finish ends the input of the n slots (one launch); a slot that is already finished
+   emits 0.  The slots stay open for trim, info, read and log_mel.
+   wh_pool_trim drops the first n_drop[i] resident samples of slot slots[i], 0 <= n_drop[i] <=
+   resident length; the rest is unchanged and later appends continue without a seam.  Every slot
+   has two buffers: the remainder is copied into the other one (one launch for all slots) and
+   the slot then reads that one, so no copy overlaps itself.
+   wh_pool_info: as wh_stream_info, for one slot.  wh_pool_read: the slot's resident samples
+   [offset, offset + n).
+   wh_pool_log_mel is wh_log_mel_batch with the files taken from the buffers of the n slots, in
+   call order: the same kernels and per-file normalisation, frame_base[n + 1] as there, and
+   wh_mel_max_batch(ctx, g, n) works afterwards.  It writes only the context mel.
+
+   A batched call is all or nothing.  Everything is checked before the first HIP call, and a
+   refused call leaves every slot, every n_out[] entry, the counters and the context mel as they
+   were: -1 for a null pointer and -7 otherwise, wh_last_error naming "pool", the field and its
+   index in the call.  Refused: no pool (a second create while one exists); n_slots or
+   slot_samples out of range; a slot out of range, or not open (already open, for open); the same
+   slot twice in one call; n < 1; null data[i] with n_frames[i] > 0; n_frames[i] < 0 or past 2^40
+   in total; an append after finish; n_drop[i] outside the resident length; a read outside it; a
+   log_mel of an empty slot; and an append (or finish) that would take a slot past slot_samples:
+   the message says "capacity", and the caller must trim first.
+   Counters: the copies go to WH_STAT_INGEST_COPY_MS, the kernels to WH_STAT_INGEST_KERNEL_MS,
+   the mel to WH_STAT_MEL_MS.  wh_version() does not change with these ten: a caller detects them
+   by the presence of the symbols. */
+int wh_pool_create(wh_ctx* ctx, int n_slots, int64_t slot_samples);
+int wh_pool_destroy(wh_ctx* ctx);
+int wh_pool_open(wh_ctx* ctx, int slot, int encoding /* WH_WAV_* */, int channels, int up, int down,
+                 const double* taps, int n_taps);
+int wh_pool_close(wh_ctx* ctx, int slot);
+int wh_pool_append(wh_ctx* ctx, int n, const int* slots, const void* const* data, const int64_t* n_frames,
+                   int64_t* n_out);
+int wh_pool_finish(wh_ctx* ctx, int n, const int* slots, int64_t* n_out);
+int wh_pool_trim(wh_ctx* ctx, int n, const int* slots, const int64_t* n_drop);
+int wh_pool_info(wh_ctx* ctx, int slot, int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped,
+                 int* finished);
+int wh_pool_read(wh_ctx* ctx, int slot, float* out, int64_t offset, int64_t n);
+int wh_pool_log_mel(wh_ctx* ctx, int n, const int* slots, int64_t padding, int n_mels, int64_t* frame_base);
+
 #ifdef __cplusplus
 }
 #endif

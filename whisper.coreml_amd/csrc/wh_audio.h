@@ -51,6 +51,17 @@ struct AudioFront {
   int stream_finish(int64_t* n_out);
   int stream_trim(int64_t n_drop);
   int stream_info(int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped, int* finished);
+  // many live streams at once: slots with buffers of their own (include/whisper_hip.h)
+  int pool_create(int n_slots, int64_t slot_samples);
+  int pool_destroy();
+  int pool_open(int slot, int encoding, int channels, int up, int down, const double* taps, int n_taps);
+  int pool_close(int slot);
+  int pool_append(int n, const int* slots, const void* const* data, const int64_t* n_frames, int64_t* n_out);
+  int pool_finish(int n, const int* slots, int64_t* n_out);
+  int pool_trim(int n, const int* slots, const int64_t* n_drop);
+  int pool_info(int slot, int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped, int* finished);
+  int pool_read(int slot, float* out, int64_t offset, int64_t n);
+  int pool_log_mel(int n, const int* slots, int64_t pad, int n_mels, int64_t* frame_base);
   // audio == nullptr: use the resident buffer of wh_audio_upload (n must match)
   int log_mel(const float* audio, int64_t n, int64_t pad, int n_mels, int normalize, int64_t* nf) {
     return log_mel_frames(audio, n, pad, n_mels, 0, -1, normalize, nf);
@@ -103,6 +114,31 @@ struct AudioFront {
   } stream;
   DevBuf<double> d_hist;
   DevBuf<float> d_bounce;  // wh_stream_trim, when the move overlaps itself
+
+  // wh_pool_*: n_slots streams, none of whose state is shared with the single stream or the
+  // resident segments.  Slot s owns floats [s][2][slot_samples] of pool_audio: its resident
+  // samples are the first samples_out - dropped of buffer `buf`, a trim copies the remainder
+  // into the other buffer and flips `buf`.  Its history is a double buffer of its own, as the
+  // single stream's.  A batched call gathers its packets in pool_stage (pinned; every packet
+  // 16-byte aligned with 8 readable bytes behind it) and its descriptors in pool_hdesc (pinned):
+  // one copy each to pool_pcm and pool_desc, one launch, one synchronisation.
+  struct PoolSlot : Stream {
+    int buf = 0;
+    DevBuf<double> hist_buf;  // [2][hist], kept across close / open
+  };
+  std::vector<PoolSlot> pool;
+  int64_t pool_samples = 0;  // slot_samples
+  DevBuf<float> pool_audio;
+  DevBuf<char> pool_pcm, pool_desc;
+  char* pool_stage = nullptr;
+  char* pool_hdesc = nullptr;
+  size_t pool_stage_cap = 0, pool_hdesc_cap = 0;
+  float* pool_base(int slot, int buf) { return pool_audio.p + ((size_t)slot * 2 + buf) * pool_samples; }
+  void pool_release(Releases& rel);
+  int pool_slots(const std::string& who, int n, const int* slots, bool for_input);
+  int pool_pinned(char** p, size_t* cap, size_t bytes);
+  int pool_run(int n, const int* slots, const void* const* data, const int64_t* n_frames, const int64_t* totals,
+               int64_t* n_out, const char* where);
 
   DevBuf<float> d_mel;
   int64_t mel_frames = 0;

@@ -28,6 +28,7 @@ void AudioFront::release(Releases& rel) {
   d_pcm.release(rel, "hipFree(pcm)");
   d_hist.release(rel, "hipFree(stream history)");
   d_bounce.release(rel, "hipFree(stream bounce)");
+  pool_release(rel);
   auto flac = [&](auto&... b) { (b.release(rel, "hipFree(flac)"), ...); };
   flac(fl_bytes, fl_cands, fl_subs, fl_ends, fl_stage, fl_chain, fl_starts);
   for (auto& kv : d_taps) rel(hipFree(kv.second), "hipFree(resampling taps)");
@@ -202,22 +203,28 @@ int AudioFront::stream_open(const std::string& who, bool for_input) {
   if (for_input && stream.finished) return fail(-7, who + "stream: already finished, no more input is taken");
   return 0;
 }
+// what wh_stream_begin and wh_pool_open refuse in a stream's format; `who` ends in "stream: " or "pool: "
+static int stream_format_check(const std::string& who, int encoding, int channels, int up, int down,
+                               const double* taps, int n_taps) {
+  if (encoding < WH_WAV_U8 || encoding > WH_WAV_ULAW) return fail(-7, who + "unknown encoding " + std::to_string(encoding));
+  if (channels < 1 || channels > 256) return fail(-7, who + "channels = " + std::to_string(channels) + " out of range");
+  if (up < 1 || down < 1 || up > (1 << 20) || down > (1 << 20))
+    return fail(-7, who + "up = " + std::to_string(up) + ", down = " + std::to_string(down) + " out of range");
+  const int64_t want = 2 * 10 * (int64_t)std::max(up, down) + 1;
+  if (up != down && (!taps || n_taps != want))
+    return fail(-7, who + "n_taps = " + std::to_string(taps ? n_taps : 0) + ", the filter of up = " +
+                        std::to_string(up) + ", down = " + std::to_string(down) + " has " + std::to_string(want));
+  return 0;
+}
+//                                     U8 S16 S24 S32 F32 F64 ALAW ULAW
+static const int stream_container[8] = {1, 2, 3, 4, 4, 8, 1, 1};
+static const int stream_bits[8] = {8, 16, 24, 32, 1, 1, 16, 16};  // as in wav_ingest
 int AudioFront::stream_begin(int encoding, int channels, int up, int down, const double* taps, int n_taps,
                              int64_t reserve) {
   const std::string who = "stream_begin: ";
-  if (encoding < WH_WAV_U8 || encoding > WH_WAV_ULAW)
-    return fail(-7, who + "stream: unknown encoding " + std::to_string(encoding));
-  if (channels < 1 || channels > 256) return fail(-7, who + "stream: channels = " + std::to_string(channels) + " out of range");
-  if (up < 1 || down < 1 || up > (1 << 20) || down > (1 << 20))
-    return fail(-7, who + "stream: up = " + std::to_string(up) + ", down = " + std::to_string(down) + " out of range");
-  const int64_t half = 10 * (int64_t)std::max(up, down), want = 2 * half + 1;
-  if (up != down && (!taps || n_taps != want))
-    return fail(-7, who + "stream: n_taps = " + std::to_string(taps ? n_taps : 0) + ", the filter of up = " +
-                        std::to_string(up) + ", down = " + std::to_string(down) + " has " + std::to_string(want));
+  TRY(stream_format_check(who + "stream: ", encoding, channels, up, down, taps, n_taps));
+  const int64_t half = 10 * (int64_t)std::max(up, down);
   if (reserve < 0) return fail(-7, who + "stream: negative reserve");
-  //                         U8 S16 S24 S32 F32 F64 ALAW ULAW
-  static const int container[8] = {1, 2, 3, 4, 4, 8, 1, 1};
-  static const int bits[8] = {8, 16, 24, 32, 1, 1, 16, 16};  // as in wav_ingest
   double* dt = nullptr;
   if (up != down) TRY(filter_taps(who, up, down, taps, n_taps, &dt));
   const int hist = up != down ? (int)(2 * half / up) : 0;
@@ -228,8 +235,8 @@ int AudioFront::stream_begin(int encoding, int channels, int up, int down, const
   HIPCHK(hipStreamSynchronize(st));
   stream = Stream();
   stream.open = true;
-  stream.encoding = encoding; stream.channels = channels; stream.bits = bits[encoding];
-  stream.frame_bytes = container[encoding] * channels;
+  stream.encoding = encoding; stream.channels = channels; stream.bits = stream_bits[encoding];
+  stream.frame_bytes = stream_container[encoding] * channels;
   stream.up = up; stream.down = down; stream.hist = hist; stream.taps = dt;
   one_segment(0);
   return 0;
@@ -316,6 +323,302 @@ int AudioFront::stream_info(int64_t* frames_in, int64_t* samples_out, int64_t* s
   if (samples_out) *samples_out = stream.samples_out;
   if (samples_dropped) *samples_dropped = stream.dropped;
   if (finished) *finished = stream.finished ? 1 : 0;
+  return 0;
+}
+
+// ------------------------------------------------------------ a pool of streams
+// (include/whisper_hip.h).  A batched call is all or nothing: everything is checked before the
+// first HIP call, and a refused call leaves every slot and every n_out[] entry as it was.
+static std::string field_at(const char* field, int i) { return std::string(field) + "[" + std::to_string(i) + "]"; }
+
+int AudioFront::pool_create(int n_slots, int64_t slot_samples) {
+  const std::string who = "pool_create: pool: ";
+  if (!pool.empty()) return fail(-7, who + "already created (" + std::to_string(pool.size()) + " slots)");
+  if (n_slots < 1 || n_slots > 4096) return fail(-7, who + "n_slots = " + std::to_string(n_slots) + " outside 1..4096");
+  if (slot_samples < 1 || slot_samples > 0x7fffffff)
+    return fail(-7, who + "slot_samples = " + std::to_string(slot_samples) + " out of range");
+  TRY(pool_audio.reserve((size_t)n_slots * 2 * (size_t)slot_samples * 4));
+  pool.assign(n_slots, PoolSlot());
+  pool_samples = slot_samples;
+  return 0;
+}
+void AudioFront::pool_release(Releases& rel) {
+  for (auto& s : pool) s.hist_buf.release(rel, "hipFree(pool history)");
+  pool.clear();
+  pool_samples = 0;
+  pool_audio.release(rel, "hipFree(pool audio)");
+  pool_pcm.release(rel, "hipFree(pool pcm)");
+  pool_desc.release(rel, "hipFree(pool descriptors)");
+  if (pool_stage) rel(hipHostFree(std::exchange(pool_stage, nullptr)), "hipHostFree(pool staging)");
+  if (pool_hdesc) rel(hipHostFree(std::exchange(pool_hdesc, nullptr)), "hipHostFree(pool descriptors)");
+  pool_stage_cap = pool_hdesc_cap = 0;
+}
+int AudioFront::pool_destroy() {
+  if (pool.empty()) return fail(-7, "pool_destroy: pool: no pool");
+  Releases rel;
+  pool_release(rel);
+  return rel.first.empty() ? 0 : fail(-100, "pool_destroy: " + rel.first);
+}
+int AudioFront::pool_open(int slot, int encoding, int channels, int up, int down, const double* taps, int n_taps) {
+  const std::string who = "pool_open: pool: ";
+  if (pool.empty()) return fail(-7, who + "no pool");
+  if (slot < 0 || slot >= (int)pool.size())
+    return fail(-7, who + "slot = " + std::to_string(slot) + " outside [0, " + std::to_string(pool.size()) + ")");
+  if (pool[slot].open) return fail(-7, who + "slot " + std::to_string(slot) + " is already open");
+  TRY(stream_format_check(who, encoding, channels, up, down, taps, n_taps));
+  const int64_t half = 10 * (int64_t)std::max(up, down);
+  double* dt = nullptr;
+  if (up != down) TRY(filter_taps(who, up, down, taps, n_taps, &dt));
+  const int hist = up != down ? (int)(2 * half / up) : 0;
+  PoolSlot& s = pool[slot];
+  TRY(s.hist_buf.reserve((size_t)std::max(hist, 1) * 16));
+  // the frames before the recording are zeros
+  HIPCHK(hipMemsetAsync(s.hist_buf.p, 0, (size_t)std::max(hist, 1) * 16, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const DevBuf<double> keep = s.hist_buf;
+  s = PoolSlot();
+  s.hist_buf = keep;
+  s.open = true;
+  s.encoding = encoding; s.channels = channels; s.bits = stream_bits[encoding];
+  s.frame_bytes = stream_container[encoding] * channels;
+  s.up = up; s.down = down; s.hist = hist; s.taps = dt;
+  return 0;
+}
+int AudioFront::pool_close(int slot) {
+  const int one[1] = {slot};
+  TRY(pool_slots("pool_close: pool: ", 1, one, false));
+  pool[slot].open = false;
+  return 0;
+}
+// the slots of a batched call: a pool, n >= 1, every slot in range, open (and still taking
+// input) and named once
+int AudioFront::pool_slots(const std::string& who, int n, const int* slots, bool for_input) {
+  if (pool.empty()) return fail(-7, who + "no pool");
+  if (n < 1) return fail(-7, who + "n = " + std::to_string(n) + ", need at least one slot");
+  if (!slots) return fail(-1, who + "null slots");
+  std::vector<char> seen(pool.size(), 0);
+  for (int i = 0; i < n; ++i) {
+    const int s = slots[i];
+    if (s < 0 || s >= (int)pool.size())
+      return fail(-7, who + field_at("slots", i) + " = " + std::to_string(s) + " outside [0, " + std::to_string(pool.size()) + ")");
+    if (!pool[s].open) return fail(-7, who + field_at("slots", i) + " = " + std::to_string(s) + " is not open");
+    if (seen[s]) return fail(-7, who + field_at("slots", i) + " = " + std::to_string(s) + " is twice in the call");
+    seen[s] = 1;
+    if (for_input && pool[s].finished)
+      return fail(-7, who + field_at("slots", i) + " = " + std::to_string(s) + " is already finished, no more input is taken");
+  }
+  return 0;
+}
+// pinned host memory that grows by doubling
+int AudioFront::pool_pinned(char** p, size_t* cap, size_t bytes) {
+  if (bytes <= *cap) return 0;
+  if (*p) HIPCHK(hipHostFree(std::exchange(*p, nullptr)));
+  *cap = 0;
+  const size_t want = std::max<size_t>(bytes, 4096);
+  void* q = nullptr;
+  HIPCHK(hipHostMalloc(&q, want, hipHostMallocDefault));
+  *p = (char*)q;
+  *cap = want;
+  return 0;
+}
+// entry i: frames [frames_in, frames_in + n_frames[i]) of slot slots[i] arrive (data[i]), or its
+// recording ends (data null, totals[i] = all there will be).  The caller has checked everything.
+int AudioFront::pool_run(int n, const int* slots, const void* const* data, const int64_t* n_frames,
+                         const int64_t* totals, int64_t* n_out, const char* where) {
+  std::vector<size_t> offs(n, 0);
+  size_t bytes = 0;
+  int work = 0;
+  for (int i = 0; i < n; ++i) {
+    const PoolSlot& s = pool[slots[i]];
+    const int64_t nc = data ? n_frames[i] : 0;
+    if (!nc && totals[i] == s.samples_out) continue;  // nothing arrives, nothing becomes final
+    ++work;
+    offs[i] = bytes;
+    bytes += ((size_t)nc * s.frame_bytes + 8 + 15) & ~(size_t)15;  // 24-bit samples are read as aligned dwords
+  }
+  if (work) {
+    const size_t dbytes = (size_t)work * pool_stream_bytes();
+    TRY(pool_pinned(&pool_stage, &pool_stage_cap, bytes > pool_stage_cap ? std::max(bytes, 2 * pool_stage_cap) : bytes));
+    TRY(pool_pinned(&pool_hdesc, &pool_hdesc_cap, dbytes));
+    TRY(pool_pcm.reserve(std::max<size_t>(pool_stage_cap, 16)));
+    TRY(pool_desc.reserve(pool_hdesc_cap));
+    int64_t blocks = 0;
+    int j = 0;
+    for (int i = 0; i < n; ++i) {
+      const PoolSlot& s = pool[slots[i]];
+      const int64_t nc = data ? n_frames[i] : 0;
+      if (!nc && totals[i] == s.samples_out) continue;
+      if (nc) memcpy(pool_stage + offs[i], data[i], (size_t)nc * s.frame_bytes);
+      const int64_t len = s.samples_out - s.dropped;
+      blocks += pool_stream_fill(pool_hdesc, j++, blocks, pool_pcm.p + offs[i], s.encoding, s.frames_in, nc, s.channels,
+                                 s.bits, s.up, s.down, s.taps, s.hist_buf.p + (size_t)s.cur * s.hist,
+                                 s.hist_buf.p + (size_t)(1 - s.cur) * s.hist, s.hist,
+                                 pool_base(slots[i], s.buf) + len, s.samples_out, totals[i] - s.samples_out);
+    }
+    TRY(tm.mark(0, st));
+    if (data) HIPCHK(hipMemcpyAsync(pool_pcm.p, pool_stage, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pool_desc.p, pool_hdesc, dbytes, hipMemcpyHostToDevice, st));
+    TRY(tm.mark(1, st));
+    launch_pcm_resample_pool(pool_desc.p, work, blocks, st);
+    TRY(tm.mark(2, st));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(launch_status(where));
+    TRY(tm.charge(0, stats[WH_STAT_INGEST_COPY_MS]));
+    TRY(tm.charge(1, stats[WH_STAT_INGEST_KERNEL_MS]));
+  }
+  for (int i = 0; i < n; ++i) {
+    PoolSlot& s = pool[slots[i]];
+    const int64_t nc = data ? n_frames[i] : 0;
+    if (n_out) n_out[i] = totals[i] - s.samples_out;
+    if (!nc && totals[i] == s.samples_out) continue;
+    if (s.hist) s.cur = 1 - s.cur;
+    s.frames_in += nc;
+    s.samples_out = totals[i];
+  }
+  return 0;
+}
+int AudioFront::pool_append(int n, const int* slots, const void* const* data, const int64_t* n_frames, int64_t* n_out) {
+  const std::string who = "pool_append: pool: ";
+  TRY(pool_slots(who, n, slots, true));
+  if (!data) return fail(-1, who + "null data");
+  if (!n_frames) return fail(-1, who + "null n_frames");
+  std::vector<int64_t> totals(n);
+  int64_t blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const PoolSlot& s = pool[slots[i]];
+    const int64_t nc = n_frames[i];
+    if (nc < 0 || nc > ((int64_t)1 << 40) - s.frames_in)
+      return fail(-7, who + field_at("n_frames", i) + " = " + std::to_string(nc) + " out of range");
+    if (nc > 0 && !data[i]) return fail(-1, who + "null " + field_at("data", i) + " with n_frames > 0");
+    totals[i] = stream_emitted(s.frames_in + nc, s.up, s.down, false);
+    const int64_t after = totals[i] - s.dropped;
+    if (after > pool_samples)
+      return fail(-7, who + field_at("n_frames", i) + " = " + std::to_string(nc) + " takes slot " + std::to_string(slots[i]) +
+                          " to " + std::to_string(after) + " resident samples, past its capacity of " +
+                          std::to_string(pool_samples) + ": the caller must trim first");
+    blocks += (totals[i] - s.samples_out + 255) / 256 + 1;
+  }
+  if (blocks > 0x7fffffff) return fail(-7, who + "too many samples for one call");
+  return pool_run(n, slots, data, n_frames, totals.data(), n_out, "pool_append");
+}
+int AudioFront::pool_finish(int n, const int* slots, int64_t* n_out) {
+  const std::string who = "pool_finish: pool: ";
+  TRY(pool_slots(who, n, slots, false));
+  std::vector<int64_t> totals(n);
+  for (int i = 0; i < n; ++i) {
+    const PoolSlot& s = pool[slots[i]];
+    totals[i] = s.finished ? s.samples_out : stream_emitted(s.frames_in, s.up, s.down, true);
+    if (totals[i] - s.dropped > pool_samples)
+      return fail(-7, who + field_at("slots", i) + " = " + std::to_string(slots[i]) + " would hold " +
+                          std::to_string(totals[i] - s.dropped) + " resident samples, past its capacity of " +
+                          std::to_string(pool_samples) + ": the caller must trim first");
+  }
+  TRY(pool_run(n, slots, nullptr, nullptr, totals.data(), n_out, "pool_finish"));
+  for (int i = 0; i < n; ++i) pool[slots[i]].finished = true;
+  return 0;
+}
+int AudioFront::pool_trim(int n, const int* slots, const int64_t* n_drop) {
+  const std::string who = "pool_trim: pool: ";
+  TRY(pool_slots(who, n, slots, false));
+  if (!n_drop) return fail(-1, who + "null n_drop");
+  int moves = 0;
+  int64_t longest = 0;
+  for (int i = 0; i < n; ++i) {
+    const PoolSlot& s = pool[slots[i]];
+    const int64_t len = s.samples_out - s.dropped;
+    if (n_drop[i] < 0 || n_drop[i] > len)
+      return fail(-7, who + field_at("n_drop", i) + " = " + std::to_string(n_drop[i]) + " outside [0, " + std::to_string(len) + "]");
+    if (n_drop[i] && len - n_drop[i]) ++moves, longest = std::max(longest, len - n_drop[i]);
+  }
+  if (moves) {
+    const size_t dbytes = (size_t)moves * sizeof(PoolMove);
+    TRY(pool_pinned(&pool_hdesc, &pool_hdesc_cap, dbytes));
+    TRY(pool_desc.reserve(pool_hdesc_cap));
+    PoolMove* mv = (PoolMove*)pool_hdesc;
+    for (int i = 0, j = 0; i < n; ++i) {
+      const PoolSlot& s = pool[slots[i]];
+      const int64_t rest = s.samples_out - s.dropped - n_drop[i];
+      if (n_drop[i] && rest) mv[j++] = PoolMove{pool_base(slots[i], s.buf) + n_drop[i], pool_base(slots[i], 1 - s.buf), rest};
+    }
+    TRY(tm.mark(0, st));
+    HIPCHK(hipMemcpyAsync(pool_desc.p, pool_hdesc, dbytes, hipMemcpyHostToDevice, st));
+    TRY(tm.mark(1, st));
+    launch_pool_move((const PoolMove*)pool_desc.p, moves, longest, st);
+    TRY(tm.mark(2, st));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(launch_status("pool_trim"));
+    TRY(tm.charge(0, stats[WH_STAT_INGEST_COPY_MS]));
+    TRY(tm.charge(1, stats[WH_STAT_INGEST_KERNEL_MS]));
+  }
+  for (int i = 0; i < n; ++i) {
+    PoolSlot& s = pool[slots[i]];
+    if (n_drop[i] && s.samples_out - s.dropped - n_drop[i]) s.buf = 1 - s.buf;
+    s.dropped += n_drop[i];
+  }
+  return 0;
+}
+int AudioFront::pool_info(int slot, int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped, int* finished) {
+  const int one[1] = {slot};
+  TRY(pool_slots("pool_info: pool: ", 1, one, false));
+  const PoolSlot& s = pool[slot];
+  if (frames_in) *frames_in = s.frames_in;
+  if (samples_out) *samples_out = s.samples_out;
+  if (samples_dropped) *samples_dropped = s.dropped;
+  if (finished) *finished = s.finished ? 1 : 0;
+  return 0;
+}
+int AudioFront::pool_read(int slot, float* out, int64_t offset, int64_t n) {
+  const std::string who = "pool_read: pool: ";
+  const int one[1] = {slot};
+  TRY(pool_slots(who, 1, one, false));
+  if (!out) return fail(-1, who + "null out");
+  const PoolSlot& s = pool[slot];
+  const int64_t len = s.samples_out - s.dropped;
+  if (offset < 0 || n < 0 || offset > len || n > len - offset)
+    return fail(-7, who + "[" + std::to_string(offset) + ", " + std::to_string(offset) + " + " + std::to_string(n) +
+                        ") is outside the " + std::to_string(len) + " resident samples of slot " + std::to_string(slot));
+  if (n) HIPCHK(hipMemcpy(out, pool_base(slot, s.buf) + offset, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+// wh_log_mel_batch with the files taken from the slots' buffers: the same descriptors, the same
+// launch_mel_seg, only audio_off points into pool_audio.  Writes the context mel alone.
+int AudioFront::pool_log_mel(int n, const int* slots, int64_t pad, int n_mels, int64_t* frame_base) {
+  const std::string who = "pool_log_mel: pool: ";
+  TRY(pool_slots(who, n, slots, false));
+  if (!frame_base) return fail(-1, who + "null frame_base");
+  if (pad < 0) return fail(-7, who + "negative padding");
+  if (!h_filters.count(n_mels)) return fail(-7, who + "mel filters for n_mels=" + std::to_string(n_mels) + " not set");
+  std::vector<MelFile> files(n);
+  int64_t frames = 0, blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const PoolSlot& s = pool[slots[i]];
+    const int64_t len = s.samples_out - s.dropped;
+    if (len < 1) return fail(-7, who + field_at("slots", i) + " = " + std::to_string(slots[i]) + " has no samples");
+    if (len + pad <= 200) return fail(-7, who + field_at("slots", i) + " = " + std::to_string(slots[i]) + " too short for reflect padding");
+    MelFile& f = files[i];
+    f.audio_off = (int64_t)(pool_base(slots[i], s.buf) - pool_audio.p);
+    f.n_real = len;
+    f.n_padded = len + pad;
+    f.nframes = (len + pad) / 160;
+    f.frame_base = frames;
+    f.block_base = blocks;
+    frames += f.nframes;
+    blocks += mel_blocks(f.nframes);
+  }
+  if (blocks > 0x7fffffff) return fail(-7, who + "too many frames for one call");
+  TRY(d_mel.reserve((size_t)n_mels * frames * 4));
+  const size_t room = std::max<size_t>(n, 64);
+  TRY(mel_files.reserve(room * sizeof(MelFile)));
+  TRY(gmax_files.reserve(room * 4));
+  mel_batch_files = 0;
+  TRY(tm.mark(0, st));
+  HIPCHK(hipMemcpyAsync(mel_files.p, files.data(), n * sizeof(MelFile), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(gmax_files.p, 0, (size_t)n * 4, st));
+  launch_mel_seg(pool_audio.p, mel_files.p, n, blocks, d_filters[n_mels], n_mels, d_mel.p, frames, gmax_files.p, st);
+  TRY(tm.finish(st, stats[WH_STAT_MEL_MS]));
+  mel_is(frames, 0, n_mels, n);
+  for (int i = 0; i < n; ++i) frame_base[i] = files[i].frame_base;
+  frame_base[n] = frames;
   return 0;
 }
 

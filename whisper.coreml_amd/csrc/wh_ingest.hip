@@ -221,14 +221,17 @@ __device__ inline double stream_frame(const StreamArgs& a, int64_t m) {
   return j >= 0 ? a.hist_old[j] : 0.0;
 }
 
+// what workgroup `block` of a stream's launch does: blocks [0, ceil(n_emit / 256)) own 256
+// outputs each, the block behind them writes the next history.  k_pcm_resample_stream and
+// k_pcm_resample_pool both run this body, so a pool slot's samples are the single stream's.
 template <typename R>
-__global__ __launch_bounds__(256) void k_pcm_resample_stream(StreamArgs a) {
+__device__ inline void stream_block(const StreamArgs& a, int64_t block) {
   const int64_t out_blocks = (a.n_emit + 255) / 256;
-  if ((int64_t)blockIdx.x >= out_blocks) {
+  if (block >= out_blocks) {
     for (int j = threadIdx.x; j < a.hist; j += 256) a.hist_new[j] = stream_frame<R>(a, a.n0 + a.nc - a.hist + j);
     return;
   }
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t i = block * 256 + threadIdx.x;
   if (i >= a.n_emit) return;
   const int64_t k = a.k0 + i;
   double y;
@@ -247,16 +250,29 @@ __global__ __launch_bounds__(256) void k_pcm_resample_stream(StreamArgs a) {
   a.out[i] = (float)r * (1.0f / 32768.0f);
 }
 
-void launch_pcm_resample_stream(const void* pcm, int encoding, int64_t n0, int64_t nc, int channels, int bits, int up,
-                                int down, const double* taps, const double* hist_old, double* hist_new, int hist,
-                                float* out, int64_t k0, int64_t n_emit, hipStream_t st) {
-  if (n_emit < 1 && hist < 1) return;
+template <typename R>
+__global__ __launch_bounds__(256) void k_pcm_resample_stream(StreamArgs a) {
+  stream_block<R>(a, (int64_t)blockIdx.x);
+}
+
+// the arguments of one stream's chunk, for its own launch or as its descriptor in a pool launch
+static StreamArgs stream_args(const void* pcm, int64_t n0, int64_t nc, int channels, int bits, int up, int down,
+                              const double* taps, const double* hist_old, double* hist_new, int hist, float* out,
+                              int64_t k0, int64_t n_emit) {
   StreamArgs a;
   a.pcm = pcm; a.n0 = n0; a.nc = nc; a.k0 = k0; a.n_emit = n_emit; a.channels = channels; a.up = up; a.down = down;
   a.half = taps ? 10 * (up > down ? up : down) : 0;
   a.hist = hist;
   a.scale = ldexp(1.0, -(bits - 1));
   a.taps = taps; a.hist_old = hist_old; a.hist_new = hist_new; a.out = out;
+  return a;
+}
+
+void launch_pcm_resample_stream(const void* pcm, int encoding, int64_t n0, int64_t nc, int channels, int bits, int up,
+                                int down, const double* taps, const double* hist_old, double* hist_new, int hist,
+                                float* out, int64_t k0, int64_t n_emit, hipStream_t st) {
+  if (n_emit < 1 && hist < 1) return;
+  const StreamArgs a = stream_args(pcm, n0, nc, channels, bits, up, down, taps, hist_old, hist_new, hist, out, k0, n_emit);
   const unsigned grid = (unsigned)((n_emit + 255) / 256) + (hist > 0 ? 1 : 0);
 #define LAUNCH_STREAM_AS(R_) k_pcm_resample_stream<R_><<<grid, 256, 0, st>>>(a), wh_launched("k_pcm_resample_stream")
   switch (encoding) {
@@ -271,6 +287,75 @@ void launch_pcm_resample_stream(const void* pcm, int encoding, int64_t n0, int64
     default: break; /* the callers pass one of the eight */
   }
 #undef LAUNCH_STREAM_AS
+}
+
+// ---------------------------------------------------------------- PCM ingest, many streams per launch
+// k_pcm_resample_stream for the stream pool (wh_pool_append, wh_pool_finish): one grid covers a
+// chunk of each of n streams.  Stream s of the call has a descriptor: the StreamArgs its own
+// launch would get, its encoding and the index of its first workgroup; it owns the workgroups
+// [block0[s], block0[s + 1]), ceil(n_emit / 256) + (hist > 0) of them, never none (the host leaves
+// out a stream that has no work).  A workgroup finds its stream by a binary search of the
+// first-workgroup indices (log2(n) block-uniform loads of a table that stays in the scalar
+// cache; a per-block map would cost a host write and a copied word per workgroup, and a tick of
+// 20 ms packets has one or two workgroups per stream anyway), copies the descriptor and runs
+// stream_block through a block-uniform switch on the encoding.
+struct PoolStream {
+  StreamArgs a;
+  int encoding;  // WH_WAV_*
+  int block0;
+};
+
+__global__ __launch_bounds__(256) void k_pcm_resample_pool(const PoolStream* __restrict__ d, int n) {
+  const int b = (int)blockIdx.x;
+  int lo = 0, hi = n - 1;  // the last stream whose first workgroup is at or before b
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (d[mid].block0 <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const StreamArgs a = d[lo].a;
+  const int64_t block = b - d[lo].block0;
+  switch (d[lo].encoding) {
+    case WH_WAV_U8: stream_block<ReadU8>(a, block); break;
+    case WH_WAV_S16: stream_block<ReadS16>(a, block); break;
+    case WH_WAV_S24: stream_block<ReadS24>(a, block); break;
+    case WH_WAV_S32: stream_block<ReadS32>(a, block); break;
+    case WH_WAV_F32: stream_block<ReadF32>(a, block); break;
+    case WH_WAV_F64: stream_block<ReadF64>(a, block); break;
+    case WH_WAV_ALAW: stream_block<ReadAlaw>(a, block); break;
+    case WH_WAV_ULAW: stream_block<ReadUlaw>(a, block); break;
+    default: break; /* the host passes one of the eight */
+  }
+}
+
+size_t pool_stream_bytes() { return sizeof(PoolStream); }
+
+int64_t pool_stream_fill(void* desc, int i, int64_t block0, const void* pcm, int encoding, int64_t n0, int64_t nc,
+                         int channels, int bits, int up, int down, const double* taps, const double* hist_old,
+                         double* hist_new, int hist, float* out, int64_t k0, int64_t n_emit) {
+  PoolStream& p = ((PoolStream*)desc)[i];
+  p.a = stream_args(pcm, n0, nc, channels, bits, up, down, taps, hist_old, hist_new, hist, out, k0, n_emit);
+  p.encoding = encoding;
+  p.block0 = (int)block0;
+  return (n_emit + 255) / 256 + (hist > 0 ? 1 : 0);
+}
+
+void launch_pcm_resample_pool(const void* desc, int n, int64_t n_blocks, hipStream_t st) {
+  if (n < 1 || n_blocks < 1) return;
+  k_pcm_resample_pool<<<(unsigned)n_blocks, 256, 0, st>>>((const PoolStream*)desc, n), wh_launched("k_pcm_resample_pool");
+}
+
+// wh_pool_trim: move i copies n floats from src to dst, which never overlap (a slot's two
+// buffers).  blockIdx.y is the move, the workgroups of a row stride over its floats.
+__global__ __launch_bounds__(256) void k_pool_move(const PoolMove* __restrict__ mv) {
+  const PoolMove m = mv[blockIdx.y];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m.n; i += (int64_t)gridDim.x * 256) m.dst[i] = m.src[i];
+}
+
+void launch_pool_move(const PoolMove* moves, int n, int64_t longest, hipStream_t st) {
+  if (n < 1 || longest < 1) return;
+  const int64_t want = (longest + 1023) / 1024;  // four floats per thread, at most 64 workgroups per move
+  k_pool_move<<<dim3((unsigned)(want < 64 ? want : 64), (unsigned)n), 256, 0, st>>>(moves), wh_launched("k_pool_move");
 }
 
 // ---------------------------------------------------------------- PCM ingest, channels apart

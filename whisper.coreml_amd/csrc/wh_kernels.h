@@ -113,6 +113,23 @@ void launch_pcm_resample(const void* pcm, int encoding, int64_t n_frames, int ch
 void launch_pcm_resample_stream(const void* pcm, int encoding, int64_t n0, int64_t nc, int channels, int bits, int up,
                                 int down, const double* taps, const double* hist_old, double* hist_new, int hist,
                                 float* out, int64_t k0, int64_t n_emit, hipStream_t st);
+// wh_pool_append / wh_pool_finish's kernel: launch_pcm_resample_stream for n streams in one grid.
+// The host fills descriptor i of a pinned array (pool_stream_bytes() each) with the arguments
+// that launch would take and the stream's first workgroup; pool_stream_fill returns the
+// workgroups the stream takes, which must not be 0 (a stream without work is left out).  The
+// device copy of the array is what the launch reads.
+size_t pool_stream_bytes();
+int64_t pool_stream_fill(void* desc, int i, int64_t block0, const void* pcm, int encoding, int64_t n0, int64_t nc,
+                         int channels, int bits, int up, int down, const double* taps, const double* hist_old,
+                         double* hist_new, int hist, float* out, int64_t k0, int64_t n_emit);
+void launch_pcm_resample_pool(const void* desc, int n, int64_t n_blocks, hipStream_t st);
+// wh_pool_trim's kernel: n moves of floats between buffers that do not overlap, one launch
+struct PoolMove {
+  const float* src;
+  float* dst;
+  int64_t n;
+};
+void launch_pool_move(const PoolMove* moves, int n, int64_t longest, hipStream_t st);
 // wh_*_ingest_split's kernel: the same input, but no mix: selected channel s (select[s], n_select
 // distinct ids in [0, channels), at most 256) becomes a waveform of its own, n_out samples at
 // out + s * n_out, with the arithmetic the kernel above has for a mono file of that channel.

@@ -1920,6 +1920,28 @@ int wh_stream_trim(wh_ctx* ctx, int64_t n_drop) { CTXCALL(ctx->audio.stream_trim
 int wh_stream_info(wh_ctx* ctx, int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped, int* finished) {
   CTXCALL(ctx->audio.stream_info(frames_in, samples_out, samples_dropped, finished));
 }
+int wh_pool_create(wh_ctx* ctx, int n_slots, int64_t slot_samples) { CTXCALL(ctx->audio.pool_create(n_slots, slot_samples)); }
+int wh_pool_destroy(wh_ctx* ctx) { CTXCALL(ctx->audio.pool_destroy()); }
+int wh_pool_open(wh_ctx* ctx, int slot, int encoding, int channels, int up, int down, const double* taps, int n_taps) {
+  CTXCALL(ctx->audio.pool_open(slot, encoding, channels, up, down, taps, n_taps));
+}
+int wh_pool_close(wh_ctx* ctx, int slot) { CTXCALL(ctx->audio.pool_close(slot)); }
+int wh_pool_append(wh_ctx* ctx, int n, const int* slots, const void* const* data, const int64_t* n_frames,
+                   int64_t* n_out) {
+  CTXCALL(ctx->audio.pool_append(n, slots, data, n_frames, n_out));
+}
+int wh_pool_finish(wh_ctx* ctx, int n, const int* slots, int64_t* n_out) { CTXCALL(ctx->audio.pool_finish(n, slots, n_out)); }
+int wh_pool_trim(wh_ctx* ctx, int n, const int* slots, const int64_t* n_drop) { CTXCALL(ctx->audio.pool_trim(n, slots, n_drop)); }
+int wh_pool_info(wh_ctx* ctx, int slot, int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped,
+                 int* finished) {
+  CTXCALL(ctx->audio.pool_info(slot, frames_in, samples_out, samples_dropped, finished));
+}
+int wh_pool_read(wh_ctx* ctx, int slot, float* out, int64_t offset, int64_t n) {
+  CTXCALL(ctx->audio.pool_read(slot, out, offset, n));
+}
+int wh_pool_log_mel(wh_ctx* ctx, int n, const int* slots, int64_t padding, int n_mels, int64_t* frame_base) {
+  CTXCALL(ctx->audio.pool_log_mel(n, slots, padding, n_mels, frame_base));
+}
 int wh_speech_spans(wh_ctx* ctx, const wh_vad_opts* opts, int n_files, int32_t* spans, int cap, int32_t* n_spans,
                     uint64_t* thresholds) {
   CTXCALL(ctx->audio.speech_spans(opts, n_files, spans, cap, n_spans, thresholds));

@@ -10,6 +10,16 @@
    with the tokens each update decoded, because the synthetic weights never choose
    end-of-text: every decode runs to its token limit, which real speech does not.
 
+With ``--pool`` the same two questions for the stream pool (``wh_pool_*``, ``StreamingPool``)
+against the single-stream path, in one process:
+
+3. Tick: S mu-law 8 kHz packets of 20 ms, one per stream, through one ``pool_append``, against
+   S ``stream_append`` calls of the same packets (S = 1, 16, 64, 256).
+4. Round: the wall time of one ``StreamingPool.feed`` in which S streams are due (one second of
+   audio each, so the feed is one append, one batched decode, one trim), against the sum of the
+   ``wall_ms`` of the same updates of S lone ``StreamingTranscriber``s run one after another on
+   the same model (S up to ``--windows``).
+
 One JSON line per measurement.
 """
 import argparse
@@ -64,12 +74,95 @@ def update_cost(model, name, seconds, **decode):
                 buffer_s_max=round(max(u.span[1] - u.span[0] for u in ups) / 16000, 2))
 
 
+def pool_tick_cost(n_streams, ticks=200):
+    """One tick of ``n_streams`` 20 ms mu-law packets: one pool_append against that many stream_appends."""
+    from whisper.audio import WAV_ENCODINGS, _mel_context
+    ctx = _mel_context(0)
+    frames, enc = 160, WAV_ENCODINGS.index("ulaw")
+    data = np.random.default_rng(0).integers(0, 256, (ticks, n_streams, frames), dtype=np.uint8)
+    slots, counts = list(range(n_streams)), [frames] * n_streams
+    ctx.pool_create(n_streams, 2 * frames * ticks + 64)
+    for s in slots:
+        ctx.pool_open(s, enc, 1, 8000)
+    ctx.stream_begin(enc, 1, 8000, reserve=2 * frames * ticks * n_streams + 64)
+    # first-touch costs (allocations, the filter upload) stay out
+    ctx.pool_append(slots, list(data[0]), counts)
+    for s in slots:
+        ctx.stream_append(data[0][s], frames)
+    out = dict(measure="pool_tick", streams=n_streams, packet_ms=20, ticks=ticks - 1)
+    for name in ("pool", "single"):
+        before, wall = ctx.stats(), []
+        for k in range(1, ticks):
+            packets = list(data[k])
+            t = time.perf_counter()
+            if name == "pool":
+                ctx.pool_append(slots, packets, counts)
+            else:
+                for p in packets:
+                    ctx.stream_append(p, frames)
+            wall.append((time.perf_counter() - t) * 1e3)
+        after = ctx.stats()
+        out[name] = dict(copy_ms=round((after["ingest_copy_ms"] - before["ingest_copy_ms"]) / (ticks - 1), 4),
+                         kernel_ms=round((after["ingest_kernel_ms"] - before["ingest_kernel_ms"]) / (ticks - 1), 4),
+                         wall_ms_p50=round(float(np.percentile(wall, 50)), 4),
+                         wall_ms_p95=round(float(np.percentile(wall, 95)), 4))
+    ctx.pool_destroy()
+    return out
+
+
+def pool_round_cost(model, name, n_streams, seconds, **decode):
+    """One round with ``n_streams`` due streams against that many lone updates of the same buffers."""
+    import whisper
+    from whisper import synthetic as S
+    pcm = [np.clip(np.round(S.synthetic_audio(seconds, seed=5 + k) * 32768.0), -32768, 32767).astype(np.int16)
+           for k in range(n_streams)]
+    rounds = int(seconds)
+    lone = np.zeros(rounds)
+    tokens = []
+    for k in range(n_streams):
+        t = whisper.StreamingTranscriber(model, 16000, "s16", 1, language="en", min_chunk=1.0, temperature=0.0, **decode)
+        ups = t.feed(pcm[k][:rounds * 16000])
+        lone += [u.wall_ms for u in ups]
+        tokens += [sum(len(s["tokens"]) for s in u.result["segments"]) for u in ups[1:]]
+    wall = []
+    with whisper.StreamingPool(model, slots=n_streams, temperature=0.0, **decode) as pool:
+        handles = [pool.open(16000, "s16", 1, language="en", min_chunk=1.0) for _ in range(n_streams)]
+        for r in range(rounds):
+            packets = {h: pcm[k][r * 16000:(r + 1) * 16000] for k, h in enumerate(handles)}
+            t = time.perf_counter()
+            ups = pool.feed(packets)
+            wall.append((time.perf_counter() - t) * 1e3)
+            assert all(len(u) == 1 for u in ups.values()) and pool.rounds[-1] == handles
+    # the first round captures the step graphs
+    return dict(measure="pool_round", model=name, decode=decode or dict(greedy=True), streams=n_streams,
+                rounds=rounds - 1, pool_ms_p50=round(float(np.percentile(wall[1:], 50)), 1),
+                pool_ms_max=round(float(max(wall[1:])), 1), lone_sum_ms_p50=round(float(np.percentile(lone[1:], 50)), 1),
+                lone_sum_ms_max=round(float(max(lone[1:])), 1), tokens_per_update_p50=int(np.percentile(tokens, 50)),
+                tokens_per_update_max=int(max(tokens)))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--models", default="turbo,large-v3")
+    ap.add_argument("--models", default=None, help="default: turbo,large-v3 (turbo with --pool)")
     ap.add_argument("--seconds", type=float, default=12.0)
+    ap.add_argument("--pool", action="store_true", help="the stream pool against the single-stream path")
+    ap.add_argument("--windows", type=int, default=8, help="--pool: max_windows of the model, the most streams per round")
     args = ap.parse_args()
     import whisper
+    if args.pool:
+        for n in (1, 16, 64, 256):
+            print(json.dumps(pool_tick_cost(n)), flush=True)
+        for name in [m for m in (args.models or "turbo").split(",") if m]:
+            model = whisper.load_model(name, device=0, dtype="fp16", max_windows=args.windows, max_group=5,
+                                       synthetic=True)
+            for decode in ({}, dict(beam_size=5)):
+                n = 1
+                while n <= args.windows:
+                    print(json.dumps(pool_round_cost(model, name, n, min(args.seconds, 6.0), **decode)), flush=True)
+                    n *= 2
+            model.close()
+        return
+    args.models = args.models or "turbo,large-v3"
     for rate, enc in ((8000, "ulaw"), (48000, "s16")):
         print(json.dumps(append_cost(rate, enc)), flush=True)
     for name in [m for m in args.models.split(",") if m]:

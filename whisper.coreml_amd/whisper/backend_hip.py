@@ -12,7 +12,7 @@ Differences from the reference shim, on purpose:
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
-from typing import NamedTuple, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -138,6 +138,16 @@ _EXPORTS = {
     "wh_stream_trim": (c_int, [c_void_p, c_int64]),
     "wh_stream_info": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int)]),
     "wh_stream_emitted": (c_int64, [c_int64, c_int, c_int, c_int]),
+    "wh_pool_create": (c_int, [c_void_p, c_int, c_int64]),
+    "wh_pool_destroy": (c_int, [c_void_p]),
+    "wh_pool_open": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int]),
+    "wh_pool_close": (c_int, [c_void_p, c_int]),
+    "wh_pool_append": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wh_pool_finish": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "wh_pool_trim": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "wh_pool_info": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int)]),
+    "wh_pool_read": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64]),
+    "wh_pool_log_mel": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p]),
 }
 N_STATS = 16  # WH_N_STATS
 FLAC_PATHS = ("device", "host")
@@ -488,6 +498,79 @@ class HipContext:
         self._check(self.lib.wh_stream_info(self.h, ctypes.byref(fi), ctypes.byref(so), ctypes.byref(sd),
                                             ctypes.byref(fin)), "wh_stream_info")
         return fi.value, so.value, sd.value, bool(fin.value)
+
+    # -- a pool of streams (include/whisper_hip.h): many live recordings, fed and decoded together
+    def pool_create(self, n_slots: int, slot_samples: int):
+        """Give the context ``n_slots`` stream slots of at most ``slot_samples`` 16 kHz samples."""
+        self._check(self.lib.wh_pool_create(self.h, int(n_slots), int(slot_samples)), "wh_pool_create")
+
+    def pool_destroy(self):
+        self._check(self.lib.wh_pool_destroy(self.h), "wh_pool_destroy")
+
+    def pool_open(self, slot: int, encoding: int, channels: int, rate: int):
+        """Open ``slot`` for raw frames in ``encoding`` (a WH_WAV_* code) at ``rate`` Hz."""
+        from .audio import resample_filter
+        up, down, taps = resample_filter(int(rate))
+        self._check(self.lib.wh_pool_open(self.h, int(slot), int(encoding), int(channels), up, down,
+                                          None if taps is None else _ptr(taps),
+                                          0 if taps is None else taps.shape[0]), "wh_pool_open")
+
+    def pool_close(self, slot: int):
+        self._check(self.lib.wh_pool_close(self.h, int(slot)), "wh_pool_close")
+
+    def pool_append(self, slots: Sequence[int], packets: Sequence, n_frames: Sequence[int]) -> List[int]:
+        """One packet per slot in one call: ``packets[i]`` (a contiguous uint8 array, or None with
+        0 frames) holds ``n_frames[i]`` frames for ``slots[i]``.  Returns the samples each slot
+        emitted.  One upload, one launch and one synchronisation for the whole call."""
+        n = len(slots)
+        sl = np.asarray(list(slots), dtype=np.int32).reshape(-1)
+        nf = np.asarray(list(n_frames), dtype=np.int64).reshape(-1)
+        if len(packets) != n or nf.shape[0] != n:
+            raise ValueError(f"pool_append: {n} slots, {len(packets)} packets, {nf.shape[0]} frame counts")
+        ptrs = (c_void_p * max(n, 1))(*[None if p is None else p.ctypes.data for p in packets])
+        n_out = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self.lib.wh_pool_append(self.h, n, _ptr(sl) if n else None, ptrs, _ptr(nf) if n else None,
+                                            _ptr(n_out)), "wh_pool_append")
+        return [int(x) for x in n_out[:n]]
+
+    def pool_finish(self, slots: Sequence[int]) -> List[int]:
+        """End the input of ``slots``: the samples each resampler still held back; how many each."""
+        sl = np.asarray(list(slots), dtype=np.int32).reshape(-1)
+        n_out = np.zeros(max(len(sl), 1), dtype=np.int64)
+        self._check(self.lib.wh_pool_finish(self.h, len(sl), _ptr(sl) if len(sl) else None, _ptr(n_out)),
+                    "wh_pool_finish")
+        return [int(x) for x in n_out[:len(sl)]]
+
+    def pool_trim(self, slots: Sequence[int], n_drop: Sequence[int]):
+        """Drop the first ``n_drop[i]`` resident samples of ``slots[i]``, all in one launch."""
+        sl = np.asarray(list(slots), dtype=np.int32).reshape(-1)
+        nd = np.asarray(list(n_drop), dtype=np.int64).reshape(-1)
+        if nd.shape[0] != sl.shape[0]:
+            raise ValueError(f"pool_trim: {sl.shape[0]} slots, {nd.shape[0]} counts")
+        self._check(self.lib.wh_pool_trim(self.h, len(sl), _ptr(sl) if len(sl) else None,
+                                          _ptr(nd) if len(sl) else None), "wh_pool_trim")
+
+    def pool_info(self, slot: int):
+        """(frames appended, samples emitted, samples dropped, finished) of an open slot."""
+        fi, so, sd, fin = c_int64(), c_int64(), c_int64(), c_int()
+        self._check(self.lib.wh_pool_info(self.h, int(slot), ctypes.byref(fi), ctypes.byref(so), ctypes.byref(sd),
+                                          ctypes.byref(fin)), "wh_pool_info")
+        return fi.value, so.value, sd.value, bool(fin.value)
+
+    def pool_read(self, slot: int, offset: int, n: int) -> np.ndarray:
+        """Resident samples [offset, offset + n) of ``slot`` as a host array."""
+        out = np.empty(max(int(n), 0), dtype=np.float32)
+        self._check(self.lib.wh_pool_read(self.h, int(slot), _ptr(out), int(offset), int(n)), "wh_pool_read")
+        return out
+
+    def pool_log_mel(self, slots: Sequence[int], n_mels: int, padding: int = 0) -> np.ndarray:
+        """``log_mel_batch`` with the files taken from the slots' resident buffers, in the given
+        order.  Returns the frame bases (int64, ``len(slots) + 1``)."""
+        sl = np.asarray(list(slots), dtype=np.int32).reshape(-1)
+        base = np.zeros(len(sl) + 1, dtype=np.int64)
+        self._check(self.lib.wh_pool_log_mel(self.h, len(sl), _ptr(sl) if len(sl) else None, int(padding), n_mels,
+                                             _ptr(base)), "wh_pool_log_mel")
+        return base
 
     def flac_decode_device(self, data: bytes):
         """``decode_flac`` on the device (wh_flac_decode_device): (samples int32

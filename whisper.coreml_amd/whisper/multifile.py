@@ -229,6 +229,99 @@ def _is_number(x) -> bool:
     return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
 
 
+def _transcribe_lanes(model: "Whisper", lengths: Sequence[int], prepare_group: Callable[[List[int]], Sequence[int]],
+                      languages: List[Optional[str]], prompts: Sequence, clips: Sequence, *,
+                      units: Optional[Sequence[int]] = None, spans: Optional[dict] = None,
+                      mel_budget_frames: int = DEFAULT_MEL_BUDGET_FRAMES, verbose: Optional[bool] = None,
+                      temperature, thresholds, condition_on_previous_text: bool, carry_initial_prompt: bool,
+                      word_timestamps: bool, prepend_punctuations: str, append_punctuations: str,
+                      hallucination_silence_threshold: Optional[float], decode_options: dict) -> List[dict]:
+    """What follows the ingest: ``lengths[i]`` samples of audio i (one lane each) are somewhere
+    ``prepare_group(indices)`` can reach; it computes the log-mel of those audios into the context
+    mel and returns their frame bases.  Then, per group: language detection for the lanes whose
+    ``languages[i]`` is None (filled in here), the plans, ``run_files`` and the per-lane result
+    dicts.  ``prompts`` and ``clips`` are per lane.  ``spans`` (skip_silence): the dict that
+    ``prepare_group`` fills with each audio's speech spans in frames, which become its clips.
+    ``transcribe_batch`` (the files of the resident segments) and ``StreamingPool`` (the buffers of
+    its slots) both run this."""
+    ctx = model.ctx
+    n = len(lengths)
+    probe = get_tokenizer(model.is_multilingual, num_languages=model.num_languages) if model.is_multilingual else None
+    clips_of: dict = {}    # skip_silence: the clips the spans give (clamped to the file's whole frames)
+
+    def file_clips(k: int, i: int, bases):
+        if spans is not None and i not in clips_of:
+            clips_of[i] = clamp_clips(spans[i], int(bases[k + 1] - bases[k]) - N_FRAMES)
+        return clips_of.get(i)
+
+    def detect(group: List[int], bases) -> None:
+        """Language of every file of the group that has none: the first window of up to
+        max_windows files per encode, one <|startoftranscript|> pass per slot."""
+        # with skip_silence the probe window starts at the first span; a file without one is not probed
+        first = {k: (file_clips(k, i, bases) or [(0, 0)])[0][0] for k, i in enumerate(group)}
+        todo = [k for k, i in enumerate(group) if languages[i] is None and file_clips(k, i, bases) != []]
+        for c0 in range(0, len(todo), ctx.max_windows):
+            chunk = todo[c0:c0 + ctx.max_windows]
+            seeks = [int(bases[k]) + first[k] for k in chunk]
+            sizes = [min(N_FRAMES, int(bases[k + 1] - bases[k]) - first[k]) for k in chunk]
+            ctx.encode(seeks, sizes)
+            model._last_windows = (seeks, sizes)
+            for slot, k in enumerate(chunk):
+                _, probs = language_probs(model, slot, probe)
+                languages[group[k]] = max(probs, key=probs.get)
+                if verbose is not None:
+                    print(f"[{group[k]}] Detected language: {LANGUAGES[languages[group[k]]].title()}")
+
+    plans = {}
+    # one sampling seed per file (per channel of a split file), drawn in input order as a loop of
+    # transcribe() calls over the files and the channel waveforms draws them
+    file_seeds = [next_seed() for _ in range(n)]
+
+    def make_lanes(group: List[int], bases) -> List[_Lane]:
+        if not model.is_multilingual:
+            for i in group:
+                languages[i] = languages[i] or "en"
+        else:
+            detect(group, bases)
+        lanes = []
+        for k, i in enumerate(group):
+            content_frames = int(bases[k + 1] - bases[k]) - N_FRAMES
+            clips_i = file_clips(k, i, bases)
+            if clips_i == []:
+                clips_i = [(0, 0)]  # no speech: a clip that offers no window, so the file takes no lane
+            opts = dict(decode_options, language=languages[i])
+            plan = _plan_file(model, content_frames, languages[i], opts, temperature=temperature,
+                              thresholds=thresholds, initial_prompt=prompts[i], word_timestamps=word_timestamps,
+                              prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
+                              clip_timestamps=clips[i],
+                              hallucination_silence_threshold=hallucination_silence_threshold, seek_clips=clips_i)
+            plans[i] = plan
+            tokenizer, seek_clips, prompt_tokens, st = plan
+            lanes.append(_Lane(model.dims.n_text_ctx, seek_clips, prompt_tokens, condition_on_previous_text,
+                               carry_initial_prompt, st, base=int(bases[k]), file_seed=file_seeds[i]))
+        return lanes
+
+    decode_round, align_round = _device_round(model, per_file=True)
+    lanes = run_files(lengths, max_windows=ctx.max_windows, mel_budget_frames=mel_budget_frames,
+                      prepare_group=prepare_group, make_lanes=make_lanes, decode_round=decode_round,
+                      align_round=align_round if word_timestamps else None, units=units)
+    results = []
+    for i, lane in enumerate(lanes):
+        tokenizer, _, prompt_tokens, _ = plans[i]
+        all_tokens = list(prompt_tokens)
+        segments = []
+        for s in lane.segments:
+            segments.append({"id": len(segments), **s})
+            all_tokens.extend(s["tokens"])
+            if verbose:
+                print(f"[{i}] [{s['start']:.2f} --> {s['end']:.2f}] {s['text']}")
+        results.append(dict(text=tokenizer.decode(all_tokens[len(prompt_tokens):]), segments=segments,
+                            language=languages[i]))
+        if spans is not None:
+            results[-1]["speech_spans"] = frames_to_seconds(spans[i])
+    return results
+
+
 def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]], *,
                      language: Union[None, str, Sequence[Optional[str]]] = None,
                      mel_budget_frames: int = DEFAULT_MEL_BUDGET_FRAMES, verbose: Optional[bool] = None,
@@ -340,7 +433,7 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     clips = per_lane(clip_timestamps, "clip_timestamps",
                      lambda v: isinstance(v, str) or all(_is_number(x) for x in v))
     thresholds = (compression_ratio_threshold, logprob_threshold, no_speech_threshold)
-    probe = get_tokenizer(model.is_multilingual, num_languages=model.num_languages) if model.is_multilingual else None
+    spans: Optional[dict] = None if vad_params is None else {}  # skip_silence: file -> its speech spans in frames
 
     def prepare_group(group: List[int]):
         # the group's files back to back in the resident buffer (PCM resampled there, arrays
@@ -365,79 +458,13 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
                 spans[i] = sp
         return ctx.log_mel_batch_resident([lengths[i] for i in group], n_mels, padding=N_SAMPLES)
 
-    spans: dict = {}       # skip_silence: file -> its speech spans in frames
-    clips_of: dict = {}    # and the clips they give (clamped to the file's whole frames)
-
-    def file_clips(k: int, i: int, bases):
-        if vad_params is not None and i not in clips_of:
-            clips_of[i] = clamp_clips(spans[i], int(bases[k + 1] - bases[k]) - N_FRAMES)
-        return clips_of.get(i)
-
-    def detect(group: List[int], bases) -> None:
-        """Language of every file of the group that has none: the first window of up to
-        max_windows files per encode, one <|startoftranscript|> pass per slot."""
-        # with skip_silence the probe window starts at the first span; a file without one is not probed
-        first = {k: (file_clips(k, i, bases) or [(0, 0)])[0][0] for k, i in enumerate(group)}
-        todo = [k for k, i in enumerate(group) if languages[i] is None and file_clips(k, i, bases) != []]
-        for c0 in range(0, len(todo), ctx.max_windows):
-            chunk = todo[c0:c0 + ctx.max_windows]
-            seeks = [int(bases[k]) + first[k] for k in chunk]
-            sizes = [min(N_FRAMES, int(bases[k + 1] - bases[k]) - first[k]) for k in chunk]
-            ctx.encode(seeks, sizes)
-            model._last_windows = (seeks, sizes)
-            for slot, k in enumerate(chunk):
-                _, probs = language_probs(model, slot, probe)
-                languages[group[k]] = max(probs, key=probs.get)
-                if verbose is not None:
-                    print(f"[{group[k]}] Detected language: {LANGUAGES[languages[group[k]]].title()}")
-
-    plans = {}
-    # one sampling seed per file (per channel of a split file), drawn in input order as a loop of
-    # transcribe() calls over the files and the channel waveforms draws them
-    file_seeds = [next_seed() for _ in range(n)]
-
-    def make_lanes(group: List[int], bases) -> List[_Lane]:
-        if not model.is_multilingual:
-            for i in group:
-                languages[i] = languages[i] or "en"
-        else:
-            detect(group, bases)
-        lanes = []
-        for k, i in enumerate(group):
-            content_frames = int(bases[k + 1] - bases[k]) - N_FRAMES
-            clips_i = file_clips(k, i, bases)
-            if clips_i == []:
-                clips_i = [(0, 0)]  # no speech: a clip that offers no window, so the file takes no lane
-            opts = dict(decode_options, language=languages[i])
-            plan = _plan_file(model, content_frames, languages[i], opts, temperature=temperature,
-                              thresholds=thresholds, initial_prompt=prompts[i], word_timestamps=word_timestamps,
-                              prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
-                              clip_timestamps=clips[i],
-                              hallucination_silence_threshold=hallucination_silence_threshold, seek_clips=clips_i)
-            plans[i] = plan
-            tokenizer, seek_clips, prompt_tokens, st = plan
-            lanes.append(_Lane(model.dims.n_text_ctx, seek_clips, prompt_tokens, condition_on_previous_text,
-                               carry_initial_prompt, st, base=int(bases[k]), file_seed=file_seeds[i]))
-        return lanes
-
-    decode_round, align_round = _device_round(model, per_file=True)
-    lanes = run_files(lengths, max_windows=ctx.max_windows, mel_budget_frames=mel_budget_frames,
-                      prepare_group=prepare_group, make_lanes=make_lanes, decode_round=decode_round,
-                      align_round=align_round if word_timestamps else None, units=file_of)
-    results = []
-    for i, lane in enumerate(lanes):
-        tokenizer, _, prompt_tokens, _ = plans[i]
-        all_tokens = list(prompt_tokens)
-        segments = []
-        for s in lane.segments:
-            segments.append({"id": len(segments), **s})
-            all_tokens.extend(s["tokens"])
-            if verbose:
-                print(f"[{i}] [{s['start']:.2f} --> {s['end']:.2f}] {s['text']}")
-        results.append(dict(text=tokenizer.decode(all_tokens[len(prompt_tokens):]), segments=segments,
-                            language=languages[i]))
-        if vad_params is not None:
-            results[-1]["speech_spans"] = frames_to_seconds(spans[i])
+    results = _transcribe_lanes(
+        model, lengths, prepare_group, languages, prompts, clips, units=file_of, spans=spans,
+        mel_budget_frames=mel_budget_frames, verbose=verbose, temperature=temperature, thresholds=thresholds,
+        condition_on_previous_text=condition_on_previous_text, carry_initial_prompt=carry_initial_prompt,
+        word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
+        append_punctuations=append_punctuations, hallucination_silence_threshold=hallucination_silence_threshold,
+        decode_options=decode_options)
     if all(sel is None for sel in selected):
         return results
     out = []

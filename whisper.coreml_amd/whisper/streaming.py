@@ -44,6 +44,16 @@ def _frame_bytes(data, encoding: str) -> bytes:
     return bytes(data)
 
 
+def _check_options(transcribe_options: dict, who: str) -> None:
+    """The transcribe options a streaming decode cannot take (``ValueError``); ``word_timestamps=True``
+    is dropped from the dict, since every decode sets it."""
+    if "word_timestamps" in transcribe_options and not transcribe_options.pop("word_timestamps"):
+        raise ValueError(f"{who} needs word_timestamps=True: the policy commits words by their times")
+    for name in _REFUSED_OPTIONS:
+        if name in transcribe_options:
+            raise ValueError(f"{who} does not take {name}: every decode is the whole resident buffer")
+
+
 class AudioStream:
     """A recording that arrives in chunks, resampled to 16 kHz mono on the GPU as it comes.
 
@@ -210,14 +220,10 @@ class StreamingTranscriber:
                  min_chunk: float = 1.0, buffer_trim: float = 15.0, max_buffer: float = 25.0, prompt_chars: int = 200,
                  initial_prompt: Optional[str] = None, stream=None,
                  decode_fn: Optional[Callable[[Optional[str], Tuple[int, int]], dict]] = None, **transcribe_options):
-        if "word_timestamps" in transcribe_options and not transcribe_options.pop("word_timestamps"):
-            raise ValueError("StreamingTranscriber needs word_timestamps=True: the policy commits words by their times")
+        _check_options(transcribe_options, "StreamingTranscriber")
         if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)):
             raise ValueError(f"channels = {channels!r}: here it is the stream's channel count, which is mixed down; "
                              f"transcribe's channels option (\"split\", a selection) is not available on a stream")
-        for name in _REFUSED_OPTIONS:
-            if name in transcribe_options:
-                raise ValueError(f"StreamingTranscriber does not take {name}: every decode is the whole resident buffer")
         if not min_chunk > 0:
             raise ValueError(f"min_chunk = {min_chunk}: must be positive")
         if not (0 < buffer_trim < max_buffer <= 30.0 - min_chunk):
@@ -330,13 +336,24 @@ class StreamingTranscriber:
 
     def _update(self, final: bool) -> StreamUpdate:
         t_begin = time.perf_counter()
+        u, due = self._begin_update(final)
+        return self._end_update(u, self._decode(u.prompt, u.span) if due else None, t_begin)
+
+    # an update in two halves, so that a pool can decode the buffers of many streams between them
+    def _begin_update(self, final: bool) -> Tuple[StreamUpdate, bool]:
+        """The update of the buffer as it is, and whether it needs a decode (then with its prompt)."""
         s0, s1 = self._s0, self._s1
-        t0 = s0 / SAMPLE_RATE
         u = StreamUpdate(span=(s0, s1), final=final, language=self.language)
-        words, result = [], None
-        if s1 > s0 and (not final or s1 > self._decoded_s1):
-            u.prompt = self.build_prompt(t0)
-            result = self._decode(u.prompt, (s0, s1))
+        due = s1 > s0 and (not final or s1 > self._decoded_s1)
+        if due:
+            u.prompt = self.build_prompt(s0 / SAMPLE_RATE)
+        return u, due
+
+    def _end_update(self, u: StreamUpdate, result: Optional[dict], t_begin: float) -> StreamUpdate:
+        """``result``: what the decode of ``u.span`` with ``u.prompt`` returned (None: there was none)."""
+        s0, s1 = u.span
+        t0 = s0 / SAMPLE_RATE
+        if result is not None:
             self._decoded_s1 = s1
             if self.language is None:
                 self.language = result.get("language")
@@ -344,7 +361,7 @@ class StreamingTranscriber:
                      for s in result["segments"] for w in s.get("words", [])]
             u.committed = self.policy.update(words)
         u.result, u.language = result, self.language
-        if final:
+        if u.final:
             u.committed = u.committed + self.policy.flush()
         elif result is not None:
             self._trim(u, result, t0)
