@@ -619,6 +619,82 @@ int wh_pool_info(wh_ctx* ctx, int slot, int64_t* frames_in, int64_t* samples_out
 int wh_pool_read(wh_ctx* ctx, int slot, float* out, int64_t offset, int64_t n);
 int wh_pool_log_mel(wh_ctx* ctx, int n, const int* slots, int64_t padding, int n_mels, int64_t* frame_base);
 
+/* ---- Voice activity of a live stream: a causal, incremental speech detector that lives on the
+   device next to a stream's samples and is updated inside the call that ingests them.
+   The definition is in integers (whisper/vad.py, StreamVad, restates it in numpy); steps 1-3 are
+   those of wh_speech_spans above (q, E, the quarter-octave bins).
+
+   Frame grid.  A detector belongs to one stream.  Frame f is the stream's emitted 16 kHz samples
+   [160 f, 160 f + 160), counted from the stream's first sample: trims do not move the grid.
+   E[f] = the uint64 sum of q^2 over the frame.
+
+   Options (wh_svad_opts): ratio_q8, t_lo, t_hi and percentile as in wh_vad_opts; window W in
+   1..6000 frames; min_silence in 1..2^20 frames; min_speech in 0..2^20 frames.
+
+   State, all zero at enable: hist[160]; ring[W] of bin numbers (uint8); frames; samples (seen so
+   far); partial (the q^2 sum of the samples of the incomplete frame `frames` seen so far); state
+   (0 SILENCE, 1 ONSET, 2 SPEECH); run_start, run_end (meaningful only while state != SILENCE);
+   closed_start, closed_end (the last span that ended), closed_total; threshold.
+
+   Per completed frame f, in order:
+     b = bin(E[f]);  hist[b] += 1;  if f >= W: hist[ring[f % W]] -= 1;  ring[f % W] = b
+     n = min(f + 1, W);  rank = max(1, ceil(n * percentile / 100))
+     N = the lower edge of the first bin whose cumulative count reaches rank
+     T = min(max((N * ratio_q8) >> 8, t_lo), t_hi)
+     if E[f] > T:
+         if state == SILENCE: state = ONSET; run_start = f
+         run_end = f + 1
+         if state == ONSET and run_end - run_start >= min_speech: state = SPEECH
+     elif state != SILENCE and f + 1 - run_end >= min_silence:
+         if state == SPEECH: (closed_start, closed_end) = (run_start, run_end); closed_total += 1
+         state = SILENCE
+     frames = f + 1;  threshold = T
+   With t_lo == t_hi the closed spans (and the open run of a stream that ends in SPEECH) are
+   step 5 of wh_speech_spans with pad = 0: the file's rules evaluated causally.
+
+   An append hands the detector exactly the samples that append emitted: whole frames are closed
+   as above, the rest goes into partial (so a trim that drops samples the grid has not closed
+   loses nothing).  A finish hands it the samples it releases and, if samples % 160 != 0, closes
+   the last frame with zeros: frames = ceil(samples / 160), partial = 0.
+
+   wh_pool_vad_enable gives an open slot that has taken no frames yet a detector (its state block
+   is allocated here).  From then on wh_pool_append / wh_pool_finish update it: with detecting
+   slots in a call, the call's descriptor copy carries their descriptors too, one more launch
+   (csrc/wh_svad.hip, one workgroup per detecting slot: the energies of the new samples in
+   parallel, then the recurrence on one wave) goes on the same stream behind the ingest kernel,
+   and one device-to-host copy of the states goes before the call's one synchronisation.  A call
+   without detecting slots launches and copies what it did before.  wh_pool_trim does not touch a
+   detector; wh_pool_close and wh_pool_destroy drop it.
+   wh_pool_vad_state: the states of n detecting slots as of each slot's last append or finish,
+   from the host copy (no HIP call).  wh_pool_vad_read (inspection): ring receives W bytes
+   (cap >= W), hist (nullable) the 160 counters.
+   wh_stream_vad_enable / wh_stream_vad_state: the same for the single stream, behind
+   wh_stream_append / wh_stream_finish; wh_stream_begin drops the detector, and so does any call
+   that ends the stream.
+   The detector's kernel time goes to WH_STAT_INGEST_KERNEL_MS, the state copy is not charged.
+
+   Refused before the first HIP call, nothing changed (-1 for a null pointer, -7 otherwise,
+   wh_last_error naming "pool" or "stream" and the field): null opts / out / ring; percentile
+   outside 1..99; ratio_q8 outside [256, 2560000]; t_lo > t_hi; window, min_silence or
+   min_speech outside the ranges above; a slot that is not open, has already taken frames (or is
+   finished) or is already detecting; state or read of a slot without a detector; cap < W.
+   wh_version() does not change with these five: a caller detects them by the symbols. */
+typedef struct wh_svad_opts {
+  uint64_t ratio_q8, t_lo, t_hi;
+  int percentile;                      /* 1..99 */
+  int window, min_silence, min_speech; /* frames */
+} wh_svad_opts;
+typedef struct wh_svad_state {
+  int64_t frames, samples, run_start, run_end, closed_start, closed_end, closed_total;
+  uint64_t threshold, partial;
+  int32_t state, reserved;
+} wh_svad_state;
+int wh_pool_vad_enable(wh_ctx* ctx, int slot, const wh_svad_opts* opts);
+int wh_pool_vad_state(wh_ctx* ctx, int n, const int* slots, wh_svad_state* out);
+int wh_pool_vad_read(wh_ctx* ctx, int slot, uint8_t* ring, int cap, uint32_t* hist);
+int wh_stream_vad_enable(wh_ctx* ctx, const wh_svad_opts* opts);
+int wh_stream_vad_state(wh_ctx* ctx, wh_svad_state* out);
+
 #ifdef __cplusplus
 }
 #endif

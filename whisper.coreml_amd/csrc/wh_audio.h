@@ -11,6 +11,7 @@
 #include "wh_flacdev.h"
 #include "wh_host.h"
 #include "wh_kernels.h"
+#include "wh_svad.h"
 #include "wh_vad.h"
 #include "whisper_hip.h"
 
@@ -51,6 +52,12 @@ struct AudioFront {
   int stream_finish(int64_t* n_out);
   int stream_trim(int64_t n_drop);
   int stream_info(int64_t* frames_in, int64_t* samples_out, int64_t* samples_dropped, int* finished);
+  // the causal speech detector of a live stream (include/whisper_hip.h), updated by the appends
+  int stream_vad_enable(const wh_svad_opts* o);
+  int stream_vad_state(wh_svad_state* out);
+  int pool_vad_enable(int slot, const wh_svad_opts* o);
+  int pool_vad_state(int n, const int* slots, wh_svad_state* out);
+  int pool_vad_read(int slot, uint8_t* ring, int cap, uint32_t* hist);
   // many live streams at once: slots with buffers of their own (include/whisper_hip.h)
   int pool_create(int n_slots, int64_t slot_samples);
   int pool_destroy();
@@ -105,12 +112,21 @@ struct AudioFront {
   // wh_stream_*: the open stream.  The resident segment is (0, samples_out - dropped); the
   // history of the last `hist` mixed-down frames lies in half `cur` of d_hist ([2][hist]
   // doubles), the next append writes the other half.  ended_by: the call that closed it
+  // A stream's speech detector: the options it was enabled with, the host copy of its state as
+  // of the last append or finish, and its state block on the device (kept across begin / open)
+  struct Svad {
+    bool on = false;
+    wh_svad_opts o{};
+    wh_svad_state host{};
+    DevBuf<char> block;
+  };
   struct Stream {
     bool open = false, finished = false;
     int encoding = 0, channels = 0, bits = 0, frame_bytes = 0, up = 1, down = 1, hist = 0, cur = 0;
     const double* taps = nullptr;  // the device filter of (up, down), null when up == down
     int64_t frames_in = 0, samples_out = 0, dropped = 0;
     std::string ended_by;
+    Svad vad;
   } stream;
   DevBuf<double> d_hist;
   DevBuf<float> d_bounce;  // wh_stream_trim, when the move overlaps itself
@@ -133,6 +149,14 @@ struct AudioFront {
   char* pool_stage = nullptr;
   char* pool_hdesc = nullptr;
   size_t pool_stage_cap = 0, pool_hdesc_cap = 0;
+  // what the detectors of one call share: the frame energies between the kernel's two phases,
+  // the states the launch leaves (device) and their pinned host copy
+  DevBuf<unsigned long long> svad_energy;
+  DevBuf<wh_svad_state> svad_out;
+  char* svad_hout = nullptr;
+  size_t svad_hout_cap = 0;
+  int svad_enable(const std::string& who, Svad& v, const wh_svad_opts* o);
+  int svad_room(int n, int64_t frames);
   float* pool_base(int slot, int buf) { return pool_audio.p + ((size_t)slot * 2 + buf) * pool_samples; }
   void pool_release(Releases& rel);
   int pool_slots(const std::string& who, int n, const int* slots, bool for_input);
@@ -163,7 +187,7 @@ struct AudioFront {
   void one_segment(int64_t n);
   void stream_ends(const char* by);
   int stream_open(const std::string& who, bool for_input);
-  int stream_run(const void* data, int64_t nc, int64_t total, int64_t* n_out);
+  int stream_run(const void* data, int64_t nc, int64_t total, int64_t* n_out, bool finish);
   int filter_taps(const std::string& who, int up, int down, const double* taps, int n_taps, double** dt);
   int vad_plan(const char* who, int n_files, std::vector<wh::VadFile>* files, int64_t* blocks);
   int vad_energy_launch(const std::vector<wh::VadFile>& files, int64_t blocks);

@@ -28,7 +28,13 @@ void AudioFront::release(Releases& rel) {
   d_pcm.release(rel, "hipFree(pcm)");
   d_hist.release(rel, "hipFree(stream history)");
   d_bounce.release(rel, "hipFree(stream bounce)");
+  stream.vad.block.release(rel, "hipFree(stream detector)");
+  stream.vad.on = false;
   pool_release(rel);
+  svad_energy.release(rel, "hipFree(detector energies)");
+  svad_out.release(rel, "hipFree(detector states)");
+  if (svad_hout) rel(hipHostFree(std::exchange(svad_hout, nullptr)), "hipHostFree(detector states)");
+  svad_hout_cap = 0;
   auto flac = [&](auto&... b) { (b.release(rel, "hipFree(flac)"), ...); };
   flac(fl_bytes, fl_cands, fl_subs, fl_ends, fl_stage, fl_chain, fl_starts);
   for (auto& kv : d_taps) rel(hipFree(kv.second), "hipFree(resampling taps)");
@@ -193,6 +199,7 @@ extern "C" long long wh_stream_emitted(int64_t n_frames, int up, int down, int f
 void AudioFront::stream_ends(const char* by) {
   if (!stream.open) return;
   stream.open = false;
+  stream.vad.on = false;
   stream.ended_by = by;
   while (!stream.ended_by.empty() && (stream.ended_by.back() == ' ' || stream.ended_by.back() == ':')) stream.ended_by.pop_back();
 }
@@ -233,7 +240,9 @@ int AudioFront::stream_begin(int encoding, int channels, int up, int down, const
   // the frames before the recording are zeros
   HIPCHK(hipMemsetAsync(d_hist.p, 0, (size_t)std::max(hist, 1) * 16, st));
   HIPCHK(hipStreamSynchronize(st));
-  stream = Stream();
+  const DevBuf<char> keep = stream.vad.block;
+  stream = Stream();  // the detector goes with the stream it belonged to
+  stream.vad.block = keep;
   stream.open = true;
   stream.encoding = encoding; stream.channels = channels; stream.bits = stream_bits[encoding];
   stream.frame_bytes = stream_container[encoding] * channels;
@@ -243,9 +252,13 @@ int AudioFront::stream_begin(int encoding, int channels, int up, int down, const
 }
 // frames [frames_in, frames_in + nc) arrive (data), or the recording ends (nc = 0, total = all
 // there will be): the outputs that become final are appended to the resident segment
-int AudioFront::stream_run(const void* data, int64_t nc, int64_t total, int64_t* n_out) {
+int AudioFront::stream_run(const void* data, int64_t nc, int64_t total, int64_t* n_out, bool finish) {
   Stream& s = stream;
   const int64_t len = s.samples_out - s.dropped, emit = total - s.samples_out;
+  // the detector takes the samples this call emits; a finish also closes its incomplete frame
+  const int fill = s.vad.on ? (int)(s.vad.host.samples % VAD_HOP) : 0;
+  const bool detect = s.vad.on && (emit > 0 || (finish && fill));
+  if (detect) TRY(svad_room(1, svad_frames(fill, emit)));
   if (len + emit > (int64_t)(d_audio.cap / 4))  // grows by doubling: an append a second does not reallocate each time
     TRY(d_audio.reserve((size_t)std::max(len + emit, 2 * len) * 4, (size_t)len * 4, st));
   const size_t bytes = (size_t)nc * s.frame_bytes;
@@ -255,14 +268,21 @@ int AudioFront::stream_run(const void* data, int64_t nc, int64_t total, int64_t*
   TRY(tm.mark(0, st));
   if (nc) HIPCHK(hipMemcpyAsync(d_pcm.p, data, bytes, hipMemcpyHostToDevice, st));
   TRY(tm.mark(1, st));
-  launch_pcm_resample_stream(d_pcm.p, s.encoding, s.frames_in, nc, s.channels, s.bits, s.up, s.down, s.taps, old_half,
-                             new_half, s.hist, d_audio.p + len, s.samples_out, emit, st);
+  const bool ingest = nc > 0 || emit > 0;  // not so only for a finish that merely closes the detector's frame
+  if (ingest)
+    launch_pcm_resample_stream(d_pcm.p, s.encoding, s.frames_in, nc, s.channels, s.bits, s.up, s.down, s.taps, old_half,
+                               new_half, s.hist, d_audio.p + len, s.samples_out, emit, st);
+  if (detect)
+    launch_stream_vad_one(SvadDesc{d_audio.p + len, emit, svad_energy.p, (SvadBlock*)s.vad.block.p, finish ? 1 : 0, 0},
+                          svad_out.p, st);
   TRY(tm.mark(2, st));
+  if (detect) HIPCHK(hipMemcpyAsync(svad_hout, svad_out.p, sizeof(wh_svad_state), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   TRY(launch_status("stream_append"));
   TRY(tm.charge(0, stats[WH_STAT_INGEST_COPY_MS]));
   TRY(tm.charge(1, stats[WH_STAT_INGEST_KERNEL_MS]));
-  if (s.hist) s.cur = 1 - s.cur;
+  if (detect) memcpy(&s.vad.host, svad_hout, sizeof(wh_svad_state));
+  if (s.hist && ingest) s.cur = 1 - s.cur;
   s.frames_in += nc;
   s.samples_out = total;
   one_segment(len + emit);
@@ -279,14 +299,16 @@ int AudioFront::stream_append(const void* data, int64_t n_frames, int64_t* n_out
     return 0;
   }
   if (!data) return fail(-1, who + "stream: null data with n_frames > 0");
-  return stream_run(data, n_frames, stream_emitted(stream.frames_in + n_frames, stream.up, stream.down, false), n_out);
+  return stream_run(data, n_frames, stream_emitted(stream.frames_in + n_frames, stream.up, stream.down, false), n_out,
+                    false);
 }
 int AudioFront::stream_finish(int64_t* n_out) {
   const std::string who = "stream_finish: ";
   TRY(stream_open(who, false));
   if (!stream.finished) {
     const int64_t total = stream_emitted(stream.frames_in, stream.up, stream.down, true);
-    if (total > stream.samples_out) TRY(stream_run(nullptr, 0, total, n_out));
+    const bool open_frame = stream.vad.on && stream.vad.host.samples % VAD_HOP != 0;
+    if (total > stream.samples_out || open_frame) TRY(stream_run(nullptr, 0, total, n_out, true));
     else if (n_out) *n_out = 0;
     stream.finished = true;
     return 0;
@@ -326,6 +348,63 @@ int AudioFront::stream_info(int64_t* frames_in, int64_t* samples_out, int64_t* s
   return 0;
 }
 
+// ------------------------------------------------------------ the detector of a live stream
+// (include/whisper_hip.h, "Voice activity of a live stream"): what the single stream and a pool
+// slot share.  svad_check is host arithmetic only.
+static int svad_check(const std::string& who, const wh_svad_opts* o) {
+  if (!o) return fail(-1, who + "null opts");
+  if (o->percentile < 1 || o->percentile > 99)
+    return fail(-7, who + "percentile = " + std::to_string(o->percentile) + " outside 1..99");
+  if (o->ratio_q8 < 256 || o->ratio_q8 > 2560000)
+    return fail(-7, who + "ratio_q8 = " + std::to_string(o->ratio_q8) + " outside [256, 2560000]");
+  if (o->t_lo > o->t_hi)
+    return fail(-7, who + "t_lo = " + std::to_string(o->t_lo) + " above t_hi = " + std::to_string(o->t_hi));
+  if (o->window < 1 || o->window > SVAD_MAX_WINDOW)
+    return fail(-7, who + "window = " + std::to_string(o->window) + " outside 1.." + std::to_string(SVAD_MAX_WINDOW));
+  if (o->min_silence < 1 || o->min_silence > SVAD_MAX_RUN)
+    return fail(-7, who + "min_silence = " + std::to_string(o->min_silence) + " outside 1..2^20");
+  if (o->min_speech < 0 || o->min_speech > SVAD_MAX_RUN)
+    return fail(-7, who + "min_speech = " + std::to_string(o->min_speech) + " outside 0..2^20");
+  return 0;
+}
+// the caller has checked everything: the state block, all zero behind the options
+int AudioFront::svad_enable(const std::string& who, Svad& v, const wh_svad_opts* o) {
+  const size_t bytes = svad_block_bytes(o->window);
+  TRY(v.block.reserve(bytes));
+  SvadBlock head{};
+  head.o = *o;
+  HIPCHK(hipMemsetAsync(v.block.p, 0, bytes, st));
+  HIPCHK(hipMemcpyAsync(v.block.p, &head, offsetof(SvadBlock, hist), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  v.o = *o;
+  v.host = wh_svad_state{};
+  v.on = true;
+  return 0;
+}
+// room for a call with n detecting slots and `frames` frame energies between them
+int AudioFront::svad_room(int n, int64_t frames) {
+  TRY(svad_energy.reserve((size_t)std::max<int64_t>(frames, 64) * 8));
+  TRY(svad_out.reserve((size_t)std::max(n, 16) * sizeof(wh_svad_state)));
+  const size_t bytes = (size_t)n * sizeof(wh_svad_state);
+  return pool_pinned(&svad_hout, &svad_hout_cap, bytes > svad_hout_cap ? std::max(bytes, 2 * svad_hout_cap) : bytes);
+}
+int AudioFront::stream_vad_enable(const wh_svad_opts* o) {
+  const std::string who = "stream_vad_enable: stream: ";
+  TRY(svad_check(who, o));
+  TRY(stream_open("stream_vad_enable: ", false));
+  if (stream.frames_in || stream.finished) return fail(-7, who + "has already taken frames: enable the detector right after wh_stream_begin");
+  if (stream.vad.on) return fail(-7, who + "is already detecting");
+  return svad_enable(who, stream.vad, o);
+}
+int AudioFront::stream_vad_state(wh_svad_state* out) {
+  const std::string who = "stream_vad_state: stream: ";
+  if (!out) return fail(-1, who + "null out");
+  TRY(stream_open("stream_vad_state: ", false));
+  if (!stream.vad.on) return fail(-7, who + "has no detector (wh_stream_vad_enable)");
+  *out = stream.vad.host;
+  return 0;
+}
+
 // ------------------------------------------------------------ a pool of streams
 // (include/whisper_hip.h).  A batched call is all or nothing: everything is checked before the
 // first HIP call, and a refused call leaves every slot and every n_out[] entry as it was.
@@ -343,7 +422,10 @@ int AudioFront::pool_create(int n_slots, int64_t slot_samples) {
   return 0;
 }
 void AudioFront::pool_release(Releases& rel) {
-  for (auto& s : pool) s.hist_buf.release(rel, "hipFree(pool history)");
+  for (auto& s : pool) {
+    s.hist_buf.release(rel, "hipFree(pool history)");
+    s.vad.block.release(rel, "hipFree(pool detector)");
+  }
   pool.clear();
   pool_samples = 0;
   pool_audio.release(rel, "hipFree(pool audio)");
@@ -376,8 +458,10 @@ int AudioFront::pool_open(int slot, int encoding, int channels, int up, int down
   HIPCHK(hipMemsetAsync(s.hist_buf.p, 0, (size_t)std::max(hist, 1) * 16, st));
   HIPCHK(hipStreamSynchronize(st));
   const DevBuf<double> keep = s.hist_buf;
+  const DevBuf<char> keep_vad = s.vad.block;
   s = PoolSlot();
   s.hist_buf = keep;
+  s.vad.block = keep_vad;
   s.open = true;
   s.encoding = encoding; s.channels = channels; s.bits = stream_bits[encoding];
   s.frame_bytes = stream_container[encoding] * channels;
@@ -388,6 +472,7 @@ int AudioFront::pool_close(int slot) {
   const int one[1] = {slot};
   TRY(pool_slots("pool_close: pool: ", 1, one, false));
   pool[slot].open = false;
+  pool[slot].vad.on = false;
   return 0;
 }
 // the slots of a batched call: a pool, n >= 1, every slot in range, open (and still taking
@@ -427,49 +512,72 @@ int AudioFront::pool_run(int n, const int* slots, const void* const* data, const
                          const int64_t* totals, int64_t* n_out, const char* where) {
   std::vector<size_t> offs(n, 0);
   size_t bytes = 0;
-  int work = 0;
+  int work = 0, vwork = 0;  // slots with samples to ingest; detecting slots with frames to take
+  int64_t vframes = 0;
+  // a detecting slot takes the samples the call emits for it; a finish also closes its incomplete frame
+  auto detects = [&](const PoolSlot& s, int64_t emit) {
+    return s.vad.on && (emit > 0 || (!data && !s.finished && s.vad.host.samples % VAD_HOP != 0));
+  };
   for (int i = 0; i < n; ++i) {
     const PoolSlot& s = pool[slots[i]];
     const int64_t nc = data ? n_frames[i] : 0;
+    if (detects(s, totals[i] - s.samples_out)) {
+      ++vwork;
+      vframes += svad_frames((int)(s.vad.host.samples % VAD_HOP), totals[i] - s.samples_out);
+    }
     if (!nc && totals[i] == s.samples_out) continue;  // nothing arrives, nothing becomes final
     ++work;
     offs[i] = bytes;
     bytes += ((size_t)nc * s.frame_bytes + 8 + 15) & ~(size_t)15;  // 24-bit samples are read as aligned dwords
   }
-  if (work) {
-    const size_t dbytes = (size_t)work * pool_stream_bytes();
+  if (work || vwork) {
+    // the detectors' descriptors lie behind the streams' in the one descriptor copy
+    const size_t voff = ((size_t)work * pool_stream_bytes() + 15) & ~(size_t)15;
+    const size_t dbytes = vwork ? voff + (size_t)vwork * sizeof(SvadDesc) : (size_t)work * pool_stream_bytes();
     TRY(pool_pinned(&pool_stage, &pool_stage_cap, bytes > pool_stage_cap ? std::max(bytes, 2 * pool_stage_cap) : bytes));
     TRY(pool_pinned(&pool_hdesc, &pool_hdesc_cap, dbytes));
     TRY(pool_pcm.reserve(std::max<size_t>(pool_stage_cap, 16)));
     TRY(pool_desc.reserve(pool_hdesc_cap));
-    int64_t blocks = 0;
-    int j = 0;
+    if (vwork) TRY(svad_room(vwork, vframes));
+    SvadDesc* vd = (SvadDesc*)(pool_hdesc + voff);
+    int64_t blocks = 0, e_base = 0;
+    int j = 0, jv = 0;
     for (int i = 0; i < n; ++i) {
       const PoolSlot& s = pool[slots[i]];
       const int64_t nc = data ? n_frames[i] : 0;
+      const int64_t len = s.samples_out - s.dropped, emit = totals[i] - s.samples_out;
+      if (detects(s, emit)) {
+        vd[jv] = SvadDesc{pool_base(slots[i], s.buf) + len, emit, svad_energy.p + e_base, (SvadBlock*)s.vad.block.p,
+                          data ? 0 : 1, jv};
+        e_base += svad_frames((int)(s.vad.host.samples % VAD_HOP), emit);
+        ++jv;
+      }
       if (!nc && totals[i] == s.samples_out) continue;
       if (nc) memcpy(pool_stage + offs[i], data[i], (size_t)nc * s.frame_bytes);
-      const int64_t len = s.samples_out - s.dropped;
       blocks += pool_stream_fill(pool_hdesc, j++, blocks, pool_pcm.p + offs[i], s.encoding, s.frames_in, nc, s.channels,
                                  s.bits, s.up, s.down, s.taps, s.hist_buf.p + (size_t)s.cur * s.hist,
                                  s.hist_buf.p + (size_t)(1 - s.cur) * s.hist, s.hist,
-                                 pool_base(slots[i], s.buf) + len, s.samples_out, totals[i] - s.samples_out);
+                                 pool_base(slots[i], s.buf) + len, s.samples_out, emit);
     }
     TRY(tm.mark(0, st));
-    if (data) HIPCHK(hipMemcpyAsync(pool_pcm.p, pool_stage, bytes, hipMemcpyHostToDevice, st));
+    if (data && work) HIPCHK(hipMemcpyAsync(pool_pcm.p, pool_stage, bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(pool_desc.p, pool_hdesc, dbytes, hipMemcpyHostToDevice, st));
     TRY(tm.mark(1, st));
-    launch_pcm_resample_pool(pool_desc.p, work, blocks, st);
+    if (work) launch_pcm_resample_pool(pool_desc.p, work, blocks, st);
+    if (vwork) launch_stream_vad_pool((const SvadDesc*)(pool_desc.p + voff), vwork, svad_out.p, st);
     TRY(tm.mark(2, st));
+    if (vwork)
+      HIPCHK(hipMemcpyAsync(svad_hout, svad_out.p, (size_t)vwork * sizeof(wh_svad_state), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     TRY(launch_status(where));
     TRY(tm.charge(0, stats[WH_STAT_INGEST_COPY_MS]));
     TRY(tm.charge(1, stats[WH_STAT_INGEST_KERNEL_MS]));
   }
-  for (int i = 0; i < n; ++i) {
+  for (int i = 0, jv = 0; i < n; ++i) {
     PoolSlot& s = pool[slots[i]];
     const int64_t nc = data ? n_frames[i] : 0;
     if (n_out) n_out[i] = totals[i] - s.samples_out;
+    if (detects(s, totals[i] - s.samples_out)) memcpy(&s.vad.host, svad_hout + (size_t)jv++ * sizeof(wh_svad_state), sizeof(wh_svad_state));
     if (!nc && totals[i] == s.samples_out) continue;
     if (s.hist) s.cur = 1 - s.cur;
     s.frames_in += nc;
@@ -565,6 +673,40 @@ int AudioFront::pool_info(int slot, int64_t* frames_in, int64_t* samples_out, in
   if (samples_out) *samples_out = s.samples_out;
   if (samples_dropped) *samples_dropped = s.dropped;
   if (finished) *finished = s.finished ? 1 : 0;
+  return 0;
+}
+int AudioFront::pool_vad_enable(int slot, const wh_svad_opts* o) {
+  const std::string who = "pool_vad_enable: pool: ";
+  TRY(svad_check(who, o));
+  const int one[1] = {slot};
+  TRY(pool_slots(who, 1, one, false));
+  PoolSlot& s = pool[slot];
+  if (s.frames_in || s.finished)
+    return fail(-7, who + "slot " + std::to_string(slot) + " has already taken frames: enable the detector right after wh_pool_open");
+  if (s.vad.on) return fail(-7, who + "slot " + std::to_string(slot) + " is already detecting");
+  return svad_enable(who, s.vad, o);
+}
+int AudioFront::pool_vad_state(int n, const int* slots, wh_svad_state* out) {
+  const std::string who = "pool_vad_state: pool: ";
+  TRY(pool_slots(who, n, slots, false));
+  if (!out) return fail(-1, who + "null out");
+  for (int i = 0; i < n; ++i)
+    if (!pool[slots[i]].vad.on)
+      return fail(-7, who + field_at("slots", i) + " = " + std::to_string(slots[i]) + " has no detector (wh_pool_vad_enable)");
+  for (int i = 0; i < n; ++i) out[i] = pool[slots[i]].vad.host;
+  return 0;
+}
+int AudioFront::pool_vad_read(int slot, uint8_t* ring, int cap, uint32_t* hist) {
+  const std::string who = "pool_vad_read: pool: ";
+  const int one[1] = {slot};
+  TRY(pool_slots(who, 1, one, false));
+  if (!ring) return fail(-1, who + "null ring");
+  const PoolSlot& s = pool[slot];
+  if (!s.vad.on) return fail(-7, who + "slot " + std::to_string(slot) + " has no detector (wh_pool_vad_enable)");
+  if (cap < s.vad.o.window)
+    return fail(-7, who + "cap = " + std::to_string(cap) + " is less than the window of " + std::to_string(s.vad.o.window) + " frames");
+  HIPCHK(hipMemcpy(ring, s.vad.block.p + sizeof(SvadBlock), (size_t)s.vad.o.window, hipMemcpyDeviceToHost));
+  if (hist) HIPCHK(hipMemcpy(hist, s.vad.block.p + offsetof(SvadBlock, hist), VAD_BINS * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 int AudioFront::pool_read(int slot, float* out, int64_t offset, int64_t n) {

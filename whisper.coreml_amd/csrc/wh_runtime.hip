@@ -1942,6 +1942,13 @@ int wh_pool_read(wh_ctx* ctx, int slot, float* out, int64_t offset, int64_t n) {
 int wh_pool_log_mel(wh_ctx* ctx, int n, const int* slots, int64_t padding, int n_mels, int64_t* frame_base) {
   CTXCALL(ctx->audio.pool_log_mel(n, slots, padding, n_mels, frame_base));
 }
+int wh_pool_vad_enable(wh_ctx* ctx, int slot, const wh_svad_opts* opts) { CTXCALL(ctx->audio.pool_vad_enable(slot, opts)); }
+int wh_pool_vad_state(wh_ctx* ctx, int n, const int* slots, wh_svad_state* out) { CTXCALL(ctx->audio.pool_vad_state(n, slots, out)); }
+int wh_pool_vad_read(wh_ctx* ctx, int slot, uint8_t* ring, int cap, uint32_t* hist) {
+  CTXCALL(ctx->audio.pool_vad_read(slot, ring, cap, hist));
+}
+int wh_stream_vad_enable(wh_ctx* ctx, const wh_svad_opts* opts) { CTXCALL(ctx->audio.stream_vad_enable(opts)); }
+int wh_stream_vad_state(wh_ctx* ctx, wh_svad_state* out) { CTXCALL(ctx->audio.stream_vad_state(out)); }
 int wh_speech_spans(wh_ctx* ctx, const wh_vad_opts* opts, int n_files, int32_t* spans, int cap, int32_t* n_spans,
                     uint64_t* thresholds) {
   CTXCALL(ctx->audio.speech_spans(opts, n_files, spans, cap, n_spans, thresholds));

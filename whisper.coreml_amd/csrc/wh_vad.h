@@ -25,6 +25,27 @@ WH_DEV_HOST int64_t vad_blocks(int64_t frames) { return (frames + VAD_FB - 1) / 
 // pairs of run scratch a file needs: active runs before any rule, at most every other frame
 WH_DEV_HOST int64_t vad_run_pairs(int64_t frames) { return frames / 2 + 1; }
 
+// q^2 of one sample: q = clamp(rint(32768 x)), rint to even in fp32 (the product is exact);
+// NaN counts as 0
+__device__ inline unsigned vad_sq(float x) {
+  if (x != x) return 0;  // before the clamp: fmaxf(NaN, a) is a
+  float r = rintf(32768.0f * x);
+  r = fminf(fmaxf(r, -32768.0f), 32767.0f);
+  const int q = (int)r;
+  return (unsigned)(q * q);  // at most 2^30
+}
+__device__ inline int vad_bin(unsigned long long e) {
+  if (e == 0) return 0;
+  const int m = 63 - __clzll((long long)e);
+  const int sub = (int)((m >= 2 ? e >> (m - 2) : e << (2 - m)) & 3);
+  return 1 + 4 * m + sub;
+}
+__device__ inline unsigned long long vad_edge(int bin) {
+  if (bin < 1) return 0;
+  const int m = (bin - 1) >> 2, sub = (bin - 1) & 3;
+  return m >= 2 ? (unsigned long long)(4 + sub) << (m - 2) : (unsigned long long)(4 + sub) >> (2 - m);
+}
+
 // E[f] of every file (energy[e_base + f]) and the files' histograms (hist[file][VAD_BINS],
 // zero before the launch).  One launch for all files.
 void launch_frame_energy(const float* audio, const VadFile* files, int n_files, int64_t n_blocks,

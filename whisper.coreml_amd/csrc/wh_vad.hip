@@ -8,26 +8,8 @@
 namespace wh {
 
 // ---------------------------------------------------------------- frame energy
-// q^2 of one sample: q = clamp(rint(32768 x)), rint to even in fp32 (the product is exact);
-// NaN counts as 0
-__device__ inline unsigned vad_sq(float x) {
-  if (x != x) return 0;  // before the clamp: fmaxf(NaN, a) is a
-  float r = rintf(32768.0f * x);
-  r = fminf(fmaxf(r, -32768.0f), 32767.0f);
-  const int q = (int)r;
-  return (unsigned)(q * q);  // at most 2^30
-}
-__device__ inline int vad_bin(unsigned long long e) {
-  if (e == 0) return 0;
-  const int m = 63 - __clzll((long long)e);
-  const int sub = (int)((m >= 2 ? e >> (m - 2) : e << (2 - m)) & 3);
-  return 1 + 4 * m + sub;
-}
-__device__ inline unsigned long long vad_edge(int bin) {
-  if (bin < 1) return 0;
-  const int m = (bin - 1) >> 2, sub = (bin - 1) & 3;
-  return m >= 2 ? (unsigned long long)(4 + sub) << (m - 2) : (unsigned long long)(4 + sub) >> (2 - m);
-}
+// vad_sq, vad_bin and vad_edge (steps 1 and 3 of the definition) live in wh_vad.h: the streaming
+// detector (wh_svad.hip) computes the same.
 
 // A workgroup owns VAD_FB consecutive frames of one file: one contiguous span of samples.
 // The span starts wherever the file's offset puts it, so it is read as 16-byte vectors from

@@ -20,6 +20,16 @@ against the single-stream path, in one process:
    ``wall_ms`` of the same updates of S lone ``StreamingTranscriber``s run one after another on
    the same model (S up to ``--windows``).
 
+With ``--vad`` the cost and the saving of the streams' speech detector (``open(vad=...)``):
+
+5. Tick: S mu-law 8 kHz packets of 20 ms through one ``pool_append`` (S = 1, 16, 64, 256) with a
+   detector on every slot and on none, ``--runs`` times each: ``ingest_kernel_ms`` (HIP events
+   around the ingest kernel and, behind it, the detector's) and the wall p50 / p95 per tick.
+6. Saving: the 12.7 s composite of the tests (silence, speech, a pause, speech, silence, cut from
+   ``--audio``) as one pool stream at ``min_chunk = 1.0``, with and without ``vad``: the decode
+   rounds, their lanes and the summed ``wall_ms``.  The round and lane counts follow from the
+   samples alone; the wall time is that of synthetic weights, whose decodes run to the token limit.
+
 One JSON line per measurement.
 """
 import argparse
@@ -110,6 +120,67 @@ def pool_tick_cost(n_streams, ticks=200):
     return out
 
 
+def vad_tick_cost(n_streams, ticks=200, runs=3):
+    """One tick of ``n_streams`` 20 ms mu-law packets through ``pool_append``: no slot detecting
+    against every slot detecting, ``runs`` times each in turn."""
+    from whisper.audio import WAV_ENCODINGS, _mel_context
+    from whisper.vad import resolve_stream_options
+    ctx = _mel_context(0)
+    frames, enc = 160, WAV_ENCODINGS.index("ulaw")
+    data = np.random.default_rng(0).integers(0, 256, (ticks, n_streams, frames), dtype=np.uint8)
+    slots, counts = list(range(n_streams)), [frames] * n_streams
+    params = resolve_stream_options()
+    out = dict(measure="vad_tick", streams=n_streams, packet_ms=20, ticks=ticks - 1, none=[], vad=[])
+    for _ in range(runs):
+        for name in ("none", "vad"):
+            ctx.pool_create(n_streams, 2 * frames * ticks + 64)
+            for s in slots:
+                ctx.pool_open(s, enc, 1, 8000)
+                if name == "vad":
+                    ctx.pool_vad_enable(s, params)
+            ctx.pool_append(slots, list(data[0]), counts)  # first-touch costs stay out
+            before, wall = ctx.stats(), []
+            for k in range(1, ticks):
+                packets = list(data[k])
+                t = time.perf_counter()
+                ctx.pool_append(slots, packets, counts)
+                wall.append((time.perf_counter() - t) * 1e3)
+            after = ctx.stats()
+            out[name].append(dict(kernel_ms=round((after["ingest_kernel_ms"] - before["ingest_kernel_ms"]) / (ticks - 1), 4),
+                                  copy_ms=round((after["ingest_copy_ms"] - before["ingest_copy_ms"]) / (ticks - 1), 4),
+                                  wall_ms_p50=round(float(np.percentile(wall, 50)), 4),
+                                  wall_ms_p95=round(float(np.percentile(wall, 95)), 4)))
+            ctx.pool_destroy()
+    return out
+
+
+def vad_saving(model, name, audio_path, **decode):
+    """The composite stream through a pool, without and with a detector."""
+    import whisper
+    from whisper.audio import load_audio
+    w = load_audio(audio_path)
+    z = lambda sec: np.zeros(int(round(sec * 16000)), np.float32)
+    comp = np.concatenate([z(1.5), w[:72000], z(2.5), w[84800:128000], z(1.5)])
+    pcm = np.clip(np.round(comp * 32768.0), -32768, 32767).astype(np.int16)
+    out = dict(measure="vad_saving", model=name, decode=decode or dict(greedy=True), seconds=round(len(pcm) / 16000, 2),
+               min_chunk=1.0)
+    for key, vad in (("none", None), ("vad", True)):
+        with whisper.StreamingPool(model, slots=1, temperature=0.0, **decode) as pool:
+            h = pool.open(16000, "s16", 1, language="en", min_chunk=1.0, vad=vad)
+            ups = []
+            for at in range(0, len(pcm), 1600):  # 100 ms packets
+                ups += pool.feed({h: pcm[at:at + 1600]})[h]
+            ups.append(pool.finish([h])[h])
+            decoded = [u for u in ups if u.result is not None]
+            out[key] = dict(updates=len(ups), rounds=len(pool.rounds), lanes=sum(len(r) for r in pool.rounds),
+                            idle=sum(u.idle for u in ups), endpoints=sum(u.endpoint for u in ups),
+                            wall_ms_sum=round(sum(u.wall_ms for u in ups), 1),
+                            # the first decode captures the step graphs
+                            wall_ms_sum_after_first=round(sum(u.wall_ms for u in decoded[1:]), 1),
+                            buffer_s_max=round(max(u.span[1] - u.span[0] for u in decoded) / 16000, 2))
+    return out
+
+
 def pool_round_cost(model, name, n_streams, seconds, **decode):
     """One round with ``n_streams`` due streams against that many lone updates of the same buffers."""
     import whisper
@@ -146,9 +217,21 @@ def main():
     ap.add_argument("--models", default=None, help="default: turbo,large-v3 (turbo with --pool)")
     ap.add_argument("--seconds", type=float, default=12.0)
     ap.add_argument("--pool", action="store_true", help="the stream pool against the single-stream path")
+    ap.add_argument("--vad", action="store_true", help="the streams' speech detector: the tick with and without it, the decodes it saves")
+    ap.add_argument("--runs", type=int, default=3, help="--vad: repetitions of every tick measurement")
+    ap.add_argument("--audio", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "tests", "golden",
+                                                    "jfk.flac"), help="--vad: the recording the composite is cut from")
     ap.add_argument("--windows", type=int, default=8, help="--pool: max_windows of the model, the most streams per round")
     args = ap.parse_args()
     import whisper
+    if args.vad:
+        for n in (1, 16, 64, 256):
+            print(json.dumps(vad_tick_cost(n, runs=args.runs)), flush=True)
+        for name in [m for m in (args.models or "turbo").split(",") if m]:
+            model = whisper.load_model(name, device=0, dtype="fp16", max_windows=1, max_group=5, synthetic=True)
+            print(json.dumps(vad_saving(model, name, args.audio)), flush=True)
+            model.close()
+        return
     if args.pool:
         for n in (1, 16, 64, 256):
             print(json.dumps(pool_tick_cost(n)), flush=True)

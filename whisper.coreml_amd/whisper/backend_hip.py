@@ -47,6 +47,17 @@ class WhVadOpts(ctypes.Structure):
                 ("min_silence", c_int), ("min_speech", c_int), ("pad", c_int)]
 
 
+class WhSvadOpts(ctypes.Structure):
+    _fields_ = [("ratio_q8", c_uint64), ("t_lo", c_uint64), ("t_hi", c_uint64), ("percentile", c_int),
+                ("window", c_int), ("min_silence", c_int), ("min_speech", c_int)]
+
+
+class WhSvadState(ctypes.Structure):
+    _fields_ = [(k, c_int64) for k in ("frames", "samples", "run_start", "run_end", "closed_start", "closed_end",
+                                       "closed_total")] + [("threshold", c_uint64), ("partial", c_uint64),
+                                                           ("state", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class WhWavFmt(ctypes.Structure):
     _fields_ = [("encoding", c_int), ("channels", c_int), ("sample_rate", c_int), ("valid_bits", c_int),
                 ("data_offset", c_int64), ("n_frames", c_int64)]
@@ -148,6 +159,11 @@ _EXPORTS = {
     "wh_pool_info": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int)]),
     "wh_pool_read": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64]),
     "wh_pool_log_mel": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "wh_pool_vad_enable": (c_int, [c_void_p, c_int, POINTER(WhSvadOpts)]),
+    "wh_pool_vad_state": (c_int, [c_void_p, c_int, c_void_p, POINTER(WhSvadState)]),
+    "wh_pool_vad_read": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "wh_stream_vad_enable": (c_int, [c_void_p, POINTER(WhSvadOpts)]),
+    "wh_stream_vad_state": (c_int, [c_void_p, POINTER(WhSvadState)]),
 }
 N_STATS = 16  # WH_N_STATS
 FLAC_PATHS = ("device", "host")
@@ -571,6 +587,48 @@ class HipContext:
         self._check(self.lib.wh_pool_log_mel(self.h, len(sl), _ptr(sl) if len(sl) else None, int(padding), n_mels,
                                              _ptr(base)), "wh_pool_log_mel")
         return base
+
+    # -- the causal speech detector of a live stream (include/whisper_hip.h)
+    @staticmethod
+    def _svad_opts(params) -> WhSvadOpts:
+        return WhSvadOpts(ratio_q8=int(params.ratio_q8), t_lo=int(params.t_lo), t_hi=int(params.t_hi),
+                          percentile=int(params.percentile), window=int(params.window),
+                          min_silence=int(params.min_silence), min_speech=int(params.min_speech))
+
+    @staticmethod
+    def _svad_state(s: WhSvadState):
+        from .vad import StreamVadState
+        return StreamVadState(*(int(getattr(s, k)) for k in StreamVadState._fields))
+
+    def pool_vad_enable(self, slot: int, params):
+        """Give ``slot`` (open, no frames taken yet) a detector; ``params``: ``vad.StreamVadParams``."""
+        o = self._svad_opts(params)
+        self._check(self.lib.wh_pool_vad_enable(self.h, int(slot), ctypes.byref(o)), "wh_pool_vad_enable")
+
+    def pool_vad_state(self, slots: Sequence[int]):
+        """``vad.StreamVadState`` of each detecting slot as of its last append or finish."""
+        sl = np.asarray(list(slots), dtype=np.int32).reshape(-1)
+        out = (WhSvadState * max(len(sl), 1))()
+        self._check(self.lib.wh_pool_vad_state(self.h, len(sl), _ptr(sl) if len(sl) else None, out), "wh_pool_vad_state")
+        return [self._svad_state(out[i]) for i in range(len(sl))]
+
+    def pool_vad_read(self, slot: int, window: int):
+        """(ring uint8 [window], hist uint32 [160]) of a detecting slot, for inspection."""
+        ring = np.zeros(max(int(window), 1), dtype=np.uint8)
+        hist = np.zeros(160, dtype=np.uint32)
+        self._check(self.lib.wh_pool_vad_read(self.h, int(slot), _ptr(ring), int(window), _ptr(hist)), "wh_pool_vad_read")
+        return ring[:max(int(window), 0)], hist
+
+    def stream_vad_enable(self, params):
+        """Give the open stream (no frames taken yet) a detector; ``params``: ``vad.StreamVadParams``."""
+        o = self._svad_opts(params)
+        self._check(self.lib.wh_stream_vad_enable(self.h, ctypes.byref(o)), "wh_stream_vad_enable")
+
+    def stream_vad_state(self):
+        """``vad.StreamVadState`` of the stream as of its last append or finish."""
+        out = WhSvadState()
+        self._check(self.lib.wh_stream_vad_state(self.h, ctypes.byref(out)), "wh_stream_vad_state")
+        return self._svad_state(out)
 
     def flac_decode_device(self, data: bytes):
         """``decode_flac`` on the device (wh_flac_decode_device): (samples int32

@@ -16,6 +16,13 @@ retracted; the buffer is trimmed behind them so that it stays inside one 30 s wi
 
 ``min_chunk``, ``buffer_trim``, ``max_buffer`` and ``prompt_chars`` are defaults of that paper's
 implementation; none of them has been measured on real speech with this backend.
+
+With ``vad=`` a stream carries a causal speech detector on the device (``vad.StreamVad`` is its
+numpy twin, include/whisper_hip.h its definition), updated inside the call that ingests the
+packets.  The policy reads its state at every decode point: a buffer without confirmed speech is
+not decoded (``StreamUpdate.idle``), the silence after an utterance ends it
+(``StreamUpdate.endpoint``: the pending words are committed at once) and the buffer is cut so
+that it starts just before the next onset.
 """
 
 import time
@@ -24,8 +31,9 @@ from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 
-from .audio import (MAX_DEVICE_TAPS, SAMPLE_RATE, WAV_CONTAINER, WAV_ENCODINGS, device_filter_taps, stream_emitted)
+from .audio import (HOP_LENGTH, MAX_DEVICE_TAPS, SAMPLE_RATE, WAV_CONTAINER, WAV_ENCODINGS, device_filter_taps, stream_emitted)
 
+SILENCE, ONSET, SPEECH = 0, 1, 2  # vad.StreamVadState.state
 _PREPEND = "\"'“¿([{-"
 _APPEND = "\"'.。,，!！?？:：”)]}、"
 # what an array handed to ``append`` must hold: the encoding's container (packed 24-bit and the
@@ -42,6 +50,21 @@ def _frame_bytes(data, encoding: str) -> bytes:
             raise TypeError(f"stream data for encoding {encoding!r} must be bytes or an array of {want}, not {data.dtype}")
         return np.ascontiguousarray(data).tobytes()
     return bytes(data)
+
+
+def resolve_vad(vad):
+    """``vad=`` of a stream: None (no detector), True (the defaults), a dict of
+    ``vad.resolve_stream_options``' options, or ``vad.StreamVadParams`` -> the params or None."""
+    from .vad import StreamVadParams, check_stream_params, resolve_stream_options
+    if vad is None or vad is False:
+        return None
+    if vad is True:
+        return resolve_stream_options()
+    if isinstance(vad, StreamVadParams):
+        return check_stream_params(vad)
+    if isinstance(vad, dict):
+        return resolve_stream_options(**vad)
+    raise TypeError(f"vad must be None, True, a dict of options or StreamVadParams, not {type(vad).__name__}")
 
 
 def _check_options(transcribe_options: dict, who: str) -> None:
@@ -62,9 +85,11 @@ class AudioStream:
     an ingest, ``transcribe`` of a path or an array) ends it: the next ``append`` then raises
     ``HipBackendError`` naming that call.  ``encoding``: one of ``audio.WAV_ENCODINGS``; the
     data are raw interleaved frames, no container.  A rate whose filter would exceed
-    ``audio.MAX_DEVICE_TAPS`` is refused (``ValueError``): there is no host path for a stream."""
+    ``audio.MAX_DEVICE_TAPS`` is refused (``ValueError``): there is no host path for a stream.
+    ``vad``: see ``resolve_vad``; the stream then carries a speech detector that every ``append``
+    and ``finish`` updates on the device, and ``vad_state`` is its state after the last of them."""
 
-    def __init__(self, model, rate: int, encoding: str = "s16", channels: int = 1, reserve: int = 0):
+    def __init__(self, model, rate: int, encoding: str = "s16", channels: int = 1, reserve: int = 0, vad=None):
         if encoding not in WAV_ENCODINGS:
             raise ValueError(f"encoding {encoding!r}: one of {', '.join(WAV_ENCODINGS)}")
         rate, channels = int(rate), int(channels)
@@ -73,6 +98,7 @@ class AudioStream:
         if device_filter_taps(rate) > MAX_DEVICE_TAPS:
             raise ValueError(f"rate {rate} Hz: its resampling filter has {device_filter_taps(rate)} taps, more than "
                              f"the device path takes ({MAX_DEVICE_TAPS}); resample the stream to a common rate first")
+        self.vad = resolve_vad(vad)
         from .audio import _device_index, _mel_context
         ctx = getattr(model, "ctx", model)
         if ctx is None or isinstance(ctx, (int, str)):
@@ -85,6 +111,13 @@ class AudioStream:
         self.finished = False
         self._tail = b""     # a trailing partial frame, waiting for its rest
         ctx.stream_begin(WAV_ENCODINGS.index(encoding), channels, rate, reserve=reserve)
+        if self.vad is not None:
+            ctx.stream_vad_enable(self.vad)
+
+    @property
+    def vad_state(self):
+        """``vad.StreamVadState`` after the last append or finish (None without ``vad``)."""
+        return self.ctx.stream_vad_state() if self.vad is not None else None
 
     def append(self, data) -> int:
         """Bytes-like data, or an array in the encoding's container dtype; a trailing partial
@@ -178,7 +211,10 @@ class StreamUpdate:
     ``(s0, s1)`` in absolute 16 kHz samples when it was decoded; ``prompt``: the
     ``initial_prompt`` the decode ran with; ``result``: what ``transcribe`` returned, times
     relative to the buffer start (None when nothing was decoded); ``forced``: pending words
-    were committed without agreement because the buffer had to be cut."""
+    were committed without agreement because the buffer had to be cut.  With a detector
+    (``vad=``): ``vad`` is its state at the decode point; ``idle``: the buffer held no confirmed
+    speech and was not decoded; ``endpoint``: the utterance in the buffer had ended, so the
+    pending words were committed with this update."""
     committed: List[dict] = field(default_factory=list)
     tentative: List[dict] = field(default_factory=list)
     span: Tuple[int, int] = (0, 0)
@@ -188,6 +224,9 @@ class StreamUpdate:
     forced: bool = False
     final: bool = False
     wall_ms: float = 0.0
+    idle: bool = False
+    endpoint: bool = False
+    vad: Optional[tuple] = None
 
 
 class StreamingTranscriber:
@@ -212,13 +251,28 @@ class StreamingTranscriber:
          t1 - buffer_trim.
     ``buffer_trim < max_buffer <= 30 - min_chunk`` keeps every decode inside one 30 s window.
 
+    With ``vad`` (True, a dict of ``vad.resolve_stream_options``' options, or its result) the
+    stream carries a speech detector and every decode point first reads its state ``st`` (frames
+    of 160 samples on the stream's absolute grid; ``pad`` in frames):
+    ``speech_end = st.frames if st.state == SPEECH else st.closed_end`` and
+    ``keep = (st.run_start if st.state == ONSET else st.frames) - pad``.
+      idle: ``160 * speech_end <= s0``, the buffer holds no confirmed speech.  No decode
+        (``result`` None, ``update.idle``), nothing committed, the buffer cut at frame ``keep``;
+        at ``finish`` the pending words are flushed.
+      endpoint: speech in the buffer and ``st.state != SPEECH``.  Decode and agreement as usual,
+        then the pending words are committed too (``update.endpoint``) and the buffer is cut at
+        frame ``max(st.closed_end, keep)``; rules 1-3 are skipped.
+      speech: ``st.state == SPEECH``: the update above, unchanged.
+    The decode points stay where they are, so the updates still depend on the samples alone.
+
     ``word_timestamps=False``, ``clip_timestamps``, ``channels``, ``schedule`` and
     ``mel_max_reduce`` are refused (``ValueError``).  ``stream`` and ``decode_fn(prompt, span)``
-    replace the device stream and the ``transcribe`` call (tests drive the policy without a GPU)."""
+    replace the device stream and the ``transcribe`` call (tests drive the policy without a GPU);
+    with ``vad`` such a ``stream`` has ``vad_state``."""
 
     def __init__(self, model, rate: int, encoding: str = "s16", channels: int = 1, *, language: Optional[str] = None,
                  min_chunk: float = 1.0, buffer_trim: float = 15.0, max_buffer: float = 25.0, prompt_chars: int = 200,
-                 initial_prompt: Optional[str] = None, stream=None,
+                 initial_prompt: Optional[str] = None, vad=None, stream=None,
                  decode_fn: Optional[Callable[[Optional[str], Tuple[int, int]], dict]] = None, **transcribe_options):
         _check_options(transcribe_options, "StreamingTranscriber")
         if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)):
@@ -245,7 +299,8 @@ class StreamingTranscriber:
         self.options = dict(transcribe_options)
         self.policy = LocalAgreement(self.options.get("prepend_punctuations", _PREPEND),
                                      self.options.get("append_punctuations", _APPEND))
-        self.stream = stream if stream is not None else AudioStream(model, rate, encoding, channels)
+        self.vad = resolve_vad(vad)
+        self.stream = stream if stream is not None else AudioStream(model, rate, encoding, channels, vad=self.vad)
         self._decode_fn = decode_fn
         self.frame_bytes = WAV_CONTAINER[WAV_ENCODINGS.index(encoding)] * self.channels
         self.frames_in = 0
@@ -334,6 +389,13 @@ class StreamingTranscriber:
             self.stream.trim(drop)
             self._s0 += drop
 
+    def _cut_frame(self, f: int) -> None:
+        """Drop the buffer's samples before frame ``f`` of the stream's grid (clipped to the buffer)."""
+        drop = min(max(HOP_LENGTH * int(f) - self._s0, 0), self._s1 - self._s0)
+        if drop:
+            self.stream.trim(drop)
+            self._s0 += drop
+
     def _update(self, final: bool) -> StreamUpdate:
         t_begin = time.perf_counter()
         u, due = self._begin_update(final)
@@ -344,7 +406,12 @@ class StreamingTranscriber:
         """The update of the buffer as it is, and whether it needs a decode (then with its prompt)."""
         s0, s1 = self._s0, self._s1
         u = StreamUpdate(span=(s0, s1), final=final, language=self.language)
-        due = s1 > s0 and (not final or s1 > self._decoded_s1)
+        if self.vad is not None:
+            st = u.vad = self.stream.vad_state
+            speech_end = st.frames if st.state == SPEECH else st.closed_end
+            u.idle = HOP_LENGTH * speech_end <= s0
+            u.endpoint = not u.idle and st.state != SPEECH
+        due = not u.idle and s1 > s0 and (not final or s1 > self._decoded_s1)
         if due:
             u.prompt = self.build_prompt(s0 / SAMPLE_RATE)
         return u, due
@@ -361,9 +428,14 @@ class StreamingTranscriber:
                      for s in result["segments"] for w in s.get("words", [])]
             u.committed = self.policy.update(words)
         u.result, u.language = result, self.language
-        if u.final:
+        if u.final or u.endpoint:
             u.committed = u.committed + self.policy.flush()
-        elif result is not None:
+        if u.idle or u.endpoint:
+            if not u.final:
+                st = u.vad
+                keep = (st.run_start if st.state == ONSET else st.frames) - self.vad.pad
+                self._cut_frame(keep if u.idle else max(st.closed_end, keep))
+        elif not u.final and result is not None:
             self._trim(u, result, t0)
         u.tentative = list(self.policy.pending)
         u.wall_ms = (time.perf_counter() - t_begin) * 1e3

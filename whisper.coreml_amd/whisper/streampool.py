@@ -34,7 +34,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .audio import MAX_DEVICE_TAPS, N_SAMPLES, SAMPLE_RATE, WAV_ENCODINGS, device_filter_taps
-from .streaming import StreamingTranscriber, StreamUpdate, _check_options, _frame_bytes
+from .streaming import StreamingTranscriber, StreamUpdate, _check_options, _frame_bytes, resolve_vad
 
 # 30 s of buffer (max_buffer + min_chunk <= 30 s) plus what the resamplers' rounding and the
 # samples a finish releases can add
@@ -53,6 +53,7 @@ class _SlotStream:
     def __init__(self, slot: int):
         self.slot = slot
         self.drop = 0
+        self.vad_state = None  # of a detecting stream: as of the batched call that reached its decode point
 
     def trim(self, n: int):
         self.drop += int(n)
@@ -70,13 +71,16 @@ class StreamingPool:
     ``initial_prompt``, ``min_chunk``, ``buffer_trim``, ``max_buffer`` and ``prompt_chars``, with
     ``StreamingTranscriber``'s checks and defaults; ``language=None`` is detected at the stream's
     first decode.  Everything ``StreamingTranscriber`` refuses is refused here (``ValueError``), and
-    so is ``skip_silence``: the span detector reads the context's resident segments, not a slot.
+    so is ``skip_silence``: the span detector reads the context's resident segments, not a slot;
+    ``open(vad=...)`` gives a stream the causal detector instead, per stream: a stream without
+    confirmed speech in its buffer then takes no lane of a round (``StreamUpdate.idle``), and a
+    tick in which nobody has speech runs no decode round at all.
 
     ``slot_samples``: the room of a slot in 16 kHz samples; the default holds the 30 s that
     ``max_buffer <= 30 - min_chunk`` allows.  ``device`` and ``decode_round_fn(items)`` replace
     the context's pool calls and the batched decode (tests drive the policy without a GPU):
-    ``device`` has ``pool_open / pool_close / pool_append / pool_finish / pool_trim`` as
-    ``HipContext`` does, ``items`` is a list of ``(handle, prompt, span)`` and the function
+    ``device`` has ``pool_open / pool_close / pool_append / pool_finish / pool_trim`` (and, for
+    ``open(vad=...)``, ``pool_vad_enable / pool_vad_state``) as ``HipContext`` does, ``items`` is a list of ``(handle, prompt, span)`` and the function
     returns one ``transcribe`` result dict per item."""
 
     def __init__(self, model, slots: int = 64, *, slot_samples: int = DEFAULT_SLOT_SAMPLES, device=None,
@@ -85,7 +89,8 @@ class StreamingPool:
         _check_options(transcribe_options, "StreamingPool")
         if transcribe_options.pop("skip_silence", False):
             raise ValueError("StreamingPool does not take skip_silence: the span detector reads the context's "
-                             "resident segments, not a pool slot")
+                             "resident segments, not a pool slot; give a stream its own causal detector with "
+                             "open(vad=...)")
         for name in _PER_STREAM:
             if name in transcribe_options:
                 raise ValueError(f"StreamingPool: {name} belongs to a stream, pass it to open()")
@@ -129,8 +134,9 @@ class StreamingPool:
 
     def open(self, rate: int, encoding: str = "s16", channels: int = 1, *, language: Optional[str] = None,
              initial_prompt: Optional[str] = None, min_chunk: float = 1.0, buffer_trim: float = 15.0,
-             max_buffer: float = 25.0, prompt_chars: int = 200) -> int:
-        """A new stream in a free slot; returns its handle."""
+             max_buffer: float = 25.0, prompt_chars: int = 200, vad=None) -> int:
+        """A new stream in a free slot; returns its handle.  ``vad``: as ``StreamingTranscriber``'s."""
+        vad = resolve_vad(vad)
         if encoding not in WAV_ENCODINGS:
             raise ValueError(f"encoding {encoding!r}: one of {', '.join(WAV_ENCODINGS)}")
         if int(rate) < 1:
@@ -143,8 +149,14 @@ class StreamingPool:
         slot = self._free[0]
         t = StreamingTranscriber(self.model, rate, encoding, channels, language=language, min_chunk=min_chunk,
                                  buffer_trim=buffer_trim, max_buffer=max_buffer, prompt_chars=prompt_chars,
-                                 initial_prompt=initial_prompt, stream=_SlotStream(slot), **self.options)
+                                 initial_prompt=initial_prompt, vad=vad, stream=_SlotStream(slot), **self.options)
         self.dev.pool_open(slot, WAV_ENCODINGS.index(encoding), t.channels, t.rate)
+        if vad is not None:
+            try:
+                self.dev.pool_vad_enable(slot, vad)
+            except Exception:
+                self.dev.pool_close(slot)
+                raise
         self._free.pop(0)
         handle = self._next_handle
         self._next_handle += 1
@@ -197,6 +209,7 @@ class StreamingPool:
                     due.append(h)
             # 2. - 4. the due streams, together
             if due:
+                self._read_vad(due)
                 for h, u in zip(due, self._update_round(due, final=False)):
                     out[h].append(u)
 
@@ -213,6 +226,7 @@ class StreamingPool:
             t.finished = True
             t._tail = b""
             t._s1 += g
+        self._read_vad(handles)
         updates = self._update_round(handles, final=True)
         for h, t in zip(handles, streams):
             self.dev.pool_close(t.stream.slot)
@@ -221,6 +235,13 @@ class StreamingPool:
             del self._streams[h]
             self._ended.add(h)
         return dict(zip(handles, updates))
+
+    def _read_vad(self, handles: Sequence[int]) -> None:
+        """The detecting streams' states as the batched call just left them (a host copy: no device call)."""
+        streams = [self._streams[h].stream for h in handles if self._streams[h].vad is not None]
+        if streams:
+            for s, st in zip(streams, self.dev.pool_vad_state([s.slot for s in streams])):
+                s.vad_state = st
 
     # -- one round of updates
     def _update_round(self, handles: List[int], final: bool) -> List[StreamUpdate]:

@@ -212,3 +212,174 @@ def speech_spans(model, audio, **opts) -> List[Tuple[float, float]]:
     if audio.offset:
         raise ValueError("DeviceAudio is a segment behind other files: speech_spans() takes the first resident one")
     return frames_to_seconds(resident_spans(ctx, 1, p)[0][0])
+
+
+# ---------------------------------------------------------------- live streams
+# The causal detector of a live stream (wh_pool_vad_* / wh_stream_vad_*, csrc/wh_svad.hip):
+# steps 1-3 above on an absolute frame grid (frame f is the stream's emitted samples
+# [160 f, 160 f + 160), whatever was trimmed), the noise level taken over the last ``window``
+# frames only, and step 5's rules evaluated frame by frame.  include/whisper_hip.h holds the
+# definition; ``StreamVad`` restates it in numpy and is what the tests compare the kernel with.
+SILENCE, ONSET, SPEECH = 0, 1, 2
+MAX_WINDOW = 6000
+MAX_RUN_FRAMES = 1 << 20
+
+STREAM_DEFAULTS = dict(DEFAULTS, min_silence=0.5, window=30.0)
+
+
+class StreamVadParams(NamedTuple):
+    """The integers of the streaming definition (``wh_svad_opts``); durations in frames.  ``pad``
+    is the policy's (``StreamingTranscriber``): the detector reports unpadded frames."""
+    percentile: int
+    ratio_q8: int
+    t_lo: int
+    t_hi: int
+    window: int
+    min_silence: int
+    min_speech: int
+    pad: int = 0
+
+
+class StreamVadState(NamedTuple):
+    """``wh_svad_state``.  ``run_start`` / ``run_end`` mean something only while ``state`` is not
+    SILENCE; ``closed_*`` is the last span that ended (``closed_total`` of them so far)."""
+    frames: int = 0
+    samples: int = 0
+    run_start: int = 0
+    run_end: int = 0
+    closed_start: int = 0
+    closed_end: int = 0
+    closed_total: int = 0
+    threshold: int = 0
+    partial: int = 0
+    state: int = SILENCE
+
+
+def resolve_stream_options(**opts) -> StreamVadParams:
+    """User options of a stream's detector -> ``StreamVadParams``: ``DEFAULTS``' keys plus
+    ``window``, the seconds the noise percentile looks back (default 30.0, at most 60).
+    ``min_silence`` defaults to 0.5 s here: on a stream it is the endpointing delay, the
+    silence after which an utterance counts as over, not a file's rule for joining clips.
+    Neither that value nor the window has been measured on real speech with this project.
+    Raises ValueError on an unknown option or a value out of range."""
+    unknown = set(opts) - set(STREAM_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown stream speech option(s) {sorted(unknown)}; known: {sorted(STREAM_DEFAULTS)}")
+    o = dict(STREAM_DEFAULTS, **opts)
+    w = o.pop("window")
+    if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)) or not np.isfinite(w):
+        raise ValueError(f"window must be a finite number, not {w!r}")
+    window = int(round(float(w) * FRAMES_PER_SECOND))
+    if not 1 <= window <= MAX_WINDOW:
+        raise ValueError(f"window = {w!r} s is outside one frame .. {MAX_WINDOW // FRAMES_PER_SECOND} s")
+    p = resolve_options(**o)
+    if not 1 <= p.min_silence <= MAX_RUN_FRAMES:
+        raise ValueError(f"min_silence = {o['min_silence']!r} s: on a stream it is at least one frame and at most "
+                         f"{MAX_RUN_FRAMES} frames")
+    if p.min_speech > MAX_RUN_FRAMES or p.pad > MAX_RUN_FRAMES:
+        raise ValueError(f"min_speech / pad = {o['min_speech']!r} / {o['pad']!r} s is out of range")
+    return StreamVadParams(percentile=p.percentile, ratio_q8=p.ratio_q8, t_lo=p.t_lo, t_hi=p.t_hi, window=window,
+                           min_silence=p.min_silence, min_speech=p.min_speech, pad=p.pad)
+
+
+def check_stream_params(p: StreamVadParams) -> StreamVadParams:
+    """The ranges ``wh_pool_vad_enable`` accepts (ValueError otherwise)."""
+    if not 1 <= p.percentile <= 99:
+        raise ValueError(f"percentile = {p.percentile} outside 1..99")
+    if not 256 <= p.ratio_q8 <= 2560000:
+        raise ValueError(f"ratio_q8 = {p.ratio_q8} outside [256, 2560000]")
+    if not 0 <= p.t_lo <= p.t_hi < 1 << 64:
+        raise ValueError(f"need 0 <= t_lo <= t_hi, not {p.t_lo}, {p.t_hi}")
+    if not 1 <= p.window <= MAX_WINDOW:
+        raise ValueError(f"window = {p.window} outside 1..{MAX_WINDOW}")
+    if not 1 <= p.min_silence <= MAX_RUN_FRAMES:
+        raise ValueError(f"min_silence = {p.min_silence} outside 1..2^20")
+    if not 0 <= p.min_speech <= MAX_RUN_FRAMES:
+        raise ValueError(f"min_speech = {p.min_speech} outside 0..2^20")
+    return p
+
+
+class StreamVad:
+    """The numpy twin of the device detector: ``feed(samples)`` takes the 16 kHz float32 samples
+    a stream emitted, ``finish()`` closes a last incomplete frame with zeros; both return the
+    ``StreamVadState``.  ``hist`` (uint32 [160]) and ``ring`` (uint8 [window]) are the state
+    ``wh_pool_vad_read`` shows; ``spans`` lists every closed span and ``thresholds`` the ``T`` of
+    every frame (the device keeps only the last of each)."""
+
+    def __init__(self, params: StreamVadParams):
+        self.p = check_stream_params(params)
+        self.hist = np.zeros(N_BINS, dtype=np.uint32)
+        self.ring = np.zeros(params.window, dtype=np.uint8)
+        self.frames = self.samples = self.partial = 0
+        self.mode = SILENCE
+        self.run_start = self.run_end = self.closed_start = self.closed_end = self.closed_total = 0
+        self.threshold = 0
+        self.finished = False
+        self.spans: List[Tuple[int, int]] = []
+        self.thresholds: List[int] = []
+        self.onsets_dropped = 0
+
+    @property
+    def state(self) -> StreamVadState:
+        return StreamVadState(self.frames, self.samples, self.run_start, self.run_end, self.closed_start,
+                              self.closed_end, self.closed_total, self.threshold, self.partial, self.mode)
+
+    def _close(self, e: int) -> None:
+        p, f = self.p, self.frames
+        b = energy_bin(e)
+        self.hist[b] += 1
+        if f >= p.window:
+            self.hist[self.ring[f % p.window]] -= 1
+        self.ring[f % p.window] = b
+        n = min(f + 1, p.window)
+        rank = max(1, -(-n * p.percentile // 100))
+        noise = bin_edge(int(np.searchsorted(np.cumsum(self.hist, dtype=np.int64), rank)))
+        t = min(max((noise * p.ratio_q8) >> 8, p.t_lo), p.t_hi)
+        if e > t:
+            if self.mode == SILENCE:
+                self.mode, self.run_start = ONSET, f
+            self.run_end = f + 1
+            if self.mode == ONSET and self.run_end - self.run_start >= p.min_speech:
+                self.mode = SPEECH
+        elif self.mode != SILENCE and f + 1 - self.run_end >= p.min_silence:
+            if self.mode == SPEECH:
+                self.closed_start, self.closed_end = self.run_start, self.run_end
+                self.closed_total += 1
+                self.spans.append((self.run_start, self.run_end))
+            else:
+                self.onsets_dropped += 1
+            self.mode = SILENCE
+        self.frames, self.threshold = f + 1, t
+        self.thresholds.append(t)
+
+    def feed(self, samples) -> StreamVadState:
+        if self.finished:
+            raise ValueError("feed() after finish()")
+        q = quantise(samples).astype(np.int64)
+        sq = q * q
+        i, n = 0, len(sq)
+        fill = self.samples % HOP_LENGTH
+        if fill and n:
+            i = min(HOP_LENGTH - fill, n)
+            self.partial += int(sq[:i].sum())
+            self.samples += i
+            if self.samples % HOP_LENGTH == 0:
+                e, self.partial = self.partial, 0
+                self._close(e)
+        whole = (n - i) // HOP_LENGTH
+        for e in sq[i:i + whole * HOP_LENGTH].reshape(whole, HOP_LENGTH).sum(axis=1).tolist():
+            self.samples += HOP_LENGTH
+            self._close(int(e))
+        rest = sq[i + whole * HOP_LENGTH:]
+        if len(rest):
+            self.partial += int(rest.sum())
+            self.samples += len(rest)
+        return self.state
+
+    def finish(self) -> StreamVadState:
+        if not self.finished:
+            self.finished = True
+            if self.samples % HOP_LENGTH:
+                e, self.partial = self.partial, 0
+                self._close(e)
+        return self.state
