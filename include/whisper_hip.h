@@ -331,6 +331,43 @@ int wh_align_batch(wh_ctx* ctx, int n_win, const int* slots, const int* tokens, 
    path [2][n_rows + n_cols], *path_len valid entries of each */
 int wh_dtw(wh_ctx* ctx, const float* x, int n_rows, int n_cols, int* path, int* path_len);
 
+/* Open-end DTW: forced alignment past one window (whisper/align.py).  wh_dtw forces all N
+   rows onto all M columns because its backtrace starts at the corner (N, M); here the end
+   row is free, so the result says how many of the offered rows the columns account for.
+   For x [N][M]:
+     cost         exactly wh_dtw's: cost[0][0] = 0, the rest of row 0 and column 0 +inf,
+                  cost[i][j] = fl32(fl64(x[i-1][j-1]) + fl64(c)), c chosen among
+                  c0 = cost[i-1][j-1], c1 = cost[i-1][j], c2 = cost[i][j-1] by the tie order
+                  (c0 < c1 && c0 < c2 -> 0, else c1 < c0 && c1 < c2 -> 1, else 2)
+     score[i]     fl32(fl64(cost[i][M]) + fl64(row_penalty) * i), i = 1..N
+     end_row e    the smallest i in [min_rows, N] with the smallest score[i] (fp32 compare)
+     path         the backtrace from (e, M) by wh_dtw's trace rules, reversed as there;
+                  path_len <= e + M, the buffers keep the size [2][N + M]
+   min_rows in 1..N and a finite row_penalty >= 0 (an fp32 value).  min_rows == 0 means
+   closed: e = N and the path is wh_dtw's, bit for bit.  The penalty is what keeps the end
+   from overshooting: without one, a row beyond the spoken text can always be entered by a
+   diagonal step through one frame whose z-score happens to be positive.  whisper/align.py
+   uses 4.0 (a token must own evidence worth about two frames at 2 sigma); that value comes
+   from planted z-normalised matrices and has NOT been measured on real speech.
+   end_scores (nullable) [n_rows] = score[1..N].  Refused before any HIP call, with a negative
+   code and wh_last_error naming the field: a null pointer, min_rows outside 0..n_rows, a
+   negative / NaN / infinite row_penalty, n_rows > 1023. */
+int wh_dtw_open(wh_ctx* ctx, const float* x, int n_rows, int n_cols, int min_rows, float row_penalty, int* path,
+                int* path_len, int* end_row, float* end_scores);
+/* wh_align_batch with an open-end DTW per window: min_rows[w] == 0 runs window w closed
+   (its results equal wh_align_batch's), otherwise its DTW ends at the best row >= min_rows[w]
+   under row_penalty.  The matrix of window w has N = T_w + 1 rows as in wh_align_batch: the
+   text tokens, then the row that predicts eot; end_rows[w] = T_w + 1 means that all the text
+   and the trailing non-speech fit.  token_probs, paths and path_lens are laid out as in
+   wh_align_batch (paths [2][T_w + 1 + num_frames[w]/2] per window, path_lens[w] <= end_rows[w]
+   + num_frames[w]/2 valid).  Refuses what wh_dtw_open and wh_align_batch refuse.  Like
+   wh_prefill_logits it writes the self-KV rows of every slot it is given: call it on slots
+   whose decode has finished or that are not in the current batch. */
+int wh_align_batch_open(wh_ctx* ctx, int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
+                        const int* num_frames, const int* align_heads, int n_align, int medfilt_width,
+                        const int* min_rows, float row_penalty, float* token_probs, int* paths, int* path_lens,
+                        int* end_rows);
+
 /* the kernels the decoder step runs for a batch of n_win windows x group rows, as
    "proj=<name>,xattn=<name>" (the dominant projection family and the cross-attention;
    what bench.py labels its roofline lines with).  Returns the length written. */

@@ -126,10 +126,15 @@ __global__ __launch_bounds__(256) void k_align_medmean(const float* __restrict__
 // PF) — only LDS traffic sits between two barriers.  The trace is packed 2 bits per
 // cell: in LDS when it fits (LDS_TRACE, the backtrace then walks LDS), otherwise in
 // the global scratch.  path: [2][N+M] (text indices, then time indices).
+// OPEN (open-end DTW, include/whisper_hip.h): lane i also keeps cost[i][M]; after the
+// sweep score[i] = fl32(fl64(cost[i][M]) + fl64(row_penalty) * i), the end row e is the
+// lowest-index minimum over rows min_rows..N (wave butterfly, then the per-wave winners
+// through the diagonal buffers, which are free by then), and lane 0 backtraces from
+// (e, M).  The closed form (OPEN = false) compiles to the code it was before OPEN existed.
 constexpr int DTW_THREADS = 1024;
 constexpr int DTW_MAXN = 1023;
 constexpr int DTW_PF = 8;
-template <bool LDS_TRACE>
+template <bool LDS_TRACE, bool OPEN>
 __global__ __launch_bounds__(DTW_THREADS) void k_dtw(const DtwJob* __restrict__ jobs, float sign) {
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   typedef __attribute__((address_space(1))) const float gfloat;
@@ -156,6 +161,7 @@ __global__ __launch_bounds__(DTW_THREADS) void k_dtw(const DtwJob* __restrict__ 
 #pragma unroll
   for (int k = 0; k < DTW_PF; ++k) q[k] = xat(1 + k);
   unsigned tw = 0;  // trace word being filled by this row
+  float last = INFINITY;  // OPEN: cost[i][M]
   const int im1 = i > 0 ? i - 1 : 0;
   __syncthreads();
   for (int d0 = 1; d0 <= N + M; d0 += DTW_PF) {
@@ -173,6 +179,7 @@ __global__ __launch_bounds__(DTW_THREADS) void k_dtw(const DtwJob* __restrict__ 
       const unsigned t = t0 ? 0u : (t1 ? 1u : 2u);
       const float cost = (float)((double)(sign * q[k]) + (double)c);
       if (d <= N + M) cur[i] = inner ? cost : INFINITY;
+      if constexpr (OPEN) last = (inner && j == M) ? cost : last;
       const int sh = (j & 15) * 2;
       tw = inner ? ((tw & ~(3u << sh)) | (t << sh)) : tw;
       if (inner && ((j & 15) == 15 || j == M)) {
@@ -186,10 +193,41 @@ __global__ __launch_bounds__(DTW_THREADS) void k_dtw(const DtwJob* __restrict__ 
     }
   }
   __syncthreads();
-  if (tid != 0) return;
+  int e = N;  // end row
+  if constexpr (OPEN) {
+    const bool row = i >= 1 && i <= N;
+    const float score = (float)((double)last + (double)jb.row_penalty * (double)i);
+    if (row && jb.scores) jb.scores[i - 1] = score;
+    // (score, row) minimum, the lower row on ties; rows outside min_rows..N never win
+    float bs = row && i >= jb.min_rows ? score : INFINITY;
+    int bi = row && i >= jb.min_rows ? i : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float os = __shfl_xor(bs, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      const bool take = os < bs || (os == bs && oi < bi);
+      bs = take ? os : bs;
+      bi = take ? oi : bi;
+    }
+    int* wrow = reinterpret_cast<int*>(dg + DS);  // second diagonal buffer: the waves' rows
+    if ((tid & 63) == 0) { dg[tid >> 6] = bs; wrow[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid != 0) return;
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
+      const float os = dg[w];
+      const int oi = wrow[w];
+      const bool take = os < bs || (os == bs && oi < bi);
+      bs = take ? os : bs;
+      bi = take ? oi : bi;
+    }
+    e = bi >= 1 && bi <= N ? bi : N;  // NaN scores only: stay inside the trace
+    *jb.end_row = e;
+  } else {
+    if (tid != 0) return;
+  }
   // backtrace (timing.py:57-79): trace[0][:] = 2, trace[:][0] = 1
   int* path = jb.path;
-  int a = N, b = M, n = 0;
+  int a = e, b = M, n = 0;
   while (a > 0 || b > 0) {
     path[n] = a - 1;
     path[(N + M) + n] = b - 1;
@@ -222,6 +260,8 @@ int dtw_prepare(DtwJob* jobs, int n, size_t* lds) {
   for (int k = 0; k < n; ++k) {
     const DtwJob& j = jobs[k];
     if (j.N < 1 || j.M < 1 || j.N > DTW_MAXN) return -1;
+    if (j.min_rows < 0 || j.min_rows > j.N || !(j.row_penalty >= 0.f) || std::isinf(j.row_penalty)) return -1;
+    if (j.min_rows > 0 && !j.end_row) return -1;
     max_n = std::max(max_n, j.N);
     tmax = std::max(tmax, dtw_trace_bytes(j.N, j.M));
   }
@@ -232,19 +272,27 @@ int dtw_prepare(DtwJob* jobs, int n, size_t* lds) {
   return 0;
 }
 
-int launch_dtw_jobs(const DtwJob* d_jobs, int n, int max_n, int in_lds, size_t lds, float sign, hipStream_t st) {
+int launch_dtw_jobs(const DtwJob* d_jobs, int n, int max_n, int in_lds, size_t lds, float sign, bool open,
+                    hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dtw<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)DTW_LDS) != hipSuccess)
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dtw<true, false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)DTW_LDS) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dtw<true, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)DTW_LDS) != hipSuccess)
       return -2;
     attr = true;
   }
   // one lane per row: the fewer waves, the cheaper each diagonal's barrier
   const int threads = dtw_threads(max_n);
   if (n <= 0) return 0;
-  if (in_lds) k_dtw<true><<<n, threads, lds, st>>>(d_jobs, sign), wh_launched("k_dtw");
-  else k_dtw<false><<<n, threads, lds, st>>>(d_jobs, sign), wh_launched("k_dtw");
+  if (open) {
+    if (in_lds) k_dtw<true, true><<<n, threads, lds, st>>>(d_jobs, sign), wh_launched("k_dtw_open");
+    else k_dtw<false, true><<<n, threads, lds, st>>>(d_jobs, sign), wh_launched("k_dtw_open");
+    return 0;
+  }
+  if (in_lds) k_dtw<true, false><<<n, threads, lds, st>>>(d_jobs, sign), wh_launched("k_dtw");
+  else k_dtw<false, false><<<n, threads, lds, st>>>(d_jobs, sign), wh_launched("k_dtw");
   return 0;
 }
 

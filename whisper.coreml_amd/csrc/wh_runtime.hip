@@ -98,6 +98,11 @@ struct wh_ctx {
                           const int* num_frames, const int* ah, int na, int medfilt, float* probs, int* paths,
                           int* plens) = 0;
   virtual int dtw(const float* x, int N, int M, int* path, int* plen) = 0;
+  virtual int align_batch_open(int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
+                               const int* num_frames, const int* ah, int na, int medfilt, const int* min_rows,
+                               float row_penalty, float* probs, int* paths, int* plens, int* end_rows) = 0;
+  virtual int dtw_open(const float* x, int N, int M, int min_rows, float row_penalty, int* path, int* plen,
+                       int* end_row, float* scores) = 0;
   virtual int time_stage(int what, int iters, double* ms) = 0;
   // tuning builds only (wh_tune_share_weights): read the weights of another context of the
   // same dims and dtype instead of this one's (probes of two window groups, one weight copy)
@@ -1444,6 +1449,26 @@ struct Ctx : public wh_ctx {
   int align_batch(int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
                   const int* num_frames, const int* ah, int na, int medfilt, float* probs, int* paths,
                   int* plens) override {
+    return align_windows(n_win, slots, tokens, n_tokens, n_sot, num_frames, ah, na, medfilt, nullptr, 0.f, probs, paths,
+                         plens, nullptr);
+  }
+
+  // wh_align_batch_open: the same pipeline, with the open-end DTW for the windows whose
+  // min_rows is not 0.  All DTWs of a pass still go in one launch: a closed window runs
+  // the open kernel with min_rows = N, which leaves it the end row N and wh_dtw's path.
+  // The slot rule of the first pass holds: it writes beam slot 0's self-KV rows of every
+  // slot it is given (check_slot_idle), so the windows of one call need a slot each.
+  int align_batch_open(int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
+                       const int* num_frames, const int* ah, int na, int medfilt, const int* min_rows,
+                       float row_penalty, float* probs, int* paths, int* plens, int* end_rows) override {
+    return align_windows(n_win, slots, tokens, n_tokens, n_sot, num_frames, ah, na, medfilt, min_rows, row_penalty,
+                         probs, paths, plens, end_rows);
+  }
+
+  // min_rows == nullptr: closed (wh_align_batch); otherwise per window, 0 = closed
+  int align_windows(int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
+                    const int* num_frames, const int* ah, int na, int medfilt, const int* min_rows, float row_penalty,
+                    float* probs, int* paths, int* plens, int* end_rows) {
     if (!finalized) return fail(-9, "weights not finalized");
     if (n_win < 1) return fail(-15, "align: no windows");
     if (na < 1 || na > Ld * nh) return fail(-15, "align: alignment head count");
@@ -1473,7 +1498,7 @@ struct Ctx : public wh_ctx {
     const size_t b_qk = al((size_t)qk_row * cap), b_lg = al((size_t)128 * V * 4), b_mat = al(mat_off[n_win] * 4),
                  b_tr = al(tr_off[n_win]), b_path = al(path_off[n_win] * 4), b_pr = al(prob_off[n_win] * 4 + 16),
                  b_pl = al((size_t)n_win * 4), b_jobs = al((size_t)n_win * sizeof(DtwJob));
-    TRY(ensure_scratch(b_qk + b_lg + b_mat + b_tr + b_path + 2 * b_pr + b_pl + b_jobs));
+    TRY(ensure_scratch(b_qk + b_lg + b_mat + b_tr + b_path + 2 * b_pr + 2 * b_pl + b_jobs));
     char* p = scratch.p;
     float* d_qk = (float*)p; p += b_qk;
     float* d_lg = (float*)p; p += b_lg;
@@ -1483,6 +1508,7 @@ struct Ctx : public wh_ctx {
     float* d_probs = (float*)p; p += b_pr;
     int* d_ptok = (int*)p; p += b_pr;
     int* d_plen = (int*)p; p += b_pl;
+    int* d_end = (int*)p; p += b_pl;
     DtwJob* d_jobs = (DtwJob*)p;
 
     // token of every probability row (timing.py:191: text_tokens[k])
@@ -1538,19 +1564,25 @@ struct Ctx : public wh_ctx {
         launch_align_matrix(d_qk + (int64_t)wr0[i] * 1500, (int64_t)R * 1500, n_tokens[w], 1500, F, na, n_sot, N,
                             medfilt, mat, st);
         jobs[w] = DtwJob{mat, (unsigned*)(d_tr + tr_off[w]), d_path + path_off[w], d_plen + w, N, F, 0};
+        if (min_rows) {
+          jobs[w].min_rows = min_rows[w] ? min_rows[w] : N;
+          jobs[w].row_penalty = row_penalty;
+          jobs[w].end_row = d_end + w;
+        }
       }
       size_t lds = 0;
       if (dtw_prepare(jobs.data() + w0, nw, &lds)) return fail(-15, "align: DTW shape");
       HIPCHK(hipMemcpyAsync(d_jobs + w0, jobs.data() + w0, nw * sizeof(DtwJob), hipMemcpyHostToDevice, st));
       int max_n = 0;
       for (int i = 0; i < nw; ++i) max_n = std::max(max_n, jobs[w0 + i].N);
-      if (launch_dtw_jobs(d_jobs + w0, nw, max_n, jobs[w0].in_lds, lds, -1.f, st))
+      if (launch_dtw_jobs(d_jobs + w0, nw, max_n, jobs[w0].in_lds, lds, -1.f, min_rows != nullptr, st))
         return fail(-15, "align: DTW launch");
       HIPCHK(hipStreamSynchronize(st));  // host row vectors of this pass go out of scope
       w0 += nw;
     }
     HIPCHK(hipMemcpyAsync(probs, d_probs, prob_off[n_win] * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(plens, d_plen, n_win * 4, hipMemcpyDeviceToHost, st));
+    if (min_rows) HIPCHK(hipMemcpyAsync(end_rows, d_end, n_win * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(paths, d_path, path_off[n_win] * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     TRY(launch_status(__func__));
@@ -1579,11 +1611,47 @@ struct Ctx : public wh_ctx {
     if (dtw_prepare(&job, 1, &lds)) return fail(-15, "dtw: shape");
     HIPCHK(hipMemcpyAsync(d_x, x, (size_t)N * M * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_job, &job, sizeof(job), hipMemcpyHostToDevice, st));
-    if (launch_dtw_jobs(d_job, 1, N, job.in_lds, lds, 1.f, st)) return fail(-15, "dtw launch");
+    if (launch_dtw_jobs(d_job, 1, N, job.in_lds, lds, 1.f, false, st)) return fail(-15, "dtw launch");
     HIPCHK(hipMemcpyAsync(plen, d_plen, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(path, d_path, (size_t)2 * (N + M) * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     TRY(launch_status(__func__));
+    return 0;
+  }
+
+  // wh_dtw_open: the open-end DTW of a host cost matrix (min_rows == 0: closed, run as
+  // min_rows = N, which gives wh_dtw's path and still fills the scores)
+  int dtw_open(const float* x, int N, int M, int min_rows, float row_penalty, int* path, int* plen, int* end_row,
+               float* scores) override {
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t b_x = al((size_t)N * M * 4), b_tr = al(dtw_trace_bytes(N, M)), b_path = al((size_t)2 * (N + M) * 4),
+                 b_sc = al((size_t)N * 4);
+    TRY(ensure_scratch(b_x + b_tr + b_path + b_sc + 256 + al(sizeof(DtwJob))));
+    char* p = scratch.p;
+    float* d_x = (float*)p; p += b_x;
+    unsigned* d_tr = (unsigned*)p; p += b_tr;
+    int* d_path = (int*)p; p += b_path;
+    float* d_sc = (float*)p; p += b_sc;
+    int* d_plen = (int*)p; p += 256;  // [0] path length, [1] end row
+    DtwJob* d_job = (DtwJob*)p;
+    DtwJob job{d_x, d_tr, d_path, d_plen, N, M, 0};
+    job.min_rows = min_rows ? min_rows : N;
+    job.row_penalty = row_penalty;
+    job.end_row = d_plen + 1;
+    job.scores = scores ? d_sc : nullptr;
+    size_t lds = 0;
+    if (dtw_prepare(&job, 1, &lds)) return fail(-15, "dtw_open: shape");
+    HIPCHK(hipMemcpyAsync(d_x, x, (size_t)N * M * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_job, &job, sizeof(job), hipMemcpyHostToDevice, st));
+    if (launch_dtw_jobs(d_job, 1, N, job.in_lds, lds, 1.f, true, st)) return fail(-15, "dtw_open launch");
+    int pe[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(pe, d_plen, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(path, d_path, (size_t)2 * (N + M) * 4, hipMemcpyDeviceToHost, st));
+    if (scores) HIPCHK(hipMemcpyAsync(scores, d_sc, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(launch_status(__func__));
+    *plen = pe[0];
+    *end_row = pe[1];
     return 0;
   }
 
@@ -2013,6 +2081,37 @@ int wh_align_batch(wh_ctx* ctx, int n_win, const int* slots, const int* tokens, 
 }
 int wh_dtw(wh_ctx* ctx, const float* x, int n_rows, int n_cols, int* path, int* path_len) {
   CTXCALL(ctx->dtw(x, n_rows, n_cols, path, path_len));
+}
+int wh_dtw_open(wh_ctx* ctx, const float* x, int n_rows, int n_cols, int min_rows, float row_penalty, int* path,
+                int* path_len, int* end_row, float* end_scores) {
+  // refused here, before the context is entered (no HIP call yet)
+  if (!x || !path || !path_len || !end_row) return fail(-1, "wh_dtw_open: null argument (x, path, path_len or end_row)");
+  if (n_rows > 1023) return fail(-15, "wh_dtw_open: n_rows above 1023");
+  if (n_rows < 1 || n_cols < 1 || (int64_t)n_rows * n_cols > (int64_t)1 << 26)
+    return fail(-15, "wh_dtw_open: n_rows / n_cols out of range");
+  if (min_rows < 0 || min_rows > n_rows) return fail(-15, "wh_dtw_open: min_rows outside 0..n_rows");
+  if (!(row_penalty >= 0.f) || std::isinf(row_penalty))
+    return fail(-15, "wh_dtw_open: row_penalty must be finite and >= 0");
+  CTXCALL(ctx->dtw_open(x, n_rows, n_cols, min_rows, row_penalty, path, path_len, end_row, end_scores));
+}
+int wh_align_batch_open(wh_ctx* ctx, int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
+                        const int* num_frames, const int* align_heads, int n_align, int medfilt_width,
+                        const int* min_rows, float row_penalty, float* token_probs, int* paths, int* path_lens,
+                        int* end_rows) {
+  // refused here, before the context is entered (no HIP call yet)
+  if (!slots || !tokens || !n_tokens || !num_frames || !align_heads || !min_rows || !token_probs || !paths ||
+      !path_lens || !end_rows)
+    return fail(-1, "wh_align_batch_open: null argument");
+  if (!(row_penalty >= 0.f) || std::isinf(row_penalty))
+    return fail(-15, "wh_align_batch_open: row_penalty must be finite and >= 0");
+  for (int w = 0; w < n_win; ++w) {
+    const int n_rows = n_tokens[w] - n_sot - 1;  // the text tokens and the row that predicts eot
+    if (n_rows > 1023) return fail(-15, "wh_align_batch_open: n_rows above 1023 (window " + std::to_string(w) + ")");
+    if (min_rows[w] < 0 || min_rows[w] > std::max(n_rows, 0))
+      return fail(-15, "wh_align_batch_open: min_rows of window " + std::to_string(w) + " outside 0..n_rows");
+  }
+  CTXCALL(ctx->align_batch_open(n_win, slots, tokens, n_tokens, n_sot, num_frames, align_heads, n_align, medfilt_width,
+                                min_rows, row_penalty, token_probs, paths, path_lens, end_rows));
 }
 int wh_stats(wh_ctx* ctx, double* out, int n) {
   if (!ctx || !out) return fail(-1, "null argument");

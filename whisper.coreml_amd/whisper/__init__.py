@@ -29,6 +29,7 @@ from .multifile import merge_channels, transcribe_batch
 from .vad import speech_spans, speech_spans_host
 from .streaming import AudioStream, LocalAgreement, StreamingTranscriber, StreamUpdate
 from .streampool import StreamingPool
+from .align import align, align_batch, dtw_open
 
 __version__ = "20240930+hip1"
 
@@ -118,4 +119,4 @@ def load_model(name: str, device: Optional[Union[str, int]] = None, download_roo
 __all__ = ["available_models", "load_model", "transcribe", "transcribe_batch", "merge_channels", "load_audio_channels", "speech_spans", "speech_spans_host", "decode", "detect_language", "DecodingOptions",
            "DecodingResult", "log_mel_spectrogram", "pad_or_trim", "load_audio", "load_audio_device", "ModelDimensions",
            "Whisper", "HipBackendError", "AudioStream", "LocalAgreement", "StreamingTranscriber", "StreamUpdate",
-           "StreamingPool"]
+           "StreamingPool", "align", "align_batch", "dtw_open"]

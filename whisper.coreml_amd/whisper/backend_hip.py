@@ -118,6 +118,10 @@ _EXPORTS = {
     "wh_align_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                c_int, c_void_p, c_void_p, c_void_p]),
     "wh_dtw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, POINTER(c_int)]),
+    "wh_dtw_open": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, POINTER(c_int),
+                            POINTER(c_int), c_void_p]),
+    "wh_align_batch_open": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                    c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wh_stats": (c_int, [c_void_p, POINTER(c_double), c_int]),
     "wh_sync": (c_int, [c_void_p]),
     "wh_time_stage": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
@@ -879,6 +883,39 @@ class HipContext:
             qo += 2 * W
         return out
 
+    def align_batch_open(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], n_sot: int,
+                         num_frames: Sequence[int], align_heads: Sequence[int], min_rows: Sequence[int],
+                         row_penalty: float, medfilt_width: int = 7):
+        """wh_align_batch_open: one (probs, text_indices, time_indices, end_row) per window;
+        ``min_rows[w] == 0`` runs window w closed.  It writes the self-KV rows of the slots."""
+        n = len(slots)
+        toks = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.int32) for t in token_lists]))
+        ntok = np.asarray([len(t) for t in token_lists], dtype=np.int32)
+        nfr = np.asarray(num_frames, dtype=np.int32)
+        sl = np.asarray(slots, dtype=np.int32)
+        ah = np.ascontiguousarray(align_heads, dtype=np.int32)
+        mr = np.ascontiguousarray(min_rows, dtype=np.int32)
+        if len(mr) != n or len(ntok) != n or len(nfr) != n:
+            raise ValueError("align_batch_open: one token list, num_frames and min_rows per slot")
+        T = np.maximum(ntok - n_sot - 2, 0)
+        widths = (T + 1) + np.maximum(nfr, 0) // 2
+        probs = np.zeros(max(int(T.sum()), 1), dtype=np.float32)
+        paths = np.zeros(max(int(2 * widths.sum()), 1), dtype=np.int32)
+        plens = np.zeros(n, dtype=np.int32)
+        ends = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.wh_align_batch_open(self.h, n, _ptr(sl), _ptr(toks), _ptr(ntok), n_sot, _ptr(nfr),
+                                                 _ptr(ah), len(ah), medfilt_width, _ptr(mr), float(row_penalty),
+                                                 _ptr(probs), _ptr(paths), _ptr(plens), _ptr(ends)),
+                    "wh_align_batch_open")
+        out, po, qo = [], 0, 0
+        for w in range(n):
+            L, W = int(plens[w]), int(widths[w])
+            path = paths[qo:qo + 2 * W].reshape(2, W)
+            out.append((probs[po:po + T[w]].copy(), path[0, :L].copy(), path[1, :L].copy(), int(ends[w])))
+            po += int(T[w])
+            qo += 2 * W
+        return out
+
     def dtw(self, x: np.ndarray) -> np.ndarray:
         """timing.dtw(x) on the GPU: [2][path length] (text indices, time indices)."""
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -887,6 +924,20 @@ class HipContext:
         n = c_int(0)
         self._check(self.lib.wh_dtw(self.h, _ptr(x), N, M, _ptr(path), ctypes.byref(n)), "wh_dtw")
         return path[:, :n.value].copy()
+
+    def dtw_open(self, x: np.ndarray, min_rows: int = 1, row_penalty: float = 4.0):
+        """wh_dtw_open (include/whisper_hip.h, open-end DTW): (path [2][length], end_row,
+        scores [N]) of cost matrix x [N][M]; ``min_rows == 0`` is the closed ``dtw(x)``."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError(f"dtw_open: x is not a matrix (shape {x.shape})")
+        N, M = x.shape
+        path = np.zeros((2, N + M), dtype=np.int32)
+        scores = np.zeros(max(N, 1), dtype=np.float32)
+        n, e = c_int(0), c_int(0)
+        self._check(self.lib.wh_dtw_open(self.h, _ptr(x), N, M, int(min_rows), float(row_penalty), _ptr(path),
+                                         ctypes.byref(n), ctypes.byref(e), _ptr(scores)), "wh_dtw_open")
+        return path[:, :n.value].copy(), e.value, scores[:N].copy()
 
     def stats(self) -> dict:
         out = (c_double * N_STATS)()

@@ -158,6 +158,28 @@ def _is_channel_value(v) -> bool:
         return False
 
 
+def ingest_group(ctx, group: Sequence[int], sources: Sequence, lengths: Sequence[int],
+                 file_of: Optional[Sequence[int]] = None) -> None:
+    """The audios ``group`` back to back in the context's resident buffer: ``sources[i]`` is what
+    ``audio.ingest`` takes, a ``_SplitSource`` (one call makes the segments of all its channels,
+    entries i, i + 1, ...) or None (a further channel of a split file), ``lengths[i]`` the 16 kHz
+    samples planned for it, ``file_of[i]`` the file named in errors (default: i)."""
+    total = sum(lengths[i] for i in group)
+    offset = 0
+    for i in group:
+        if sources[i] is None:
+            continue  # a further channel of a split file: its first channel's call made the segment
+        if isinstance(sources[i], _SplitSource):
+            segs = ingest(ctx, sources[i].source, dst_offset=offset, reserve=total, channels=sources[i].channels)
+        else:
+            segs = [ingest(ctx, sources[i], dst_offset=offset, reserve=total)]
+        for k, seg in enumerate(segs):
+            if seg.n_samples != lengths[i + k] or seg.offset != offset:
+                raise RuntimeError(f"audio {i if file_of is None else file_of[i]}: {seg.n_samples} samples ingested "
+                                   f"at {seg.offset}, {lengths[i + k]} planned at {offset}")
+            offset += seg.n_samples
+
+
 def run_lanes(lanes: Sequence["_Lane"], max_windows: int, decode_round: Callable[[List[Window]], List[DecodingResult]],
               align_round: Optional[Callable[[List[Tuple[int, "_Lane", int]]], List[list]]] = None) -> None:
     """Rounds over ``lanes`` (taken in the given order): every live lane offers its next
@@ -438,20 +460,7 @@ def transcribe_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray]],
     def prepare_group(group: List[int]):
         # the group's files back to back in the resident buffer (PCM resampled there, arrays
         # copied), then the log-mel of the resident segments
-        total = sum(lengths[i] for i in group)
-        offset = 0
-        for i in group:
-            if sources[i] is None:
-                continue  # a further channel of a split file: its first channel's call made the segment
-            if isinstance(sources[i], _SplitSource):
-                segs = ingest(ctx, sources[i].source, dst_offset=offset, reserve=total, channels=sources[i].channels)
-            else:
-                segs = [ingest(ctx, sources[i], dst_offset=offset, reserve=total)]
-            for k, seg in enumerate(segs):
-                if seg.n_samples != lengths[i + k] or seg.offset != offset:
-                    raise RuntimeError(f"audio {file_of[i]}: {seg.n_samples} samples ingested at {seg.offset}, "
-                                       f"{lengths[i + k]} planned at {offset}")
-                offset += seg.n_samples
+        ingest_group(ctx, group, sources, lengths, file_of)
         if vad_params is not None:
             # one detector call for the group, on the segments that were just ingested
             for i, (sp, _) in zip(group, resident_spans(ctx, len(group), vad_params)):
