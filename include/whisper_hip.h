@@ -259,6 +259,34 @@ int wh_encode(wh_ctx* ctx, int n_win, const int64_t* seek_frames, const int* seg
 int wh_read_audio_features(wh_ctx* ctx, int slot, float* out);                   /* [n_audio_ctx][n_state] */
 int wh_read_cross_kv(wh_ctx* ctx, int slot, int layer, float* k_out, float* v_out); /* [H][n_audio_ctx][64] */
 
+/* Cross-KV formats.  The decoder step's cross-attention reads each window's K and V once per
+   token; WH_CKV_FP8_E4M3 gives it an 8-bit copy to read instead (about half the bytes).  The
+   copy is made behind every encode from the fp16 cross-KV, which stays: first passes, word
+   timestamps and alignment read the fp16 values and do not change.  Memory grows by about
+   half the cross-KV.  Per (layer, slot, head, key t < n_audio_ctx), separately for K and V,
+   over the head's 64 channels (x: the fp16 values):
+     amax  = max |x|
+     scale = amax / 448                                   (fp32)
+     code  = e4m3(clamp(x * (448 / amax), -448, 448))     (OCP E4M3, round to nearest even)
+   amax == 0 gives scale 0 and codes 0; padding keys have scale 0 and codes 0; the NaN codes
+   0x7F / 0xFF are never written.  The step computes with code * scale: a key's K scale
+   multiplies its fp32 score, its V scale its fp32 probability; the query and the probabilities
+   keep fp16 precision.  The copy serves decoder steps of up to 128 rows (windows x beams), the
+   steps the step kernel serves; a larger step reads the fp16 cross-KV, as on a WH_CKV_NATIVE
+   context, and wh_step_kernels then reports the kernel without <kv8>.
+   wh_set_cross_kv_format: after wh_create and before the first wh_encode.  Refused with
+   wh_last_error set and the context unchanged: WH_CKV_FP8_E4M3 on an fp32 context, a change
+   after the first wh_encode, an unknown format.  Setting the format the context already has
+   always succeeds.  wh_version() does not change with these two: a caller detects them by the
+   symbols.
+   wh_read_cross_kv8: the codes in logical order [H][n_audio_ctx][64] and the scales
+   [H][n_audio_ctx] of one slot and layer (un-permuted on the host); refused on a context whose
+   format is WH_CKV_NATIVE. */
+enum { WH_CKV_NATIVE = 0, WH_CKV_FP8_E4M3 = 1 };
+int wh_set_cross_kv_format(wh_ctx* ctx, int fmt);
+int wh_read_cross_kv8(wh_ctx* ctx, int slot, int layer, uint8_t* k_codes, float* k_scales, uint8_t* v_codes,
+                      float* v_scales);
+
 /* decode n_win windows (slots 0..n_win-1): prefill of the initial tokens
    (init_tokens[w*max_init + i], i < n_init[w]) and the first token update */
 int wh_decode_begin(wh_ctx* ctx, int n_win, const wh_decode_opts* opts, const int* init_tokens, const int* n_init,

@@ -6,6 +6,18 @@ namespace wh {
 
 constexpr int TKP = 1536;  // cross-KV keys per (window, head) block: 1500 padded to whole 64-key tiles
 // cross-V (V^T) is tile-major: xv_index (wh_common.h)
+// The 8-bit copy of the cross-KV (whisper_hip.h "cross-KV formats"), [layer][slot][head][tile]
+// records of one 64-key tile each:
+//   [0, 4096)     K codes, key row kk (64 B): byte 16 g + 8 s + e = channel 32 s + 8 g + e
+//   [4096, 8192)  V^T codes, channel row d (64 B): byte 16 g + 8 s + e = the fp16 row's position
+//                 32 s + 8 g + e (xv_perm), i.e. key 32 s + 16 (e >> 2) + 4 g + (e & 3) of the tile
+//   [8192, 8448)  K scales, fp32, key order;  [8448, 8704)  V scales, fp32, key order
+constexpr int CKV8_REC = 8704, CKV8_TILES = TKP / 64;
+inline size_t ckv8_slot_bytes(int H) { return (size_t)H * CKV8_TILES * CKV8_REC; }
+// k_ckv_quant: slots [slot0, slot0 + nslots) of every layer, from the fp16 cross-KV
+// ckv [2 * layer + kv][nslots_cap][H][TKP * 64] into ckv8 [layer][nslots_cap][H][tile] records
+void launch_ckv_quant(const void* ckv, void* ckv8, int layers, int nslots_cap, int slot0, int nslots, int H,
+                      hipStream_t st);
 
 template <typename T>
 void launch_layernorm(const float* x, T* y, const float* g, const float* b, int rows, int n, float eps,
@@ -52,6 +64,10 @@ struct XQPart {
   const void* qx = nullptr;
   const void* qwf = nullptr;
 };
+// the KV8 instantiations of k_xattn_seg (wh_ckv8.hip); launch_cross_attn's step arguments
+void launch_xattn_seg8(const void* q, int ldq, const void* kv8, int Tk, int H, int npair, int nsp, int nwg, bool full,
+                       const int* win_row0, const int* win_nrows, const int* win_slot, const XQPart& xq, void* out,
+                       int ldo, hipStream_t st);
 // the shapes the in-kernel query projection serves: fp16, n = 1280 (large-v3, turbo), <= 8
 // rows per window; the choice depends on the model and the beam group only, never on the
 // window count (a window's step stays batch-invariant)
@@ -73,7 +89,7 @@ template <typename T>
 void launch_cross_attn(const T* q, int ldq, const T* ck, const T* cv, int Tk, int H, int nsplit, int nwin,
                        const int* win_row0, const int* win_nrows, const int* win_slot, int64_t win_stride, float* po,
                        float* pm, float* pl, T* out, int ldo, int rows, float* qk_out, const int* qk_map, int qk_rows,
-                       hipStream_t st, XQPart xq = XQPart());
+                       hipStream_t st, XQPart xq = XQPart(), const void* kv8 = nullptr);
 template <typename T>
 void launch_embed(const T* E, const T* P, int n, const int* row_tok, int* row_pos, const int* hist,
                   const int* cur_len, int G, int hctx, int pmax, float* x, int rows, hipStream_t st);

@@ -82,6 +82,8 @@ struct wh_ctx {
   virtual int encode(int n_win, const int64_t* seeks, const int* segs) = 0;
   virtual int read_xa(int slot, float* out) = 0;
   virtual int read_ckv(int slot, int layer, float* k, float* v) = 0;
+  virtual int set_ckv_format(int fmt) = 0;
+  virtual int read_ckv8(int slot, int layer, uint8_t* kc, float* ks, uint8_t* vc, float* vs) = 0;
   virtual int decode_begin(int n_win, const wh_decode_opts* o, const int* init, const int* n_init, int max_init,
                            const int* sot_index, const int* slots) = 0;
   virtual int decode_steps(int max_steps, int* n_done) = 0;
@@ -150,6 +152,12 @@ struct Ctx : public wh_ctx {
 
   // encoder buffers
   T *melT, *h1, *xn_e, *qkv_e, *vt_e, *att_e, *hm_e, *xa, *ckv;
+  // the 8-bit copy of the cross-KV the step's cross-attention reads (wh_set_cross_kv_format:
+  // [layer][slot][head][tile] records, wh_kernels.h CKV8_REC), written by k_ckv_quant behind
+  // every cross-KV GEMM; null = the step reads ckv.  Allocated once, when the format is chosen
+  char* ckv8 = nullptr;
+  bool encoded = false;  // an encode has run: the format is fixed
+  const void* kv8_layer(int l) const { return ckv8 ? ckv8 + (size_t)l * Wcap * ckv8_slot_bytes(nh) : nullptr; }
   float* x_e;
   int64_t* d_seeks;
   int* d_segs;
@@ -227,6 +235,7 @@ struct Ctx : public wh_ctx {
     if (st) rel(hipStreamDestroy(st), "hipStreamDestroy");
     if (wbase) rel(hipFree(wbase), "hipFree(weights)");
     if (abase) rel(hipFree(abase), "hipFree(activations)");
+    if (ckv8) rel(hipFree(ckv8), "hipFree(cross-KV 8-bit copy)");
     audio.release(rel);
     scratch.release(rel, "hipFree(scratch)");
     if (h_done) rel(hipHostFree(h_done), "hipHostFree(done flags)");
@@ -594,6 +603,7 @@ struct Ctx : public wh_ctx {
     g.x_group_rows = 1500; g.x_group_stride = (int64_t)1500 * n;
     g.out = ckv; g.hs_state = n; g.hs_heads = nh; g.hs_T = TKP; g.hs_nslots = Wcap; g.hs_slot0 = s0;
     TRY(gemm(xa_s, n, ckv_w, ckv_b, M, 2 * Ld * n, n, EPI_HEADSPLIT, g));
+    if (ckv8) launch_ckv_quant(ckv, ckv8, Ld, Wcap, s0, we, nh, st);
     return 0;
   }
 
@@ -609,6 +619,7 @@ struct Ctx : public wh_ctx {
       if (s < 0 || segs[i] < 1 || s + std::min(segs[i], 3000) > mel.frames) return fail(-9, "bad window");
       h_seeks[i] = s;
     }
+    encoded = true;
     TRY(tm.mark(0, st));
     HIPCHK(hipMemcpyAsync(d_seeks, h_seeks.data(), n_win * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_segs, segs, n_win * 4, hipMemcpyHostToDevice, st));
@@ -644,6 +655,51 @@ struct Ctx : public wh_ctx {
                 kv ? (float)h[(size_t)hh * 64 * TKP + xv_index(dd, t)] : (float)h[((size_t)hh * TKP + t) * 64 + dd];
         }
     }
+    return 0;
+  }
+
+  int set_ckv_format(int fmt) override {
+    if (fmt != WH_CKV_NATIVE && fmt != WH_CKV_FP8_E4M3)
+      return fail(-12, "cross_kv_format: unknown format " + std::to_string(fmt));
+    if (fmt == (ckv8 ? WH_CKV_FP8_E4M3 : WH_CKV_NATIVE)) return 0;
+    if (encoded) return fail(-12, "cross_kv_format: the format is fixed by the first wh_encode");
+    if (fmt == WH_CKV_NATIVE) {
+      HIPCHK(hipFree(ckv8));
+      ckv8 = nullptr;
+      return 0;
+    }
+    if (sizeof(T) != 2) return fail(-12, "cross_kv_format: WH_CKV_FP8_E4M3 needs an fp16 context (this one is fp32)");
+    const size_t bytes = (size_t)Ld * Wcap * ckv8_slot_bytes(nh);
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    if (hipMemset(p, 0, bytes) != hipSuccess) {
+      (void)hipFree(p);
+      return fail(-100, "cross_kv_format: hipMemset failed");
+    }
+    ckv8 = (char*)p;
+    return 0;
+  }
+  int read_ckv8(int slot, int layer, uint8_t* kc, float* ks, uint8_t* vc, float* vs) override {
+    if (!ckv8) return fail(-12, "read_cross_kv8: the context's cross-KV format is WH_CKV_NATIVE");
+    if (slot < 0 || slot >= Wcap || layer < 0 || layer >= Ld) return fail(-10, "slot/layer");
+    std::vector<char> h(ckv8_slot_bytes(nh));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(h.data(), (const char*)kv8_layer(layer) + (size_t)slot * h.size(), h.size(), hipMemcpyDeviceToHost));
+    for (int hh = 0; hh < nh; ++hh)
+      for (int t = 0; t < 1500; ++t) {
+        const char* rec = h.data() + ((size_t)hh * CKV8_TILES + t / 64) * CKV8_REC;
+        const int kk = t & 63;
+        const size_t o = (size_t)hh * 1500 + t;
+        memcpy(&ks[o], rec + 8192 + 4 * kk, 4);
+        memcpy(&vs[o], rec + 8448 + 4 * kk, 4);
+        const int vpos = xv_perm(kk);  // the key's position in the fp16 V^T rows
+        for (int dd = 0; dd < 64; ++dd) {
+          // a row's byte 16 g + 8 s + e holds element 32 s + 8 g + e (wh_kernels.h CKV8_REC)
+          auto at = [](int c) { return 16 * ((c >> 3) & 3) + 8 * (c >> 5) + (c & 7); };
+          kc[o * 64 + dd] = (uint8_t)rec[kk * 64 + at(dd)];
+          vc[o * 64 + dd] = (uint8_t)rec[4096 + dd * 64 + at(vpos)];
+        }
+      }
     return 0;
   }
 
@@ -795,7 +851,7 @@ struct Ctx : public wh_ctx {
       const T* ck = ckv + (size_t)(2 * l) * Wcap * TKP * n;
       const T* cv = ckv + (size_t)(2 * l + 1) * Wcap * TKP * n;
       launch_cross_attn<T>(q_d, n, ck, cv, 1500, nh, NSPLIT, nwin, wr0, wnr, wsl, (int64_t)TKP * n, po, pm, pl, att_d,
-                           n, R, aqk, qkmap ? qkmap + l * nh : nullptr, qkrows, st, xq);
+                           n, R, aqk, qkmap ? qkmap + l * nh : nullptr, qkrows, st, xq, skinny ? kv8_layer(l) : nullptr);
       TRY(resid(att_d, n, e.wox, e.box, R, e.ln2_g, e.ln2_b));
       TRY(proj(e.w1, e.b1, R, 4 * n, hm_d, 1, skinny));
       const bool last = l + 1 == Ld;
@@ -879,8 +935,12 @@ struct Ctx : public wh_ctx {
   bool p1_active(int R, int n_win) const { return n_win == 1 && p1_enabled() && proj1_supported(R, ns); }
   std::string step_kernels(int n_win, int group) const override {
     const bool p1 = p1_active(n_win * group, n_win), h = sizeof(T) == 2;
+    const bool qp = !p1 && xq_proj_active(group);
+    // the 8-bit copy serves the steps k_xattn_seg serves: up to 128 rows (dec_layers: skinny);
+    // a larger step runs the first-pass kernel over the fp16 cross-KV, in either format
+    const bool kv8 = ckv8 && n_win * group <= 128;
     return std::string("proj=") + (p1 ? "k_proj1" : "k_proj") + ",xattn=k_xattn_seg" +
-           (!p1 && xq_proj_active(group) ? "<qproj>" : "") + ",self_attn=" +
+           (kv8 ? (qp ? "<kv8,qproj>" : "<kv8>") : qp ? "<qproj>" : "") + ",self_attn=" +
            (p1 ? (h ? "k_self_attn<kco>" : "k_self_attn") : h ? "k_self_attn_qkv<pipe+kco>" : "k_self_attn_qkv") +
            ",tail=vocab+k_logit_part";
   }
@@ -933,7 +993,7 @@ struct Ctx : public wh_ctx {
       const T* ck = ckv + (size_t)(2 * l) * Wcap * TKP * n;
       const T* cv = ckv + (size_t)(2 * l + 1) * Wcap * TKP * n;
       launch_cross_attn<T>(q_d, n, ck, cv, 1500, nh, NSPLIT, nwin, wr0, wnr, wsl, (int64_t)TKP * n, po, pm, pl, att_d,
-                           n, R, nullptr, nullptr, 0, st, xq);
+                           n, R, nullptr, nullptr, 0, st, xq, kv8_layer(l));
       // (not deferred: fc1's 16-wave LayerNorm prologue has no registers for two more row copies)
       TRY(resid(att_d, n, e.wox, e.box, false));
       // MLP; the last layer's fc2 reduces in-launch (the final LayerNorm reads x)
@@ -1726,7 +1786,7 @@ struct Ctx : public wh_ctx {
               xq.qx = xn_d; xq.qwf = e.wqx_f; xq.bias = e.bqx;
             }
             launch_cross_attn<T>(q_d, n, ck, cv, 1500, nh, NSPLIT, cur_nwin, st_win_row0, st_win_nrows, st_win_slot,
-                                 (int64_t)TKP * n, po, pm, pl, att_d, n, R, nullptr, nullptr, 0, st, xq);
+                                 (int64_t)TKP * n, po, pm, pl, att_d, n, R, nullptr, nullptr, 0, st, xq, kv8_layer(l));
             ++launches;
           }
         }
@@ -2036,6 +2096,12 @@ int wh_mel_write(wh_ctx* ctx, const float* mel, int64_t nf) { CTXCALL(ctx->audio
 int wh_encode(wh_ctx* ctx, int n_win, const int64_t* seeks, const int* segs) { CTXCALL(ctx->encode(n_win, seeks, segs)); }
 int wh_read_audio_features(wh_ctx* ctx, int slot, float* out) { CTXCALL(ctx->read_xa(slot, out)); }
 int wh_read_cross_kv(wh_ctx* ctx, int slot, int layer, float* k, float* v) { CTXCALL(ctx->read_ckv(slot, layer, k, v)); }
+int wh_set_cross_kv_format(wh_ctx* ctx, int fmt) { CTXCALL(ctx->set_ckv_format(fmt)); }
+int wh_read_cross_kv8(wh_ctx* ctx, int slot, int layer, uint8_t* k_codes, float* k_scales, uint8_t* v_codes,
+                      float* v_scales) {
+  if (!k_codes || !k_scales || !v_codes || !v_scales) return fail(-1, "null argument");
+  CTXCALL(ctx->read_ckv8(slot, layer, k_codes, k_scales, v_codes, v_scales));
+}
 int wh_decode_begin(wh_ctx* ctx, int n_win, const wh_decode_opts* o, const int* init, const int* n_init, int max_init,
                     const int* sot_index) {
   if (!o || !init || !n_init || !sot_index) return fail(-1, "null argument");

@@ -69,8 +69,10 @@ def _device_index(device) -> int:
 
 def load_model(name: str, device: Optional[Union[str, int]] = None, download_root: Optional[str] = None,
                in_memory: bool = False, use_coreml: bool = False, *, dtype: str = "fp16", max_windows: int = 8,
-               max_group: int = 5, synthetic: Optional[bool] = None, seed: int = 0) -> Whisper:
-    """Load a model onto one MI355X (reference __init__.py:107-179)."""
+               max_group: int = 5, synthetic: Optional[bool] = None, seed: int = 0,
+               cross_kv: Optional[str] = None) -> Whisper:
+    """Load a model onto one MI355X (reference __init__.py:107-179).  cross_kv="fp8": the decoder
+    step reads an 8-bit copy of the cross-KV (HipContext)."""
     dev = _device_index(device)
     if download_root is None:
         default = os.path.join(os.path.expanduser("~"), ".cache")
@@ -108,7 +110,8 @@ def load_model(name: str, device: Optional[Union[str, int]] = None, download_roo
         warnings.warn(f"{name!r}: seeded synthetic weights (seed={seed}), not a trained checkpoint")
         dims = ModelDimensions(**MODEL_DIMS[name])
         state = synthetic_state_dict(MODEL_DIMS[name], seed)
-    model = Whisper(dims, name, device=dev, dtype=dtype, max_windows=max_windows, max_group=max_group)
+    model = Whisper(dims, name, device=dev, dtype=dtype, max_windows=max_windows, max_group=max_group,
+                    cross_kv=cross_kv)
     model.load_state_dict(state)
     del state
     if align is not None:

@@ -11,6 +11,7 @@ Differences from the reference shim, on purpose:
 
 import ctypes
 import os
+import re
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 from typing import List, NamedTuple, Optional, Sequence
 
@@ -21,6 +22,8 @@ _DEFAULT_LIB = os.path.join(os.path.dirname(_PKG_DIR), "lib", "libwhisper_hip.so
 
 WH_F32 = 0
 WH_F16 = 1
+WH_CKV_NATIVE = 0
+WH_CKV_FP8_E4M3 = 1
 WH_PCM_S16, WH_PCM_S32, WH_PCM_F32 = 0, 1, 2
 
 
@@ -102,6 +105,8 @@ _EXPORTS = {
     "wh_encode": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "wh_read_audio_features": (c_int, [c_void_p, c_int, c_void_p]),
     "wh_read_cross_kv": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "wh_set_cross_kv_format": (c_int, [c_void_p, c_int]),
+    "wh_read_cross_kv8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wh_decode_begin": (c_int, [c_void_p, c_int, POINTER(WhDecodeOpts), c_void_p, c_void_p, c_int, c_void_p]),
     "wh_decode_begin_slots": (c_int, [c_void_p, c_int, c_void_p, POINTER(WhDecodeOpts), c_void_p, c_void_p, c_int,
                                       c_void_p]),
@@ -302,7 +307,17 @@ def max_windows_limit(dims: dict, dtype: str, max_group: int) -> int:
 class HipContext:
     """One libwhisper_hip context = one model on one GPU (per process)."""
 
-    def __init__(self, dims: dict, device: int = 0, dtype: str = "fp16", max_windows: int = 8, max_group: int = 5):
+    def __init__(self, dims: dict, device: int = 0, dtype: str = "fp16", max_windows: int = 8, max_group: int = 5,
+                 cross_kv: Optional[str] = None):
+        """cross_kv: None (the compute type) or "fp8": the decoder step's cross-attention reads
+        an 8-bit (E4M3) copy of the cross-KV (wh_set_cross_kv_format).  With None, the
+        environment variable WHISPER_HIP_CROSS_KV=fp8 selects it for fp16 contexts."""
+        if cross_kv is None and dtype == "fp16" and os.environ.get("WHISPER_HIP_CROSS_KV", "") == "fp8":
+            cross_kv = "fp8"
+        if cross_kv not in (None, "fp8"):
+            raise ValueError(f"cross_kv={cross_kv!r}: None or 'fp8'")
+        if cross_kv == "fp8" and dtype != "fp16":
+            raise ValueError(f"cross_kv='fp8' needs dtype='fp16', not dtype={dtype!r}: the 8-bit copy feeds fp16 MFMAs")
         lim = max_windows_limit(dims, dtype, max_group)
         if max_windows > lim:
             raise ValueError(f"max_windows={max_windows} with max_group={max_group} in {dtype}: one layer's self-KV cache "
@@ -319,6 +334,9 @@ class HipContext:
         self._check(self.lib.wh_create(device, ctypes.byref(d), code, max_windows, max_group, ctypes.byref(h)),
                     "wh_create")
         self.h = h
+        self.cross_kv_format = cross_kv
+        if cross_kv == "fp8":
+            self.set_cross_kv_format(WH_CKV_FP8_E4M3)
         self.phrase_bias = None  # what set_phrase_bias installed: (phrases, boosts, start)
 
     # -- errors
@@ -767,6 +785,22 @@ class HipContext:
         self._check(self.lib.wh_read_cross_kv(self.h, slot, layer, _ptr(k), _ptr(v)), "wh_read_cross_kv")
         return k, v
 
+    def set_cross_kv_format(self, fmt: int):
+        """wh_set_cross_kv_format: WH_CKV_NATIVE or WH_CKV_FP8_E4M3, before the first encode."""
+        self._check(self.lib.wh_set_cross_kv_format(self.h, int(fmt)), "wh_set_cross_kv_format")
+
+    def cross_kv8(self, slot: int, layer: int):
+        """The 8-bit copy of one slot and layer: (k_codes, k_scales, v_codes, v_scales), codes
+        uint8 E4M3 [H][n_audio_ctx][64], scales fp32 [H][n_audio_ctx]; value = code * scale."""
+        H, T = self.dims["n_text_head"], self.dims["n_audio_ctx"]
+        kc = np.empty((H, T, 64), dtype=np.uint8)
+        vc = np.empty_like(kc)
+        ks = np.empty((H, T), dtype=np.float32)
+        vs = np.empty_like(ks)
+        self._check(self.lib.wh_read_cross_kv8(self.h, slot, layer, _ptr(kc), _ptr(ks), _ptr(vc), _ptr(vs)),
+                    "wh_read_cross_kv8")
+        return kc, ks, vc, vs
+
     # -- decoding
     def decode_begin(self, opts: WhDecodeOpts, init_tokens: Sequence[Sequence[int]], sot_index: Sequence[int],
                      slots: Optional[Sequence[int]] = None):
@@ -964,7 +998,8 @@ class HipContext:
         buf = ctypes.create_string_buffer(256)
         n = self.lib.wh_step_kernels(self.h, n_win, group, buf, 256)
         self._check(0 if n >= 0 else n, "wh_step_kernels")
-        return dict(kv.split("=", 1) for kv in buf.value.decode().split(","))
+        # fields are separated by the commas in front of a `name=` ("<kv8,qproj>" holds one too)
+        return dict(kv.split("=", 1) for kv in re.split(r",(?=\w+=)", buf.value.decode()))
 
     def time_stage(self, what: int, iters: int) -> float:
         ms = c_double()
