@@ -54,6 +54,55 @@ def _read(m, task, n):
     return out
 
 
+def test_prefill_logits_twice_then_alignment_between_chunks(micro32):
+    """wh_prefill_logits carves its device outputs from the context's grow-only scratch, which
+    alignment uses too.  Inside a live decode of three windows: a small call without alignment
+    heads, a larger one with them (the scratch grows between the two), then an alignment on the
+    same slot.  The decode ends as the uninterrupted one does, and both calls return what the
+    same two calls return on a fresh context (the same kernels on the same inputs).  First in
+    the file: in file order the module's context has not aligned yet, so its scratch starts empty."""
+    import whisper
+    from whisper.timing import _alignment_head_ids
+    from whisper.tokenizer import get_tokenizer
+    m, n = micro32, 3
+    task = _setup(m, n)
+    init = [task.initial_tokens] * n
+    m.ctx.decode_begin(task.wh_opts(), init, [task.sot_index] * n)
+    m.ctx.decode_steps(task.sample_len)
+    ref = _read(m, task, n)
+
+    tok = get_tokenizer(m.is_multilingual, num_languages=m.num_languages, language="en", task="transcribe")
+    heads = _alignment_head_ids(m)
+    short, long_ = list(range(300, 305)), list(range(400, 440))
+    seq = [*tok.sot_sequence, tok.no_timestamps, *range(100, 140), tok.eot]
+
+    fresh = whisper.load_model("micro", device=0, dtype="fp32", max_windows=4, max_group=5, synthetic=True)
+    try:
+        _setup(fresh, n)
+        want_short, none = fresh.ctx.prefill_logits(3, short)
+        want_long, want_qk = fresh.ctx.prefill_logits(3, long_, heads)
+    finally:
+        fresh.close()
+    assert none is None and want_qk.shape == (len(heads), len(long_), 1500)
+
+    m.ctx.decode_begin(task.wh_opts(), init, [task.sot_index] * n)
+    done = m.ctx.decode_steps(9)
+    assert done < n, "the decode must still be live at the cut"
+    got_short, none = m.ctx.prefill_logits(3, short)
+    got_long, got_qk = m.ctx.prefill_logits(3, long_, heads)
+    m.ctx.align_batch([3], [seq], len(tok.sot_sequence), [3000], heads)
+    m.ctx.decode_steps(task.sample_len)
+    got = _read(m, task, n)
+
+    assert none is None
+    np.testing.assert_array_equal(got_short, want_short, err_msg="5-token prefill logits")
+    np.testing.assert_array_equal(got_long, want_long, err_msg="40-token prefill logits")
+    np.testing.assert_array_equal(got_qk, want_qk, err_msg="40-token cross-QK of the alignment heads")
+    for w in range(n):
+        for a, b, what in zip(got[w], ref[w], ("tokens", "sum_logprobs", "length", "fin_len", "fin_score")):
+            np.testing.assert_array_equal(a, b, err_msg=f"window {w}: {what} changed by the interleaved work")
+
+
 @pytest.mark.parametrize("n", [3, 1])
 def test_decode_resumes_after_alignment_and_prefill(micro32, n):
     from whisper.timing import _alignment_head_ids
@@ -80,3 +129,4 @@ def test_decode_resumes_after_alignment_and_prefill(micro32, n):
     for w in range(n):
         for a, b, what in zip(got[w], ref[w], ("tokens", "sum_logprobs", "length", "fin_len", "fin_score")):
             np.testing.assert_array_equal(a, b, err_msg=f"window {w}: {what} changed by the interleaved work")
+

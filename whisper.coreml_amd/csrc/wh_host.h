@@ -1,4 +1,5 @@
-// Host plumbing shared by the runtime's translation units (wh_runtime.hip, wh_audio.hip):
+// Host plumbing shared by the runtime's translation units (wh_runtime.hip, wh_audio.hip,
+// wh_loop.hip):
 // the thread's error text and the status macros, the checked releases of a context's
 // destructor, stage timing between HIP events and the grow-only device buffer.
 #pragma once

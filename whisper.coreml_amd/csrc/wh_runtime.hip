@@ -3,10 +3,11 @@
 // Objective-C++ CoreML runner coreml/coreml.mm:18-463 (process-global state, one
 // model per process, void returns); here everything lives in a context object,
 // every entry point returns a status, and all stage data stays in HBM.
+// The audio front end (wh_audio.hip) and the host side of the decode loop and of alignment
+// (wh_loop.hip) do not depend on the element type: compiled once, outside Ctx<T>.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -20,6 +21,7 @@
 #include "wh_gemm.h"
 #include "wh_host.h"
 #include "wh_kernels.h"
+#include "wh_loop.h"
 
 using namespace wh;
 
@@ -27,8 +29,6 @@ static thread_local std::string g_release_error;  // a failed release in the las
 
 namespace {
 
-constexpr int CTX = 448;          // text positions (decoder.py:243, decoding.py:173)
-constexpr int HCTX = CTX + 1;     // history capacity (tokens.shape[-1] may reach n_ctx + 1)
 constexpr int NSPLIT = 8;         // cross-attention key splits (1500 / 8 = 188 keys)
 // encoder windows per pass (WHISPER_HIP_ENC_CHUNK overrides; activations scale with it)
 static int enc_chunk() {
@@ -67,14 +67,14 @@ template <typename T>
 struct DecLayer {
   float *ln1_g, *ln1_b, *bqkv, *bo, *lnx_g, *lnx_b, *bqx, *box, *ln2_g, *ln2_b, *b1, *b2;
   T *wqkv, *wo, *wqx, *wox, *w1, *w2;
-  // round 6: W_q in the in-kernel query projection's fragment order (xq_project: each wave's
+  // W_q in the in-kernel query projection's fragment order (xq_project: each wave's
   // 16 B-per-lane loads are 1 KB contiguous), fp16 contexts whose shape xattn_fused_q serves
   T* wqx_f = nullptr;
 };
 
 }  // namespace
 
-struct wh_ctx {
+struct wh_ctx : DecodeLoop {
   virtual std::string step_kernels(int n_win, int group) const = 0;
   virtual ~wh_ctx() {}
   virtual int load(const std::string& name, const float* data, const int64_t* shape, int ndim) = 0;
@@ -86,25 +86,10 @@ struct wh_ctx {
   virtual int read_ckv8(int slot, int layer, uint8_t* kc, float* ks, uint8_t* vc, float* vs) = 0;
   virtual int decode_begin(int n_win, const wh_decode_opts* o, const int* init, const int* n_init, int max_init,
                            const int* sot_index, const int* slots) = 0;
-  virtual int decode_steps(int max_steps, int* n_done) = 0;
   virtual int step_prefill(int n_win, int G, const int* init, const int* n_init, int max_init, const int* sot_index,
                            float* lg) = 0;
   virtual int step_tokens(const int* tok, const int* offsets, float* lg) = 0;
-  virtual int reorder_kv(const int* src) = 0;
-  virtual int decode_read(int slot, int* tokens, float* slp, int* len, int* fin_n, int* fin_tok, int* fin_len,
-                          float* fin_score, float* nsp) = 0;
   virtual int prefill_logits(int slot, const int* tokens, int n, float* logits, const int* ah, int na, float* aqk) = 0;
-  virtual int align(int slot, const int* tokens, int n, int n_sot, int num_frames, const int* ah, int na, int medfilt,
-                    float* probs, int* path, int* plen) = 0;
-  virtual int align_batch(int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
-                          const int* num_frames, const int* ah, int na, int medfilt, float* probs, int* paths,
-                          int* plens) = 0;
-  virtual int dtw(const float* x, int N, int M, int* path, int* plen) = 0;
-  virtual int align_batch_open(int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
-                               const int* num_frames, const int* ah, int na, int medfilt, const int* min_rows,
-                               float row_penalty, float* probs, int* paths, int* plens, int* end_rows) = 0;
-  virtual int dtw_open(const float* x, int N, int M, int min_rows, float row_penalty, int* path, int* plen,
-                       int* end_row, float* scores) = 0;
   virtual int time_stage(int what, int iters, double* ms) = 0;
   // tuning builds only (wh_tune_share_weights): read the weights of another context of the
   // same dims and dtype instead of this one's (probes of two window groups, one weight copy)
@@ -113,15 +98,8 @@ struct wh_ctx {
   // context this one reads from; wh_destroy refuses a context others still read from
   int sharers = 0;
   wh_ctx* shares_from = nullptr;
-  std::vector<float> token_ms;  // per-token wall ms of each decode_steps chunk
-  double stats[WH_N_STATS] = {0};  // WH_STAT_*
   AudioFront audio;  // waveforms and the log-mel (csrc/wh_audio.h)
   int n_mels = 0;    // the model's
-  int n_vocab = 0;   // the model's
-  // the phrase table of wh_set_phrase_bias, kept on the host; the next wh_decode_begin
-  // uploads it (a decode in progress keeps the table it began with)
-  std::vector<wh::BiasRec> bias_tab;
-  int maxc = 5;
   int maxc_stride = 1;
   int device = 0;
 };
@@ -131,16 +109,13 @@ namespace {
 template <typename T>
 struct Ctx : public wh_ctx {
   wh_dims d;
-  int ns, nh, La, Ld, V, K1p;
-  int Wcap, Gcap;
-  hipStream_t st = nullptr;
+  int ns, La, K1p;
   Arena wa;  // weights
   Arena aa;  // activations / state
   void* wbase = nullptr;
   void* abase = nullptr;
   std::set<std::string> loaded;
   size_t expected = 0;
-  bool finalized = false;
 
   // weights
   T *conv1_w, *conv2_w, *E, *Pdec, *ckv_w;
@@ -165,10 +140,9 @@ struct Ctx : public wh_ctx {
   std::vector<T*> kc, vc;
   // decoder buffers
   int RD;
-  int PRE = PRE_ROWS;
-  float *x_d, *po, *pm, *pl, *logits, *logits2, *nsp, *part;
+  float *x_d, *po, *pm, *pl, *logits, *logits2, *part;
   T *xn_d, *q_d, *att_d, *hm_d;
-  int *row_tok, *row_pos, *row_win, *row_slot, *win_row0, *win_nrows, *win_slot, *rows_in, *src_rows;
+  int *row_tok, *row_pos, *row_win, *row_slot, *win_row0, *win_nrows, *win_slot, *rows_in;
   int *st_row_win, *st_row_slot, *st_win_row0, *st_win_nrows, *st_win_slot;
   int* fp_anc = nullptr;
   static constexpr int P1_SLABS = 2048;  // k_proj1 split-K slabs: zs x 16-column tiles <= 16 x 80 at n = 1280
@@ -192,20 +166,6 @@ struct Ctx : public wh_ctx {
     xq.max_pairs = Wcap * nh;
     return xq;
   }
-  int* qk_map;  // [Ld][nh]
-  unsigned* suppress;
-  BiasRec* bias_dev = nullptr;  // [BIAS_MAX_ENTRIES], allocated once: DecOpts::bias never changes
-  DecState S;
-  DecOpts O;
-  int cur_nwin = 0, cur_G = 1;
-  // graph cache
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t gexec = nullptr;
-  std::vector<char> graph_key;
-  int* h_done = nullptr;
-  hipEvent_t poll_ev[2] = {nullptr, nullptr};
-
-  Timer tm;
   std::vector<hipEvent_t> proj_ev;  // time_stage(7) event pairs, empty otherwise
   int proj_ev_n = 0;
 
@@ -254,7 +214,6 @@ struct Ctx : public wh_ctx {
     La = d.n_audio_layer;
     Ld = d.n_text_layer;
     V = d.n_vocab;
-    n_vocab = V;
     n_mels = d.n_mels;
     if (d.n_audio_state != ns || d.n_audio_head != nh) return fail(-2, "audio/text state or head mismatch unsupported");
     if (ns != nh * 64) return fail(-2, "head dim must be 64 (decoder.py:62-64)");
@@ -1028,97 +987,38 @@ struct Ctx : public wh_ctx {
   }
 
   // ------------------------------------------------------------ decoding
-  int set_opts(const wh_decode_opts* o, int n_win) {
-    // every refusal comes before the first write: a refused call leaves O, S and maxc alone
-    if (o->group < 1 || o->group > Gcap) return fail(-11, "group exceeds context max_group");
-    // max_candidates = round(beam_size * patience) (decoding.py:339): Python rounds half
-    // to even; the host passes its own value, else nearbyint (default mode: half to even)
-    const int mc = !o->beam ? 0
-                   : o->max_candidates > 0 ? o->max_candidates
-                                           : (int)std::nearbyint((double)o->group * (o->patience > 0 ? o->patience : 1.0));
-    if (o->beam && (mc < 1 || mc > 16)) return fail(-11, "max_candidates out of range (1..16)");
-    if (o->no_repeat_ngram < 0 || o->no_repeat_ngram > 16)
-      return fail(-11, "no_repeat_ngram " + std::to_string(o->no_repeat_ngram) + " out of range (0..16)");
-    if (!(o->repetition_penalty >= 0.f) || std::isinf(o->repetition_penalty))
-      return fail(-11, "repetition_penalty must be finite and not negative (0 or 1: off)");
-    const float pen = o->repetition_penalty == 0.f ? 1.f : o->repetition_penalty;
-    const bool rep_on = o->no_repeat_ngram > 0 || pen != 1.f;
-    if (rep_on || !bias_tab.empty()) {
-      // the history filters exist in the sliced selection only
-      DecOpts q = DecOpts();
-      q.V = V; q.ts_begin = o->timestamp_begin;
-      if (!logit_slices(S, q, n_win))
-        return fail(-11, std::string(!rep_on ? "phrase_bias" : bias_tab.empty() ? "no_repeat_ngram / repetition_penalty"
-                                                                  : "no_repeat_ngram / repetition_penalty / phrase_bias") +
-                             " need the sliced selection (k_logit_part): not with this vocabulary or "
-                             "WHISPER_HIP_LOGIT_SPLIT=0");
-    }
-    if (!bias_tab.empty()) {
-      for (size_t e = 0; e < bias_tab.size(); ++e)
-        if (bias_tab[e].id >= o->eot) {
-          const int j = (int)std::count_if(bias_tab.begin(), bias_tab.begin() + e + 1, [](const BiasRec& r) { return r.k == 0; }) - 1;
-          return fail(-11, "phrase_bias: phrase " + std::to_string(j) + " names id " + std::to_string(bias_tab[e].id) +
-                               ", not a text id (eot " + std::to_string(o->eot) + ")");
-        }
-    }
-    O = DecOpts();
-    O.no_repeat_ngram = o->no_repeat_ngram; O.repetition_penalty = pen;
-    // the table as it is now, for this decode; the pointer and the count are all DecOpts sees
-    O.n_bias = (int)bias_tab.size();
-    O.bias = O.n_bias ? bias_dev : nullptr;
-    if (O.n_bias)
-      HIPCHK(hipMemcpyAsync(bias_dev, bias_tab.data(), bias_tab.size() * sizeof(BiasRec), hipMemcpyHostToDevice, st));
-    O.V = V; O.eot = o->eot; O.ts_begin = o->timestamp_begin; O.no_ts = o->no_timestamps;
-    O.n_blank = std::min(o->n_blank, 3);
-    for (int i = 0; i < O.n_blank; ++i) O.blank[i] = o->blank[i];
-    O.blank[O.n_blank] = o->eot;  // SuppressBlank masks encode(" ") + [eot]
-    O.n_blank += 1;
-    O.suppress_blank = o->suppress_blank; O.timestamps = o->timestamps; O.max_initial = o->max_initial;
-    O.beam = o->beam; O.sample_len = o->sample_len; O.n_ctx = CTX; O.temperature = o->temperature;
-    h_seed = o->seed;
-    std::vector<unsigned> mask((V + 31) / 32, 0u);
-    for (int i = 0; i < o->n_suppress; ++i) {
-      const int t = o->suppress[i];
-      if (t >= 0 && t < V) mask[t >> 5] |= 1u << (t & 31);
-    }
-    HIPCHK(hipMemcpyAsync(suppress, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, st));
-    O.suppress = o->n_suppress > 0 ? suppress : nullptr;
-    maxc = mc;
-    S.G = o->group;
-    S.maxc = 16;
-    return 0;
+  // The rows of a first pass through the decoder layers.  rows_dirty comes before the first
+  // upload into row_pos / x_d: a failing copy must still make the next decode_steps re-embed
+  // its rows.  The plan lives in the caller's frame until the caller has synchronised.
+  // group / anc: the beams per window of the ancestry table the self-attention reads
+  int run_rows(const RowPlan& p, int group, float* d_qk, const int* qkmap, int qk_rows, const int* anc) {
+    rows_dirty = true;
+    HIPCHK(hipMemcpyAsync(row_tok, p.row_tok.data(), p.R * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(row_pos, p.row_pos.data(), p.R * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(row_win, p.row_win.data(), p.R * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(row_slot, p.row_slot.data(), p.R * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(win_row0, p.win_row0.data(), p.nw() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(win_nrows, p.win_nrows.data(), p.nw() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(win_slot, p.win_slot.data(), p.nw() * 4, hipMemcpyHostToDevice, st));
+    launch_embed<T>(E, Pdec, ns, row_tok, row_pos, nullptr, nullptr, 1, HCTX, CTX - 1, x_d, p.R, st);
+    return dec_layers(p.R, row_win, row_slot, row_pos, group, p.nw(), win_row0, win_nrows, win_slot, d_qk, qkmap, qk_rows,
+                      false, anc);
   }
 
-  int prefill(int w0, int nw, const std::vector<int>& toks, const std::vector<int>& nin, const int* sot_index,
-              bool first_update_rows) {
-    // rows of windows w0..w0+nw-1, all in beam slot 0; cross attention per window
-    std::vector<int> rt, rp, rw, rs, wr0(nw), wnr(nw), wsl(nw), sel;
-    for (int i = 0; i < nw; ++i) {
-      wr0[i] = (int)rt.size();
-      wnr[i] = nin[i];
-      wsl[i] = win_slots[w0 + i];
-      for (int p = 0; p < nin[i]; ++p) {
-        rt.push_back(toks[(size_t)i * HCTX + p]);
-        rp.push_back(p);
-        rw.push_back(w0 + i);
-        rs.push_back(0);
-      }
-      sel.push_back(wr0[i] + sot_index[w0 + i]);
-      sel.push_back(wr0[i] + nin[i] - 1);
+  // the prompt pass of decode windows w0..w0+nw-1, all in beam slot 0; the logits of each
+  // window's sot_index and last rows go to logits2.  (rows_dirty, which run_rows sets, changes
+  // nothing here: decode_begin clears it right after, a per-step batch never reads it.)
+  int prefill(int w0, int nw, const int* init, const int* n_init, int max_init, const int* sot_index) {
+    RowPlan rows;
+    std::vector<int> sel;
+    for (int w = w0; w < w0 + nw; ++w) {
+      rows.add(w, win_slots[w], init + (size_t)w * max_init, n_init[w]);
+      sel.push_back(rows.win_row0.back() + sot_index[w]);
+      sel.push_back(rows.win_row0.back() + n_init[w] - 1);
     }
-    const int R = (int)rt.size();
-    HIPCHK(hipMemcpyAsync(row_tok, rt.data(), R * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(row_pos, rp.data(), R * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(row_win, rw.data(), R * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(row_slot, rs.data(), R * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(win_row0, wr0.data(), nw * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(win_nrows, wnr.data(), nw * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(win_slot, wsl.data(), nw * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(rows_in, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, st));
-    launch_embed<T>(E, Pdec, ns, row_tok, row_pos, nullptr, nullptr, 1, HCTX, CTX - 1, x_d, R, st);
-    TRY(dec_layers(R, row_win, row_slot, row_pos, S.G, nw, win_row0, win_nrows, win_slot, nullptr, nullptr, 0));
+    TRY(run_rows(rows, S.G, nullptr, nullptr, 0, nullptr));
     TRY(vocab(rows_in, 2 * nw, logits2 + (size_t)2 * w0 * V));
-    (void)first_update_rows;
     // the host vectors must outlive the async copies
     HIPCHK(hipStreamSynchronize(st));
     return 0;
@@ -1131,41 +1031,17 @@ struct Ctx : public wh_ctx {
   // Window w reads the audio features / cross-KV of slot slots[w] (identity when null):
   // a temperature fallback decodes the windows that still need work straight from the
   // slots that hold them, without re-running the encoder.
-  std::vector<int> h_len;      // host mirror of S.len for the per-step ABI
-  std::vector<int> win_slots;  // cross-KV slot of each decode window
-  unsigned long long h_seed = 0;
   int begin_batch(int n_win, int G, const int* init, const int* n_init, int max_init, const int* sot_index,
                   int no_speech, const int* slots = nullptr) {
-    if (!finalized) return fail(-9, "weights not finalized");
-    // no usable batch until this one is fully set up: a failure below leaves neither the
-    // device loop nor the per-step ABI (wh_step / wh_reorder_kv) a half-written batch
-    cur_nwin = 0;
-    step_api = false;
-    if (n_win < 1 || n_win > Wcap) return fail(-11, "n_win out of range");
-    if (G < 1 || G > Gcap) return fail(-11, "group exceeds context max_group");
-    win_slots.resize(n_win);
-    for (int w = 0; w < n_win; ++w) {
-      win_slots[w] = slots ? slots[w] : w;
-      if (win_slots[w] < 0 || win_slots[w] >= Wcap) return fail(-11, "window slot out of range");
-    }
+    TRY(begin_check(n_win, G, init, n_init, max_init, sot_index, slots));
     // host-side initial state
-    std::vector<int> hist((size_t)n_win * Gcap * HCTX, 0), anc((size_t)n_win * Gcap * CTX, 0), toks((size_t)n_win * HCTX, 0);
-    std::vector<int> nin(n_win), lens(n_win), zeros(n_win, 0);
-    for (int w = 0; w < n_win; ++w) {
-      nin[w] = n_init[w];
-      if (nin[w] < 1 || nin[w] > CTX - 1) return fail(-11, "initial token count out of range");
-      if (sot_index[w] < 0 || sot_index[w] >= nin[w]) return fail(-11, "bad sot_index");
-      for (int p = 0; p < nin[w]; ++p) {
-        const int t = init[(size_t)w * max_init + p];
-        if (t < 0 || t >= V) return fail(-11, "initial token out of vocabulary");
-        toks[(size_t)w * HCTX + p] = t;
-      }
-    }
+    std::vector<int> hist((size_t)n_win * Gcap * HCTX, 0), anc((size_t)n_win * Gcap * CTX, 0);
+    const std::vector<int> nin(n_init, n_init + n_win);
     S.G = G;
     // history / ancestry laid out with the runtime group G ([w][G][..])
     for (int w = 0; w < n_win; ++w)
       for (int b = 0; b < G; ++b) {
-        for (int p = 0; p < nin[w]; ++p) hist[((size_t)w * G + b) * HCTX + p] = toks[(size_t)w * HCTX + p];
+        for (int p = 0; p < nin[w]; ++p) hist[((size_t)w * G + b) * HCTX + p] = init[(size_t)w * max_init + p];
         for (int p = 0; p < CTX; ++p) anc[((size_t)w * G + b) * CTX + p] = p < nin[w] ? 0 : b;
       }
     // prefill (anc must be in place first: prefill rows read slot 0 through it)
@@ -1175,9 +1051,7 @@ struct Ctx : public wh_ctx {
       int rows = 0, nw = 0;
       while (w0 + nw < n_win && (nw == 0 || rows + nin[w0 + nw] <= PRE)) rows += nin[w0 + nw++];
       if (rows > PRE) return fail(-11, "prefill rows exceed buffer");
-      std::vector<int> sub_toks(toks.begin() + (size_t)w0 * HCTX, toks.begin() + (size_t)(w0 + nw) * HCTX);
-      std::vector<int> sub_n(nin.begin() + w0, nin.begin() + w0 + nw);
-      TRY(prefill(w0, nw, sub_toks, sub_n, sot_index, true));
+      TRY(prefill(w0, nw, init, n_init, max_init, sot_index));
       w0 += nw;
     }
     // no_speech prob from the sot row of each window (decoding.py:716-720)
@@ -1226,7 +1100,6 @@ struct Ctx : public wh_ctx {
     TRY(begin_batch(n_win, o->group, init, n_init, max_init, sot_index, o->no_speech, slots));
     S.maxc = std::max(maxc, 1);
     maxc_stride = S.maxc;
-    step_api = false;
     // first update on the prefill logits (decoding.py:713-733, i == 0); the merge also
     // embeds each row's new token: the first step's input rows
     launch_select_merge(logits, V, S, O, n_win, st, merge_embed());
@@ -1234,13 +1107,9 @@ struct Ctx : public wh_ctx {
     return tm.finish(st, stats[WH_STAT_PREFILL_MS], __func__);
   }
 
-  // The device loop's step input rows (x_d, row_pos) are written by the previous update's
-  // merge (no k_embed per token).  Any other use of those buffers between two
-  // decode_steps calls (a first pass for alignment or prefill logits, a timing stage)
-  // sets rows_dirty, and the next decode_steps re-embeds every row once from the decode
-  // state (S.hist, S.len) before its first step.
-  bool rows_dirty = false;
-  void restore_rows() {
+  // re-embeds every step row from the decode state (S.hist, S.len) after other work went
+  // through x_d / row_pos (wh_loop.h rows_dirty)
+  void restore_rows() override {
     if (!rows_dirty || cur_nwin < 1 || step_api) return;
     launch_embed<T>(E, Pdec, ns, nullptr, row_pos, S.hist, S.len, cur_G, HCTX, CTX - 1, x_d, cur_nwin * cur_G, st);
     rows_dirty = false;
@@ -1253,7 +1122,7 @@ struct Ctx : public wh_ctx {
   }
   // one decoder step for the current batch (graph body); its input rows were embedded by
   // the previous update's k_merge (decode_begin's first update for the first step)
-  int step_body() {
+  int step_body() override {
     const int R = cur_nwin * cur_G;
     TRY(dec_layers(R, st_row_win, st_row_slot, row_pos, cur_G, cur_nwin, st_win_row0, st_win_nrows, st_win_slot,
                    nullptr, nullptr, 0, true));
@@ -1268,7 +1137,6 @@ struct Ctx : public wh_ctx {
   // decoder1Predict :404-444, rearrange_mkv :251-277), so its Python DecodingTask keeps
   // filters and beam search (decoding.py:707-737).  These entry points serve that
   // caller: the same decoder step as the graph body, without the device token selection.
-  bool step_api = false;
   int step_prefill(int n_win, int G, const int* init, const int* n_init, int max_init, const int* sot_index,
                    float* lg) override {
     TRY(tm.mark(0, st));
@@ -1279,16 +1147,8 @@ struct Ctx : public wh_ctx {
   }
 
   int step_tokens(const int* tok, const int* offsets, float* lg) override {
-    if (!step_api || cur_nwin < 1) return fail(-13, "no per-step batch (call wh_prefill first)");
+    TRY(step_check(tok, offsets));
     const int R = cur_nwin * cur_G;
-    for (int r = 0; r < R; ++r)
-      if (tok[r] < 0 || tok[r] >= V) return fail(-13, "step token out of vocabulary");
-    for (int w = 0; w < cur_nwin; ++w) {
-      if (h_len[w] >= CTX) return fail(-13, "text context full (448 positions)");
-      if (offsets && offsets[w] != h_len[w])
-        return fail(-13, "text_offset " + std::to_string(offsets[w]) + " of window " + std::to_string(w) +
-                             " != cached length " + std::to_string(h_len[w]));
-    }
     TRY(tm.mark(0, st));
     HIPCHK(hipMemcpyAsync(rows_in, tok, R * 4, hipMemcpyHostToDevice, st));
     launch_append_tokens(S, rows_in, cur_nwin, st);
@@ -1303,47 +1163,12 @@ struct Ctx : public wh_ctx {
     return 0;
   }
 
-  int reorder_kv(const int* src) override {
-    if (!step_api || cur_nwin < 1) return fail(-13, "no per-step batch (call wh_prefill first)");
-    const int R = cur_nwin * cur_G;
-    for (int r = 0; r < R; ++r)
-      if (src[r] / cur_G != r / cur_G || src[r] < 0)
-        return fail(-13, "source row " + std::to_string(src[r]) + " of row " + std::to_string(r) +
-                             " is not a row of the same window");
-    HIPCHK(hipMemcpyAsync(src_rows, src, R * 4, hipMemcpyHostToDevice, st));
-    launch_reorder_rows(S, src_rows, cur_nwin, st);
-    HIPCHK(hipStreamSynchronize(st));
-    TRY(launch_status(__func__));
-    return 0;
-  }
-
-  int ensure_graph() {
-    std::vector<char> key(sizeof(DecOpts) + sizeof(DecState) + 8);
-    memcpy(key.data(), &O, sizeof(DecOpts));
-    memcpy(key.data() + sizeof(DecOpts), &S, sizeof(DecState));
-    memcpy(key.data() + sizeof(DecOpts) + sizeof(DecState), &cur_nwin, 4);
-    memcpy(key.data() + sizeof(DecOpts) + sizeof(DecState) + 4, &cur_G, 4);
-    if (gexec && key == graph_key) return 0;
-    if (gexec) { hipGraphExecDestroy(gexec); gexec = nullptr; }
-    if (graph) { hipGraphDestroy(graph); graph = nullptr; }
-    HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    const int rc = step_body();
-    hipGraph_t g = nullptr;
-    const hipError_t e = hipStreamEndCapture(st, &g);
-    if (rc) { if (g) hipGraphDestroy(g); return rc; }
-    if (e != hipSuccess) return fail(-12, std::string("graph capture: ") + hipGetErrorString(e));
-    graph = g;
-    HIPCHK(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
-    graph_key = key;
-    return 0;
-  }
-
   // WHISPER_HIP_XQ=0 keeps the separate cross-query reduce (A/B switch)
   const bool xq_fused = [] {
     const char* e = tune_env("WHISPER_HIP_XQ");
     return !(e && e[0] == '0');
   }();
-  // round 6: the step's cross-attention query projected inside k_xattn_seg (no cross-q
+  // the step's cross-attention query projected inside k_xattn_seg (no cross-q
   // k_proj launch) wherever xattn_fused_q serves the shape; WHISPER_HIP_XQP=0 keeps the
   // split-K projection + slabs (A/B switch)
   static bool xq_proj_on() {
@@ -1356,388 +1181,55 @@ struct Ctx : public wh_ctx {
   bool xq_proj_active(int rows_per_window) const {
     return xq_proj_on() && xattn_fused_q(ns, rows_per_window, (int)sizeof(T));
   }
-  // WHISPER_HIP_EAGER=1 launches the step kernels directly instead of replaying the
-  // captured graph (same kernels; used under profilers that do not follow graphs)
-  bool eager() const {
-    const char* e = tune_env("WHISPER_HIP_EAGER");
-    return e && e[0] == '1';
-  }
-
-  int launch_step() {
-    if (eager()) return step_body();
-    HIPCHK(hipGraphLaunch(gexec, st));
-    return 0;
-  }
-
-  int decode_steps(int max_steps, int* n_done) override {
-    if (cur_nwin < 1) return fail(-13, "no decode in progress");
-    if (step_api) return fail(-13, "the batch was begun with wh_prefill (per-step mode): use wh_step");
-    if (!eager()) TRY(ensure_graph());
-    TRY(tm.mark(0, st));
-    restore_rows();
-    int steps = 0, done = 0;
-    static const int chunk = [] {  // WHISPER_HIP_POLL_CHUNK: steps per done-flag poll (A/B)
-      const char* e = tune_env("WHISPER_HIP_POLL_CHUNK");
-      const int v = e ? atoi(e) : 8;
-      return v < 1 ? 1 : v;
-    }();
-    // chunks of `chunk` steps, each followed by an async copy of the done flags; the
-    // next chunk is queued before the host waits for the previous chunk's flags, so
-    // the GPU never idles on the poll (at most one chunk of no-op steps after the last
-    // window finishes: finished windows' rows are clamped and skipped by the selection)
-    auto queue_chunk = [&](int b) -> int {
-      const int k = std::min(chunk, max_steps - steps);
-      for (int i = 0; i < k; ++i) TRY(launch_step());
-      steps += k;
-      HIPCHK(hipMemcpyAsync(h_done + b * Wcap, S.done, cur_nwin * 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipEventRecord(poll_ev[b], st));
-      return k;
-    };
-    auto tc = std::chrono::steady_clock::now();
-    int b = 0, kq[2] = {0, 0};
-    kq[0] = queue_chunk(0);
-    if (kq[0] < 0) return kq[0];
-    while (true) {
-      const int nb = b ^ 1;
-      kq[nb] = steps < max_steps ? queue_chunk(nb) : 0;
-      if (kq[nb] < 0) return kq[nb];
-      HIPCHK(hipEventSynchronize(poll_ev[b]));
-      // per-token wall time (graph launches + done poll, pipelined), for the p50
-      const auto now = std::chrono::steady_clock::now();
-      token_ms.push_back((float)(std::chrono::duration<double, std::milli>(now - tc).count() / kq[b]));
-      tc = now;
-      done = 0;
-      for (int w = 0; w < cur_nwin; ++w) done += h_done[b * Wcap + w] != 0;
-      if (done == cur_nwin || kq[nb] == 0) break;
-      b = nb;
+  int align_rows(const RowPlan& p, const std::vector<int>& sel, float* d_qk, float* d_lg, int eot, const int* ptok,
+                 float* probs) override {
+    TRY(run_rows(p, 1, d_qk, qk_map, p.R, fp_anc));
+    // probabilities of the text tokens, 128 logit rows at a time
+    for (int c0 = 0; c0 < (int)sel.size(); c0 += 128) {
+      const int rr = std::min<int>(128, (int)sel.size() - c0);
+      HIPCHK(hipMemcpyAsync(rows_in, sel.data() + c0, rr * 4, hipMemcpyHostToDevice, st));
+      TRY(vocab(rows_in, rr, d_lg));
+      launch_token_probs(d_lg, V, rr, eot, ptok + c0, probs + c0, st);
     }
-    TRY(tm.finish(st, stats[WH_STAT_STEPS_MS]));
-    stats[WH_STAT_STEPS] += steps;
-    *n_done = done;
     return 0;
   }
 
-  int decode_read(int slot, int* tokens, float* slp, int* len, int* fin_n, int* fin_tok, int* fin_len,
-                  float* fin_score, float* nspo) override {
-    if (slot < 0 || slot >= cur_nwin) return fail(-14, "slot");
-    const int G = cur_G;
-    HIPCHK(hipStreamSynchronize(st));
-    if (tokens) HIPCHK(hipMemcpy(tokens, S.hist + (size_t)slot * G * HCTX, (size_t)G * HCTX * 4, hipMemcpyDeviceToHost));
-    if (slp) HIPCHK(hipMemcpy(slp, S.sum_lp + slot * G, G * 4, hipMemcpyDeviceToHost));
-    if (len) HIPCHK(hipMemcpy(len, S.len + slot, 4, hipMemcpyDeviceToHost));
-    if (fin_n) HIPCHK(hipMemcpy(fin_n, S.fin_n + slot, 4, hipMemcpyDeviceToHost));
-    const int mc = S.maxc;
-    if (fin_tok) HIPCHK(hipMemcpy(fin_tok, S.fin_tok + (size_t)slot * mc * HCTX, (size_t)mc * HCTX * 4, hipMemcpyDeviceToHost));
-    if (fin_len) HIPCHK(hipMemcpy(fin_len, S.fin_len + slot * mc, mc * 4, hipMemcpyDeviceToHost));
-    if (fin_score) HIPCHK(hipMemcpy(fin_score, S.fin_score + slot * mc, mc * 4, hipMemcpyDeviceToHost));
-    if (nspo) HIPCHK(hipMemcpy(nspo, nsp + slot, 4, hipMemcpyDeviceToHost));
-    return 0;
-  }
-
-  // Whisper.forward (model.py:110-119): all-row logits of a first pass for one window,
-  // optional raw cross-QK of alignment heads.  Uses beam slot 0 of `slot` and the anc
-  // table with a 1-beam layout; call it when no decode of that slot is in flight.
-  // first pass of `n` tokens at offset 0 for one window slot (beam slot 0, a 1-beam
-  // anc layout), optional raw cross-QK of the alignment heads into d_aqk [na][n][1500];
-  // on return xn_d holds the final LayerNorm of every row.  The host vectors are kept
-  // alive in `keep` until the caller synchronises.
-  // A first pass writes beam slot 0's self-KV rows of its slot: refused on a slot that the
-  // live device-loop batch is still decoding (its done flag unset), which it would corrupt.
-  // Slots outside the batch, finished windows and the per-step ABI's batch are allowed.
-  int check_slot_idle(int slot) {
-    if (cur_nwin < 1 || step_api) return 0;
-    for (int w = 0; w < cur_nwin; ++w)
-      if (win_slots[w] == slot) {
-        int d = 0;
-        HIPCHK(hipMemcpyAsync(&d, S.done + w, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (!d)
-          return fail(-15, "slot " + std::to_string(slot) + " is still decoding (window " + std::to_string(w) +
-                               " of the current batch): a first pass would overwrite its self-KV rows");
-      }
-    return 0;
-  }
-
-  int first_pass(int slot, const int* tokens, int n, const int* ah, int na, float* d_aqk,
-                 std::vector<std::vector<int>>& keep) {
+  // Whisper.forward (model.py:110-119): all-row logits of a first pass of `n` tokens at
+  // offset 0 for one window slot (beam slot 0, a 1-beam anc layout), optional raw cross-QK of
+  // the alignment heads [na][n][1500].  Refused on a slot that is still decoding
+  // (check_slot_idle).  The device outputs are carved from the loop's scratch, which no
+  // kernel of the first pass touches (its buffers are the activation arena's) and which
+  // alignment only uses in calls of its own, before or after this one on the same stream.
+  int prefill_logits(int slot, const int* tokens, int n, float* lg, const int* ah, int na, float* aqk) override {
+    const size_t b_out = ((size_t)n * V * 4 + 255) & ~size_t(255), b_qk = na > 0 && aqk ? (size_t)na * n * 1500 * 4 : 0;
+    TRY(ensure_scratch(b_out + b_qk));
+    float* out = (float*)scratch.p;
+    float* d_aqk = b_qk ? (float*)(scratch.p + b_out) : nullptr;
     if (!finalized) return fail(-9, "weights not finalized");
     if (slot < 0 || slot >= Wcap || n < 1 || n > CTX) return fail(-15, "bad slot or token count");
     TRY(check_slot_idle(slot));
-    rows_dirty = true;  // the first pass runs its rows through x_d / row_pos
     for (int i = 0; i < n; ++i)
       if (tokens[i] < 0 || tokens[i] >= V) return fail(-15, "token out of vocabulary");
-    keep.assign(9, {});
-    auto& rt = keep[0]; auto& rp = keep[1]; auto& rw = keep[2]; auto& rs = keep[3];
-    rt.assign(tokens, tokens + n); rp.resize(n); rw.assign(n, slot); rs.assign(n, 0);
-    keep[4] = {0}; keep[5] = {n}; keep[6] = {slot};
-    for (int i = 0; i < n; ++i) rp[i] = i;
-    auto& map = keep[8];
-    map.assign((size_t)Ld * nh, -1);
+    // the host vectors of this frame outlive the async copies (the synchronises below)
+    RowPlan rows;
+    rows.add(slot, slot, tokens, n);
+    std::vector<int> map((size_t)Ld * nh, -1), s2(n);
     for (int i = 0; i < na; ++i)
       if (ah[i] >= 0 && ah[i] < Ld * nh) map[ah[i]] = i;
-    HIPCHK(hipMemcpyAsync(row_tok, rt.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(row_pos, rp.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(row_win, rw.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(row_slot, rs.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(win_row0, keep[4].data(), 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(win_nrows, keep[5].data(), 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(win_slot, keep[6].data(), 4, hipMemcpyHostToDevice, st));
+    for (int i = 0; i < n; ++i) s2[i] = i;
     HIPCHK(hipMemcpyAsync(qk_map, map.data(), map.size() * 4, hipMemcpyHostToDevice, st));
-    launch_embed<T>(E, Pdec, ns, row_tok, row_pos, nullptr, nullptr, 1, HCTX, CTX - 1, x_d, n, st);
     // its own all-zero ancestry table: the decode's S.anc ([w][G][CTX]) stays untouched,
     // so a device-loop decode of other slots can continue afterwards
-    return dec_layers(n, row_win, row_slot, row_pos, 1, 1, win_row0, win_nrows, win_slot, d_aqk,
-                      d_aqk ? qk_map : nullptr, n, false, fp_anc);
-  }
-
-  // grow-only device scratch for the alignment / prefill readbacks
-  DevBuf<char> scratch;
-  int ensure_scratch(size_t bytes) {
-    if (bytes <= scratch.cap) return 0;
-    HIPCHK(hipStreamSynchronize(st));
-    return scratch.reserve(bytes);
-  }
-
-  // find_alignment's device half (timing.py:163-231) for a batch of windows: window w
-  // is sot_sequence + [no_timestamps] + text + [eot] (n_tokens[w] ids at tokens[sum of
-  // the previous n_tokens]) over the audio features of slots[w].  The windows' first
-  // passes run together (up to PRE rows per pass, cross-QK of the alignment
-  // heads captured), then the text tokens' probabilities, the filtered head-mean
-  // matrices and one DTW workgroup per window (all DTWs of a pass in one launch).
-  // Outputs are concatenated in window order: probs [T_w], paths [2][T_w+1+F_w],
-  // plens [n_win].
-  int align_batch(int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
-                  const int* num_frames, const int* ah, int na, int medfilt, float* probs, int* paths,
-                  int* plens) override {
-    return align_windows(n_win, slots, tokens, n_tokens, n_sot, num_frames, ah, na, medfilt, nullptr, 0.f, probs, paths,
-                         plens, nullptr);
-  }
-
-  // wh_align_batch_open: the same pipeline, with the open-end DTW for the windows whose
-  // min_rows is not 0.  All DTWs of a pass still go in one launch: a closed window runs
-  // the open kernel with min_rows = N, which leaves it the end row N and wh_dtw's path.
-  // The slot rule of the first pass holds: it writes beam slot 0's self-KV rows of every
-  // slot it is given (check_slot_idle), so the windows of one call need a slot each.
-  int align_batch_open(int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
-                       const int* num_frames, const int* ah, int na, int medfilt, const int* min_rows,
-                       float row_penalty, float* probs, int* paths, int* plens, int* end_rows) override {
-    return align_windows(n_win, slots, tokens, n_tokens, n_sot, num_frames, ah, na, medfilt, min_rows, row_penalty,
-                         probs, paths, plens, end_rows);
-  }
-
-  // min_rows == nullptr: closed (wh_align_batch); otherwise per window, 0 = closed
-  int align_windows(int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
-                    const int* num_frames, const int* ah, int na, int medfilt, const int* min_rows, float row_penalty,
-                    float* probs, int* paths, int* plens, int* end_rows) {
-    if (!finalized) return fail(-9, "weights not finalized");
-    if (n_win < 1) return fail(-15, "align: no windows");
-    if (na < 1 || na > Ld * nh) return fail(-15, "align: alignment head count");
-    if (medfilt < 1 || medfilt > 15 || medfilt % 2 == 0) return fail(-15, "align: medfilt_width must be odd <= 15");
-    std::vector<int64_t> tok_off(n_win + 1, 0), prob_off(n_win + 1, 0), path_off(n_win + 1, 0), mat_off(n_win + 1, 0),
-        tr_off(n_win + 1, 0);
-    int rows_max = 0;
-    for (int w = 0; w < n_win; ++w) {
-      const int n = n_tokens[w], Tt = n - n_sot - 2, F = num_frames[w] / 2;
-      if (n_sot < 1 || Tt < 1) return fail(-15, "align: need sot_sequence + no_timestamps + >= 1 text token + eot");
-      if (n > CTX) return fail(-15, "align: more than 448 tokens");
-      if (F < 1 || F > 1500) return fail(-15, "align: num_frames out of range");
-      if (slots[w] < 0 || slots[w] >= Wcap) return fail(-15, "align: bad slot");
-      TRY(check_slot_idle(slots[w]));
-      const int N = Tt + 1;
-      tok_off[w + 1] = tok_off[w] + n;
-      prob_off[w + 1] = prob_off[w] + Tt;
-      path_off[w + 1] = path_off[w] + 2 * (N + F);
-      mat_off[w + 1] = mat_off[w] + ((int64_t)N * F + 63) / 64 * 64;
-      tr_off[w + 1] = tr_off[w] + (dtw_trace_bytes(N, F) + 255) / 256 * 256;
-      rows_max = std::max(rows_max, n);
-    }
-    // pass grouping: consecutive windows while the rows fit PRE and the cross-QK budget
-    const int64_t qk_row = (int64_t)na * 1500 * 4;
-    const int cap = (int)std::max<int64_t>(rows_max, std::min<int64_t>(PRE, ((int64_t)1 << 30) / qk_row));
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t b_qk = al((size_t)qk_row * cap), b_lg = al((size_t)128 * V * 4), b_mat = al(mat_off[n_win] * 4),
-                 b_tr = al(tr_off[n_win]), b_path = al(path_off[n_win] * 4), b_pr = al(prob_off[n_win] * 4 + 16),
-                 b_pl = al((size_t)n_win * 4), b_jobs = al((size_t)n_win * sizeof(DtwJob));
-    TRY(ensure_scratch(b_qk + b_lg + b_mat + b_tr + b_path + 2 * b_pr + 2 * b_pl + b_jobs));
-    char* p = scratch.p;
-    float* d_qk = (float*)p; p += b_qk;
-    float* d_lg = (float*)p; p += b_lg;
-    float* d_mat = (float*)p; p += b_mat;
-    char* d_tr = p; p += b_tr;
-    int* d_path = (int*)p; p += b_path;
-    float* d_probs = (float*)p; p += b_pr;
-    int* d_ptok = (int*)p; p += b_pr;
-    int* d_plen = (int*)p; p += b_pl;
-    int* d_end = (int*)p; p += b_pl;
-    DtwJob* d_jobs = (DtwJob*)p;
-
-    // token of every probability row (timing.py:191: text_tokens[k])
-    std::vector<int> ptok(prob_off[n_win]);
-    for (int w = 0; w < n_win; ++w)
-      for (int k = 0; k < prob_off[w + 1] - prob_off[w]; ++k) ptok[prob_off[w] + k] = tokens[tok_off[w] + n_sot + 1 + k];
-    HIPCHK(hipMemcpyAsync(d_ptok, ptok.data(), ptok.size() * 4, hipMemcpyHostToDevice, st));
-    std::vector<int> map((size_t)Ld * nh, -1);
-    for (int i = 0; i < na; ++i)
-      if (ah[i] >= 0 && ah[i] < Ld * nh) map[ah[i]] = i;
-    HIPCHK(hipMemcpyAsync(qk_map, map.data(), map.size() * 4, hipMemcpyHostToDevice, st));
-    std::vector<DtwJob> jobs(n_win);
-    const int eot = tokens[tok_off[1] - 1];
-    for (int w0 = 0; w0 < n_win;) {
-      int nw = 0, R = 0;
-      while (w0 + nw < n_win && (nw == 0 || R + n_tokens[w0 + nw] <= cap)) R += n_tokens[w0 + nw++];
-      // rows of this pass: window slot, beam slot 0, position
-      std::vector<int> rt(R), rp(R), rw(R), rs(R, 0), wr0(nw), wnr(nw), wsl(nw), sel;
-      int r = 0;
-      for (int i = 0; i < nw; ++i) {
-        const int w = w0 + i, n = n_tokens[w];
-        wr0[i] = r; wnr[i] = n; wsl[i] = slots[w];
-        for (int q = 0; q < n; ++q, ++r) { rt[r] = tokens[tok_off[w] + q]; rp[r] = q; rw[r] = slots[w]; }
-        for (int k = 0; k < n - n_sot - 2; ++k) sel.push_back(wr0[i] + n_sot + k);
-        if (tokens[tok_off[w] + n - 1] != eot) return fail(-15, "align: windows must end with the same eot");
-      }
-      for (int q = 0; q < R; ++q)
-        if (rt[q] < 0 || rt[q] >= V) return fail(-15, "align: token out of vocabulary");
-      // set before the first upload into row_pos / x_d (as first_pass does): a failing copy
-      // below must still make the next decode_steps re-embed its rows
-      rows_dirty = true;  // this first pass runs its rows through x_d / row_pos
-      HIPCHK(hipMemcpyAsync(row_tok, rt.data(), R * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(row_pos, rp.data(), R * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(row_win, rw.data(), R * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(row_slot, rs.data(), R * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(win_row0, wr0.data(), nw * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(win_nrows, wnr.data(), nw * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(win_slot, wsl.data(), nw * 4, hipMemcpyHostToDevice, st));
-      launch_embed<T>(E, Pdec, ns, row_tok, row_pos, nullptr, nullptr, 1, HCTX, CTX - 1, x_d, R, st);
-      TRY(dec_layers(R, row_win, row_slot, row_pos, 1, nw, win_row0, win_nrows, win_slot, d_qk, qk_map, R, false,
-                     fp_anc));
-      // probabilities of the text tokens, 128 logit rows at a time
-      const int64_t pb = prob_off[w0];
-      for (int c0 = 0; c0 < (int)sel.size(); c0 += 128) {
-        const int rr = std::min<int>(128, (int)sel.size() - c0);
-        HIPCHK(hipMemcpyAsync(rows_in, sel.data() + c0, rr * 4, hipMemcpyHostToDevice, st));
-        TRY(vocab(rows_in, rr, d_lg));
-        launch_token_probs(d_lg, V, rr, eot, d_ptok + pb + c0, d_probs + pb + c0, st);
-      }
-      for (int i = 0; i < nw; ++i) {
-        const int w = w0 + i, N = n_tokens[w] - n_sot - 1, F = num_frames[w] / 2;
-        float* mat = d_mat + mat_off[w];
-        launch_align_matrix(d_qk + (int64_t)wr0[i] * 1500, (int64_t)R * 1500, n_tokens[w], 1500, F, na, n_sot, N,
-                            medfilt, mat, st);
-        jobs[w] = DtwJob{mat, (unsigned*)(d_tr + tr_off[w]), d_path + path_off[w], d_plen + w, N, F, 0};
-        if (min_rows) {
-          jobs[w].min_rows = min_rows[w] ? min_rows[w] : N;
-          jobs[w].row_penalty = row_penalty;
-          jobs[w].end_row = d_end + w;
-        }
-      }
-      size_t lds = 0;
-      if (dtw_prepare(jobs.data() + w0, nw, &lds)) return fail(-15, "align: DTW shape");
-      HIPCHK(hipMemcpyAsync(d_jobs + w0, jobs.data() + w0, nw * sizeof(DtwJob), hipMemcpyHostToDevice, st));
-      int max_n = 0;
-      for (int i = 0; i < nw; ++i) max_n = std::max(max_n, jobs[w0 + i].N);
-      if (launch_dtw_jobs(d_jobs + w0, nw, max_n, jobs[w0].in_lds, lds, -1.f, min_rows != nullptr, st))
-        return fail(-15, "align: DTW launch");
-      HIPCHK(hipStreamSynchronize(st));  // host row vectors of this pass go out of scope
-      w0 += nw;
-    }
-    HIPCHK(hipMemcpyAsync(probs, d_probs, prob_off[n_win] * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(plens, d_plen, n_win * 4, hipMemcpyDeviceToHost, st));
-    if (min_rows) HIPCHK(hipMemcpyAsync(end_rows, d_end, n_win * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(paths, d_path, path_off[n_win] * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    TRY(launch_status(__func__));
-    return 0;
-  }
-
-  int align(int slot, const int* tokens, int n, int n_sot, int num_frames, const int* ah, int na, int medfilt,
-            float* probs, int* path, int* plen) override {
-    return align_batch(1, &slot, tokens, &n, n_sot, &num_frames, ah, na, medfilt, probs, path, plen);
-  }
-
-  // timing.dtw (timing.py:82-105, 139-151) of a host cost matrix x [N][M] on the GPU
-  int dtw(const float* x, int N, int M, int* path, int* plen) override {
-    if (N < 1 || M < 1 || N > 1023 || (int64_t)N * M > (int64_t)1 << 26) return fail(-15, "dtw: shape out of range");
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t b_x = al((size_t)N * M * 4), b_tr = al(dtw_trace_bytes(N, M)), b_path = al((size_t)2 * (N + M) * 4);
-    TRY(ensure_scratch(b_x + b_tr + b_path + 256 + al(sizeof(DtwJob))));
-    char* p = scratch.p;
-    float* d_x = (float*)p; p += b_x;
-    unsigned* d_tr = (unsigned*)p; p += b_tr;
-    int* d_path = (int*)p; p += b_path;
-    int* d_plen = (int*)p; p += 256;
-    DtwJob* d_job = (DtwJob*)p;
-    DtwJob job{d_x, d_tr, d_path, d_plen, N, M, 0};
-    size_t lds = 0;
-    if (dtw_prepare(&job, 1, &lds)) return fail(-15, "dtw: shape");
-    HIPCHK(hipMemcpyAsync(d_x, x, (size_t)N * M * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_job, &job, sizeof(job), hipMemcpyHostToDevice, st));
-    if (launch_dtw_jobs(d_job, 1, N, job.in_lds, lds, 1.f, false, st)) return fail(-15, "dtw launch");
-    HIPCHK(hipMemcpyAsync(plen, d_plen, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(path, d_path, (size_t)2 * (N + M) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    TRY(launch_status(__func__));
-    return 0;
-  }
-
-  // wh_dtw_open: the open-end DTW of a host cost matrix (min_rows == 0: closed, run as
-  // min_rows = N, which gives wh_dtw's path and still fills the scores)
-  int dtw_open(const float* x, int N, int M, int min_rows, float row_penalty, int* path, int* plen, int* end_row,
-               float* scores) override {
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t b_x = al((size_t)N * M * 4), b_tr = al(dtw_trace_bytes(N, M)), b_path = al((size_t)2 * (N + M) * 4),
-                 b_sc = al((size_t)N * 4);
-    TRY(ensure_scratch(b_x + b_tr + b_path + b_sc + 256 + al(sizeof(DtwJob))));
-    char* p = scratch.p;
-    float* d_x = (float*)p; p += b_x;
-    unsigned* d_tr = (unsigned*)p; p += b_tr;
-    int* d_path = (int*)p; p += b_path;
-    float* d_sc = (float*)p; p += b_sc;
-    int* d_plen = (int*)p; p += 256;  // [0] path length, [1] end row
-    DtwJob* d_job = (DtwJob*)p;
-    DtwJob job{d_x, d_tr, d_path, d_plen, N, M, 0};
-    job.min_rows = min_rows ? min_rows : N;
-    job.row_penalty = row_penalty;
-    job.end_row = d_plen + 1;
-    job.scores = scores ? d_sc : nullptr;
-    size_t lds = 0;
-    if (dtw_prepare(&job, 1, &lds)) return fail(-15, "dtw_open: shape");
-    HIPCHK(hipMemcpyAsync(d_x, x, (size_t)N * M * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_job, &job, sizeof(job), hipMemcpyHostToDevice, st));
-    if (launch_dtw_jobs(d_job, 1, N, job.in_lds, lds, 1.f, true, st)) return fail(-15, "dtw_open launch");
-    int pe[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(pe, d_plen, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(path, d_path, (size_t)2 * (N + M) * 4, hipMemcpyDeviceToHost, st));
-    if (scores) HIPCHK(hipMemcpyAsync(scores, d_sc, (size_t)N * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    TRY(launch_status(__func__));
-    *plen = pe[0];
-    *end_row = pe[1];
-    return 0;
-  }
-
-  int prefill_logits(int slot, const int* tokens, int n, float* lg, const int* ah, int na, float* aqk) override {
-    float* d_aqk = nullptr;
-    float* out = nullptr;
-    if (na > 0 && aqk) HIPCHK(hipMalloc((void**)&d_aqk, (size_t)na * n * 1500 * 4));
-    HIPCHK(hipMalloc((void**)&out, (size_t)n * V * 4));
-    std::vector<std::vector<int>> keep;
-    int rc = first_pass(slot, tokens, n, ah, na, d_aqk, keep);
-    std::vector<int> s2(n);
-    for (int i = 0; i < n; ++i) s2[i] = i;
-    for (int r0 = 0; r0 < n && rc == 0; r0 += 128) {
+    TRY(run_rows(rows, 1, d_aqk, d_aqk ? qk_map : nullptr, n, fp_anc));
+    for (int r0 = 0; r0 < n; r0 += 128) {
       const int rr = std::min(128, n - r0);
-      if (hipMemcpyAsync(rows_in, s2.data() + r0, rr * 4, hipMemcpyHostToDevice, st) != hipSuccess) rc = -100;
-      if (!rc) rc = vocab(rows_in, rr, out + (size_t)r0 * V);
-      if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = -100;
+      HIPCHK(hipMemcpyAsync(rows_in, s2.data() + r0, rr * 4, hipMemcpyHostToDevice, st));
+      TRY(vocab(rows_in, rr, out + (size_t)r0 * V));
+      HIPCHK(hipStreamSynchronize(st));
     }
-    if (!rc && hipMemcpyAsync(lg, out, (size_t)n * V * 4, hipMemcpyDeviceToHost, st) != hipSuccess) rc = -100;
-    if (!rc && d_aqk && hipMemcpyAsync(aqk, d_aqk, (size_t)na * n * 1500 * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
-      rc = -100;
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -100;
-    if (hipFree(out) != hipSuccess && !rc) rc = -100;
-    if (d_aqk && hipFree(d_aqk) != hipSuccess && !rc) rc = -100;
-    if (rc == -100) return fail(-100, "prefill_logits: HIP copy / sync / free failed");
-    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(lg, out, (size_t)n * V * 4, hipMemcpyDeviceToHost, st));
+    if (d_aqk) HIPCHK(hipMemcpyAsync(aqk, d_aqk, (size_t)na * n * 1500 * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     TRY(launch_status(__func__));
     return 0;
   }
@@ -1965,9 +1457,9 @@ int wh_set_phrase_bias(wh_ctx* ctx, int n_phrases, const int* tokens, const int*
       return fail(-11, ph + ": more than " + std::to_string(wh::BIAS_MAX_ENTRIES) + " tokens in total");
     if (!(boost[j] > 0.f) || std::isinf(boost[j])) return fail(-11, ph + ": boost must be finite and greater than 0");
     for (int i = offsets[j]; i < offsets[j + 1]; ++i) {
-      if (tokens[i] < 0 || tokens[i] >= ctx->n_vocab)
+      if (tokens[i] < 0 || tokens[i] >= ctx->V)
         return fail(-11, ph + ": id " + std::to_string(tokens[i]) + " outside the vocabulary [0, " +
-                             std::to_string(ctx->n_vocab) + ")");
+                             std::to_string(ctx->V) + ")");
       const int k = i - offsets[j];
       const float start_bonus = boost[j] * start;  // fl32(b * start): one fp32 multiply
       tab.push_back({tokens[i], k, k == 0 ? start_bonus : boost[j], 0});
@@ -2136,17 +1628,17 @@ int wh_prefill_logits(wh_ctx* ctx, int slot, const int* tokens, int n, float* lo
 }
 int wh_align(wh_ctx* ctx, int slot, const int* tokens, int n_tokens, int n_sot, int num_frames, const int* align_heads,
              int n_align, int medfilt_width, float* token_probs, int* path, int* path_len) {
-  CTXCALL(ctx->align(slot, tokens, n_tokens, n_sot, num_frames, align_heads, n_align, medfilt_width, token_probs, path,
-                     path_len));
+  CTXCALL(ctx->align_windows(1, &slot, tokens, &n_tokens, n_sot, &num_frames, align_heads, n_align, medfilt_width,
+                             nullptr, 0.f, token_probs, path, path_len, nullptr));
 }
 int wh_align_batch(wh_ctx* ctx, int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
                    const int* num_frames, const int* align_heads, int n_align, int medfilt_width, float* token_probs,
                    int* paths, int* path_lens) {
-  CTXCALL(ctx->align_batch(n_win, slots, tokens, n_tokens, n_sot, num_frames, align_heads, n_align, medfilt_width,
-                           token_probs, paths, path_lens));
+  CTXCALL(ctx->align_windows(n_win, slots, tokens, n_tokens, n_sot, num_frames, align_heads, n_align, medfilt_width,
+                             nullptr, 0.f, token_probs, paths, path_lens, nullptr));
 }
 int wh_dtw(wh_ctx* ctx, const float* x, int n_rows, int n_cols, int* path, int* path_len) {
-  CTXCALL(ctx->dtw(x, n_rows, n_cols, path, path_len));
+  CTXCALL(ctx->dtw(x, n_rows, n_cols, path, path_len, nullptr));
 }
 int wh_dtw_open(wh_ctx* ctx, const float* x, int n_rows, int n_cols, int min_rows, float row_penalty, int* path,
                 int* path_len, int* end_row, float* end_scores) {
@@ -2158,7 +1650,8 @@ int wh_dtw_open(wh_ctx* ctx, const float* x, int n_rows, int n_cols, int min_row
   if (min_rows < 0 || min_rows > n_rows) return fail(-15, "wh_dtw_open: min_rows outside 0..n_rows");
   if (!(row_penalty >= 0.f) || std::isinf(row_penalty))
     return fail(-15, "wh_dtw_open: row_penalty must be finite and >= 0");
-  CTXCALL(ctx->dtw_open(x, n_rows, n_cols, min_rows, row_penalty, path, path_len, end_row, end_scores));
+  const DecodeLoop::DtwOpen open{min_rows, row_penalty, end_row, end_scores};
+  CTXCALL(ctx->dtw(x, n_rows, n_cols, path, path_len, &open));
 }
 int wh_align_batch_open(wh_ctx* ctx, int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
                         const int* num_frames, const int* align_heads, int n_align, int medfilt_width,
@@ -2176,8 +1669,8 @@ int wh_align_batch_open(wh_ctx* ctx, int n_win, const int* slots, const int* tok
     if (min_rows[w] < 0 || min_rows[w] > std::max(n_rows, 0))
       return fail(-15, "wh_align_batch_open: min_rows of window " + std::to_string(w) + " outside 0..n_rows");
   }
-  CTXCALL(ctx->align_batch_open(n_win, slots, tokens, n_tokens, n_sot, num_frames, align_heads, n_align, medfilt_width,
-                                min_rows, row_penalty, token_probs, paths, path_lens, end_rows));
+  CTXCALL(ctx->align_windows(n_win, slots, tokens, n_tokens, n_sot, num_frames, align_heads, n_align, medfilt_width,
+                             min_rows, row_penalty, token_probs, paths, path_lens, end_rows));
 }
 int wh_stats(wh_ctx* ctx, double* out, int n) {
   if (!ctx || !out) return fail(-1, "null argument");
