@@ -396,6 +396,42 @@ int wh_align_batch_open(wh_ctx* ctx, int n_win, const int* slots, const int* tok
                         const int* min_rows, float row_penalty, float* token_probs, int* paths, int* path_lens,
                         int* end_rows);
 
+/* Scoring: how well a given token fits each row, without the logits ever being stored
+   (csrc/wh_score.hip: the vocabulary projection with an online log-sum-exp epilogue).
+   For row r of x [n_rows][n_text_state] and the token embedding E [n_vocab][n_text_state]:
+     z[v]           sum_k x[r][k] E[v][k], accumulated in fp32 with k ascending
+     m, lse         max_v z[v],  m + log sum_v exp(z[v] - m)
+     logprob[r]     z[targets[r]] - lse
+     top_id[r]      the smallest v with z[v] == m
+     top_logprob[r] m - lse
+   x holds rows as they leave the decoder's final LayerNorm; it is converted to the context
+   type first, which in an fp16 context rounds every element to the nearest fp16 value, ties
+   to even.  n_rows in 1..4096 (run 256 rows per pass).  A row's three outputs are
+   bit-identical whatever other rows share the call and wherever the row stands in it.  Needs
+   finalized weights; touches no decode state.  Refused before any HIP call, with a negative
+   code and wh_last_error naming the field and its index: a null pointer, n_rows outside
+   1..4096, a target outside [0, n_vocab), weights not finalized. */
+int wh_vocab_score(wh_ctx* ctx, const float* x, int n_rows, const int* targets, float* logprob, int* top_id,
+                   float* top_logprob);
+/* Teacher-forced log-probabilities of given token sequences.  Sequence s is n_tokens[s] ids
+   (2..n_text_ctx), back to back in tokens, run as a first pass over the audio features in
+   encoder slot slots[s]; its first n_ctx[s] >= 1 ids are context (a prompt, the SOT sequence,
+   <|notimestamps|>).  For every position i in [n_ctx[s], n_tokens[s]) the call gives
+   logprob = log softmax(logits of row i - 1)[tokens[i]] over the WHOLE vocabulary of the RAW
+   logits (no suppression, no timestamp rules, no phrase bias: not the filtered distribution a
+   decode samples from), and that row's top_id / top_logprob as in wh_vocab_score.  Outputs are
+   concatenated in sequence order, n_tokens[s] - n_ctx[s] entries each.  Several sequences may
+   name the same slot (candidates for one recording): a sequence borrows the self-KV rows of a
+   window that is idle (one that the current device-loop batch is not decoding, as
+   wh_prefill_logits requires of its slot) and overwrites them; more sequences than idle
+   windows, or more rows than a first pass holds, run in several passes.  Refused before any
+   HIP call, with a negative code and wh_last_error naming the field and its index, nothing
+   changed: a null pointer, n_seq < 1, a slot outside the context's windows, n_tokens[s]
+   outside 2..n_text_ctx, n_ctx[s] outside 1..n_tokens[s] - 1, an id outside [0, n_vocab),
+   weights not finalized. */
+int wh_score_batch(wh_ctx* ctx, int n_seq, const int* slots, const int* tokens, const int* n_tokens, const int* n_ctx,
+                   float* logprob, int* top_id, float* top_logprob);
+
 /* the kernels the decoder step runs for a batch of n_win windows x group rows, as
    "proj=<name>,xattn=<name>" (the dominant projection family and the cross-attention;
    what bench.py labels its roofline lines with).  Returns the length written. */

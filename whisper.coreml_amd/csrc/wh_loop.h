@@ -1,8 +1,8 @@
 // The host side of a context's decode loop and of alignment: the decode options, the step
 // graph and its two-deep done-flag poll, the readback, the per-step ABI's checks, the DTW
-// driver and the window bookkeeping of wh_align_batch.  None of it depends on the model's
-// element type, so it is a plain struct compiled once (csrc/wh_loop.hip) and the base of
-// wh_ctx; what does depend on it, it reaches through three virtuals of Ctx<T>.
+// driver and the window bookkeeping of wh_align_batch and wh_score_batch.  None of it depends
+// on the model's element type, so it is a plain struct compiled once (csrc/wh_loop.hip) and the
+// base of wh_ctx; what does depend on it, it reaches through five virtuals of Ctx<T>.
 #pragma once
 #include <string>
 #include <vector>
@@ -11,6 +11,7 @@
 #include "wh_host.h"
 #include "wh_kernels.h"
 #include "wh_rows.h"
+#include "wh_score.h"
 #include "whisper_hip.h"
 
 namespace wh {
@@ -87,6 +88,24 @@ struct DecodeLoop {
   int align_windows(int n_win, const int* slots, const int* tokens, const int* n_tokens, int n_sot,
                     const int* num_frames, const int* ah, int na, int medfilt, const int* min_rows, float row_penalty,
                     float* probs, int* paths, int* plens, int* end_rows);
+  // wh_vocab_score / wh_score_batch (whisper_hip.h).  The *_check halves are host code with
+  // no HIP call: the entry points run them before the context is entered.
+  int vocab_score_check(const float* x, int n_rows, const int* targets, const float* logprob, const int* top_id,
+                        const float* top_logprob);
+  // n_rows host rows [nh * 64] through the fused kernel, SCORE_PASS rows per pass
+  int vocab_score(const float* x, int n_rows, const int* targets, float* logprob, int* top_id, float* top_logprob);
+  int score_check(int n_seq, const int* slots, const int* tokens, const int* n_tokens, const int* n_ctx,
+                  const float* logprob, const int* top_id, const float* top_logprob);
+  // Teacher-forced scoring: sequence s runs as one window of a first pass, its self-KV rows in
+  // an idle window (check_slot_idle) that it borrows for the pass, its cross-attention over
+  // encoder slot slots[s], so several sequences may name one slot.  Row i - 1 scores tokens[i]
+  // for i in [n_ctx, n_tokens); the last token is never fed.  A pass takes consecutive
+  // sequences while an idle window and PRE rows are left.
+  int score_windows(int n_seq, const int* slots, const int* tokens, const int* n_tokens, const int* n_ctx,
+                    float* logprob, int* top_id, float* top_logprob);
+  static constexpr int SCORE_PASS = 256;  // rows per pass of vocab_score: 1 MB of records
+  // the device operands of one fused scoring launch (wh_score.h ScoreArgs)
+  struct ScoreOut { const int* target; void* rec; float* logprob; int* top_id; float* top_logprob; };
 
  protected:
   ~DecodeLoop() = default;
@@ -97,4 +116,9 @@ struct DecodeLoop {
   // [na][p.R][1500], then probs[k] of ptok[k] at row sel[k] through d_lg (128 logit rows)
   virtual int align_rows(const wh::RowPlan& p, const std::vector<int>& sel, float* d_qk, float* d_lg, int eot,
                          const int* ptok, float* probs) = 0;
+  // one scoring pass: the first pass of p's rows, then the fused kernel on rows sel[0..n_sel) of
+  // the final LayerNorm's output
+  virtual int score_rows(const wh::RowPlan& p, const int* sel, int n_sel, const ScoreOut& o) = 0;
+  // n rows of fp32 device rows xf, converted to the context type in xt, through the fused kernel
+  virtual int score_host_rows(const float* xf, void* xt, int n, const ScoreOut& o) = 0;
 };

@@ -372,3 +372,121 @@ int DecodeLoop::align_windows(int n_win, const int* slots, const int* tokens, co
   TRY(launch_status(__func__));
   return 0;
 }
+
+int DecodeLoop::vocab_score_check(const float* x, int n_rows, const int* targets, const float* logprob, const int* top_id,
+                                  const float* top_logprob) {
+  const char* null = !x ? "x" : !targets ? "targets" : !logprob ? "logprob" : !top_id ? "top_id" : !top_logprob ? "top_logprob" : nullptr;
+  if (null) return fail(-1, std::string("wh_vocab_score: null argument (") + null + ")");
+  if (n_rows < 1 || n_rows > 4096) return fail(-15, "wh_vocab_score: n_rows = " + std::to_string(n_rows) + " outside 1..4096");
+  for (int r = 0; r < n_rows; ++r)
+    if (targets[r] < 0 || targets[r] >= V)
+      return fail(-15, "wh_vocab_score: targets[" + std::to_string(r) + "] = " + std::to_string(targets[r]) +
+                           " outside [0, " + std::to_string(V) + ")");
+  if (!finalized) return fail(-9, "wh_vocab_score: weights not finalized");
+  return 0;
+}
+
+int DecodeLoop::vocab_score(const float* x, int n_rows, const int* targets, float* logprob, int* top_id,
+                            float* top_logprob) {
+  const int ns = nh * 64;
+  const size_t b_x = al256((size_t)SCORE_PASS * ns * 4), b_rec = al256(score_rec_bytes(SCORE_PASS)),
+               b_o = al256((size_t)SCORE_PASS * 4);
+  TRY(ensure_scratch(2 * b_x + b_rec + 4 * b_o));
+  char* p = scratch.p;
+  float* d_xf = (float*)p; p += b_x;
+  void* d_xt = p; p += b_x;
+  void* d_rec = p; p += b_rec;
+  int* d_tgt = (int*)p; p += b_o;
+  float* d_lp = (float*)p; p += b_o;
+  int* d_top = (int*)p; p += b_o;
+  float* d_tlp = (float*)p;
+  for (int r0 = 0; r0 < n_rows; r0 += SCORE_PASS) {
+    const int n = std::min(SCORE_PASS, n_rows - r0);
+    HIPCHK(hipMemcpyAsync(d_xf, x + (size_t)r0 * ns, (size_t)n * ns * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_tgt, targets + r0, n * 4, hipMemcpyHostToDevice, st));
+    TRY(score_host_rows(d_xf, d_xt, n, ScoreOut{d_tgt, d_rec, d_lp, d_top, d_tlp}));
+    HIPCHK(hipMemcpyAsync(logprob + r0, d_lp, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(top_id + r0, d_top, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(top_logprob + r0, d_tlp, n * 4, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(launch_status(__func__));
+  return 0;
+}
+
+int DecodeLoop::score_check(int n_seq, const int* slots, const int* tokens, const int* n_tokens, const int* n_ctx,
+                            const float* logprob, const int* top_id, const float* top_logprob) {
+  const char* null = !slots ? "slots" : !tokens ? "tokens" : !n_tokens ? "n_tokens" : !n_ctx ? "n_ctx" : !logprob ? "logprob"
+                     : !top_id ? "top_id" : !top_logprob ? "top_logprob" : nullptr;
+  if (null) return fail(-1, std::string("wh_score_batch: null argument (") + null + ")");
+  if (n_seq < 1) return fail(-15, "wh_score_batch: n_seq = " + std::to_string(n_seq) + " below 1");
+  auto at = [](const char* field, int i, int v) { return std::string("wh_score_batch: ") + field + "[" + std::to_string(i) + "] = " + std::to_string(v); };
+  int64_t off = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    if (slots[s] < 0 || slots[s] >= Wcap) return fail(-15, at("slots", s, slots[s]) + " outside 0.." + std::to_string(Wcap - 1));
+    if (n_tokens[s] < 2 || n_tokens[s] > CTX) return fail(-15, at("n_tokens", s, n_tokens[s]) + " outside 2.." + std::to_string(CTX));
+    if (n_ctx[s] < 1 || n_ctx[s] > n_tokens[s] - 1)
+      return fail(-15, at("n_ctx", s, n_ctx[s]) + " outside 1.." + std::to_string(n_tokens[s] - 1));
+    for (int i = 0; i < n_tokens[s]; ++i)
+      if (tokens[off + i] < 0 || tokens[off + i] >= V)
+        return fail(-15, at("tokens", (int)(off + i), tokens[off + i]) + " outside [0, " + std::to_string(V) + ") (id " +
+                             std::to_string(i) + " of sequence " + std::to_string(s) + ")");
+    off += n_tokens[s];
+  }
+  if (!finalized) return fail(-9, "wh_score_batch: weights not finalized");
+  return 0;
+}
+
+int DecodeLoop::score_windows(int n_seq, const int* slots, const int* tokens, const int* n_tokens, const int* n_ctx,
+                              float* logprob, int* top_id, float* top_logprob) {
+  // the self-KV windows a sequence may borrow: every one the live batch is not decoding in
+  std::vector<int> idle;
+  for (int w = 0; w < Wcap; ++w) {
+    const int rc = check_slot_idle(w);
+    if (rc == 0) idle.push_back(w);
+    else if (rc != -15) return rc;
+  }
+  if (idle.empty()) return fail(-15, "wh_score_batch: every self-KV window is still decoding");
+  std::vector<int64_t> tok_off(n_seq + 1, 0), out_off(n_seq + 1, 0);
+  for (int s = 0; s < n_seq; ++s) {
+    tok_off[s + 1] = tok_off[s] + n_tokens[s];
+    out_off[s + 1] = out_off[s] + n_tokens[s] - n_ctx[s];
+  }
+  const size_t b_rows = al256((size_t)PRE * 4), b_rec = al256(score_rec_bytes(PRE)), b_out = al256(out_off[n_seq] * 4);
+  TRY(ensure_scratch(2 * b_rows + b_rec + 3 * b_out));
+  char* p = scratch.p;
+  int* d_sel = (int*)p; p += b_rows;
+  int* d_tgt = (int*)p; p += b_rows;
+  void* d_rec = p; p += b_rec;
+  float* d_lp = (float*)p; p += b_out;
+  int* d_top = (int*)p; p += b_out;
+  float* d_tlp = (float*)p;
+  for (int s0 = 0; s0 < n_seq;) {
+    // rows of this pass: the borrowed window, beam slot 0, position; sel: the rows that are scored
+    RowPlan rows;
+    std::vector<int> sel, tgt;
+    int nw = 0;
+    while (s0 + nw < n_seq && nw < (int)idle.size() && rows.R + n_tokens[s0 + nw] - 1 <= PRE) {
+      const int s = s0 + nw, n = n_tokens[s];
+      const int* t = tokens + tok_off[s];
+      rows.add(idle[nw], slots[s], t, n - 1);
+      for (int i = n_ctx[s]; i < n; ++i) {
+        sel.push_back(rows.win_row0[nw] + i - 1);
+        tgt.push_back(t[i]);
+      }
+      ++nw;
+    }
+    HIPCHK(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_tgt, tgt.data(), tgt.size() * 4, hipMemcpyHostToDevice, st));
+    const int64_t ob = out_off[s0];
+    TRY(score_rows(rows, d_sel, (int)sel.size(), ScoreOut{d_tgt, d_rec, d_lp + ob, d_top + ob, d_tlp + ob}));
+    HIPCHK(hipStreamSynchronize(st));  // the row plan, sel and tgt of this pass go out of scope
+    s0 += nw;
+  }
+  HIPCHK(hipMemcpyAsync(logprob, d_lp, out_off[n_seq] * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(top_id, d_top, out_off[n_seq] * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(top_logprob, d_tlp, out_off[n_seq] * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  TRY(launch_status(__func__));
+  return 0;
+}

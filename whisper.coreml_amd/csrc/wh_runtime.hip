@@ -1194,6 +1194,23 @@ struct Ctx : public wh_ctx {
     return 0;
   }
 
+  int score_launch(const T* X, const int* sel, int n, const ScoreOut& o) {
+    ScoreArgs a;
+    a.X = X; a.E = E; a.x_rows = sel; a.target = o.target; a.rec = (float4_t*)o.rec;
+    a.logprob = o.logprob; a.top_id = o.top_id; a.top_logprob = o.top_logprob;
+    a.ldx = ns; a.R = n; a.V = V; a.K = ns;
+    if (launch_vocab_score<T>(a, st)) return fail(-15, "score: k_score_part does not serve this n_state / n_vocab");
+    return 0;
+  }
+  int score_rows(const RowPlan& p, const int* sel, int n_sel, const ScoreOut& o) override {
+    TRY(run_rows(p, 1, nullptr, nullptr, 0, fp_anc));
+    return score_launch(xn_d, sel, n_sel, o);
+  }
+  int score_host_rows(const float* xf, void* xt, int n, const ScoreOut& o) override {
+    launch_score_cast<T>(xf, (T*)xt, (int64_t)n * ns, st);
+    return score_launch((const T*)xt, nullptr, n, o);
+  }
+
   // Whisper.forward (model.py:110-119): all-row logits of a first pass of `n` tokens at
   // offset 0 for one window slot (beam slot 0, a 1-beam anc layout), optional raw cross-QK of
   // the alignment heads [na][n][1500].  Refused on a slot that is still decoding
@@ -1671,6 +1688,22 @@ int wh_align_batch_open(wh_ctx* ctx, int n_win, const int* slots, const int* tok
   }
   CTXCALL(ctx->align_windows(n_win, slots, tokens, n_tokens, n_sot, num_frames, align_heads, n_align, medfilt_width,
                              min_rows, row_penalty, token_probs, paths, path_lens, end_rows));
+}
+int wh_vocab_score(wh_ctx* ctx, const float* x, int n_rows, const int* targets, float* logprob, int* top_id,
+                   float* top_logprob) {
+  // refused here, before the context is entered (no HIP call yet)
+  if (!ctx) return fail(-1, "wh_vocab_score: null context");
+  const int rc = ctx->vocab_score_check(x, n_rows, targets, logprob, top_id, top_logprob);
+  if (rc) return rc;
+  CTXCALL(ctx->vocab_score(x, n_rows, targets, logprob, top_id, top_logprob));
+}
+int wh_score_batch(wh_ctx* ctx, int n_seq, const int* slots, const int* tokens, const int* n_tokens, const int* n_ctx,
+                   float* logprob, int* top_id, float* top_logprob) {
+  // refused here, before the context is entered (no HIP call yet)
+  if (!ctx) return fail(-1, "wh_score_batch: null context");
+  const int rc = ctx->score_check(n_seq, slots, tokens, n_tokens, n_ctx, logprob, top_id, top_logprob);
+  if (rc) return rc;
+  CTXCALL(ctx->score_windows(n_seq, slots, tokens, n_tokens, n_ctx, logprob, top_id, top_logprob));
 }
 int wh_stats(wh_ctx* ctx, double* out, int n) {
   if (!ctx || !out) return fail(-1, "null argument");

@@ -127,6 +127,8 @@ _EXPORTS = {
                             POINTER(c_int), c_void_p]),
     "wh_align_batch_open": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                     c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wh_vocab_score": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wh_score_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wh_stats": (c_int, [c_void_p, POINTER(c_double), c_int]),
     "wh_sync": (c_int, [c_void_p]),
     "wh_time_stage": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
@@ -972,6 +974,38 @@ class HipContext:
         self._check(self.lib.wh_dtw_open(self.h, _ptr(x), N, M, int(min_rows), float(row_penalty), _ptr(path),
                                          ctypes.byref(n), ctypes.byref(e), _ptr(scores)), "wh_dtw_open")
         return path[:, :n.value].copy(), e.value, scores[:N].copy()
+
+    def vocab_score(self, x: np.ndarray, targets: Sequence[int]):
+        """wh_vocab_score: (logprob, top_id, top_logprob) per row of x [rows][n_text_state],
+        rows as they leave the decoder's final LayerNorm."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        t = np.ascontiguousarray(targets, dtype=np.int32)
+        if x.ndim != 2 or x.shape[1] != self.dims["n_text_state"] or t.shape != (x.shape[0],):
+            raise ValueError(f"vocab_score: x {x.shape} is not [rows][n_text_state] with one target per row")
+        n = x.shape[0]
+        lp, top, tlp = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
+        self._check(self.lib.wh_vocab_score(self.h, _ptr(x), n, _ptr(t), _ptr(lp), _ptr(top), _ptr(tlp)),
+                    "wh_vocab_score")
+        return lp[:n], top[:n], tlp[:n]
+
+    def score_batch(self, slots: Sequence[int], token_lists: Sequence[Sequence[int]], n_ctx: Sequence[int]):
+        """wh_score_batch: one (logprob, top_id, top_logprob) per sequence, each over the
+        positions n_ctx[s]..len(token_lists[s]) - 1.  It writes self-KV rows of idle windows."""
+        n = len(token_lists)
+        if len(slots) != n or len(n_ctx) != n:
+            raise ValueError("score_batch: one slot and one n_ctx per token list")
+        toks = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
+                                                   or [np.zeros(0, np.int32)]))
+        ntok = np.asarray([len(t) for t in token_lists], dtype=np.int32)
+        nctx = np.ascontiguousarray(n_ctx, dtype=np.int32)
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        counts = np.maximum(ntok - nctx, 0)
+        total = max(int(counts.sum()), 1)
+        lp, top, tlp = np.zeros(total, np.float32), np.zeros(total, np.int32), np.zeros(total, np.float32)
+        self._check(self.lib.wh_score_batch(self.h, n, _ptr(sl), _ptr(toks), _ptr(ntok), _ptr(nctx), _ptr(lp),
+                                            _ptr(top), _ptr(tlp)), "wh_score_batch")
+        ends = np.cumsum(counts)
+        return [(lp[e - c:e].copy(), top[e - c:e].copy(), tlp[e - c:e].copy()) for e, c in zip(ends, counts)]
 
     def stats(self) -> dict:
         out = (c_double * N_STATS)()
