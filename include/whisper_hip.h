@@ -287,6 +287,39 @@ int wh_set_cross_kv_format(wh_ctx* ctx, int fmt);
 int wh_read_cross_kv8(wh_ctx* ctx, int slot, int layer, uint8_t* k_codes, float* k_scales, uint8_t* v_codes,
                       float* v_scales);
 
+/* Encoder formats.  WH_ENC_FP8_E4M3 runs the four GEMMs of every encoder block (QKV,
+   attention-out, fc1, fc2; batched and single-window encode) on the 8-bit matrix path:
+   E4M3 codes for both operands, fp32 accumulation.  The convolutions, the encoder attention,
+   ln_post and the cross-KV GEMM stay fp16; the residual stream stays fp32.  Off by default; the
+   default path runs the same kernels, launches and buffers as before.
+     weights      one fp32 scale per output channel (row of the [out][in] matrix):
+                    amax = max |w| over the row (w: the fp16 weight), scale = amax / 448  (fp32)
+                    code = e4m3(clamp(w / scale, -448, 448))   (OCP E4M3, round to nearest even)
+                  quantised once (at wh_finalize, or when the format is set after it) into a
+                  buffer of their own; the fp16 weights stay, so the format can be switched.
+     activations  one fp32 scale per row over the whole K, same rule, computed for every GEMM
+                  input at run time from its fp16 value (the LayerNorm output, the attention
+                  output, the GELU output).
+   amax == 0 gives scale 0 and codes 0; the NaN codes 0x7F / 0xFF are never written.
+     Y[m][n] = sa[m] * sw[n] * sum_k code_x[m][k] code_w[n][k]   (+ bias, then the fp16 epilogue)
+   Accuracy on real speech is unmeasured: Whisper's encoder is known for outlier channels,
+   which one scale per row may serve poorly.
+   wh_set_encoder_format: before or after wh_finalize, and between encodes.  Refused with
+   wh_last_error set and the context unchanged: WH_ENC_FP8_E4M3 on an fp32 context, an unknown
+   format.  wh_encoder_kernels: which GEMM kernel each of the four runs for an encode of n_win
+   windows, e.g. "encoder=fp8,qkv=k_gemm8<256x128>,..." (as wh_step_kernels: bytes written).
+   wh_fp8_linear (for tests): y = x w^T (+ bias, GELU if gelu) through the encoder's 8-bit path:
+   x [M][K] and w [N][K] are rounded to fp16, quantised by k_quant_rows / k_quant_weights,
+   multiplied by k_gemm8 (tile: 0 = the encoder's choice for the shape, 256 / 128 = that tile),
+   stored as fp16 and widened.  The codes and scales come back with it.  Refused by name: an
+   fp32 context, K not a multiple of the K-tile (128), N not a multiple of the tile's columns
+   (128 for tile 256, 64 for tile 128). */
+enum { WH_ENC_NATIVE = 0, WH_ENC_FP8_E4M3 = 1 };
+int wh_set_encoder_format(wh_ctx* ctx, int fmt);
+int wh_encoder_kernels(wh_ctx* ctx, int n_win, char* buf, int cap);
+int wh_fp8_linear(wh_ctx* ctx, int M, int N, int K, const float* x, const float* w, const float* bias, int gelu,
+                  int tile, float* y, uint8_t* x_codes, float* x_scales, uint8_t* w_codes, float* w_scales);
+
 /* decode n_win windows (slots 0..n_win-1): prefill of the initial tokens
    (init_tokens[w*max_init + i], i < n_init[w]) and the first token update */
 int wh_decode_begin(wh_ctx* ctx, int n_win, const wh_decode_opts* opts, const int* init_tokens, const int* n_init,

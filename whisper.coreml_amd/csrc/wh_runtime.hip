@@ -19,6 +19,7 @@
 #include "wh_align.h"
 #include "wh_audio.h"
 #include "wh_gemm.h"
+#include "wh_gemm8.h"
 #include "wh_host.h"
 #include "wh_kernels.h"
 #include "wh_loop.h"
@@ -63,6 +64,11 @@ struct EncLayer {
   float *ln1_g, *ln1_b, *bqkv, *bo, *ln2_g, *ln2_b, *b1, *b2;
   T *wqkv, *wo, *w1, *w2;
 };
+// the 8-bit copy of an encoder layer's four weights: codes [out][in], one scale per out
+struct Enc8Layer {
+  uint8_t *wqkv, *wo, *w1, *w2;
+  float *sqkv, *so, *s1, *s2;
+};
 template <typename T>
 struct DecLayer {
   float *ln1_g, *ln1_b, *bqkv, *bo, *lnx_g, *lnx_b, *bqx, *box, *ln2_g, *ln2_b, *b1, *b2;
@@ -84,6 +90,10 @@ struct wh_ctx : DecodeLoop {
   virtual int read_ckv(int slot, int layer, float* k, float* v) = 0;
   virtual int set_ckv_format(int fmt) = 0;
   virtual int read_ckv8(int slot, int layer, uint8_t* kc, float* ks, uint8_t* vc, float* vs) = 0;
+  virtual int set_enc_format(int fmt) = 0;
+  virtual std::string encoder_kernels(int n_win) const = 0;
+  virtual int fp8_linear(int M, int N, int K, const float* x, const float* w, const float* bias, int gelu, int tile,
+                         float* y, uint8_t* xc, float* xs, uint8_t* wc, float* ws) = 0;
   virtual int decode_begin(int n_win, const wh_decode_opts* o, const int* init, const int* n_init, int max_init,
                            const int* sot_index, const int* slots) = 0;
   virtual int step_prefill(int n_win, int G, const int* init, const int* n_init, int max_init, const int* sot_index,
@@ -132,6 +142,15 @@ struct Ctx : public wh_ctx {
   // every cross-KV GEMM; null = the step reads ckv.  Allocated once, when the format is chosen
   char* ckv8 = nullptr;
   bool encoded = false;  // an encode has run: the format is fixed
+  // encoder format (wh_set_encoder_format).  The 8-bit weight copies and the activation
+  // codes + row scales of one GEMM input ([WE x 1500][<= 4n] bytes) are allocated when
+  // WH_ENC_FP8_E4M3 is first chosen and kept until the context is destroyed
+  int enc_fmt = WH_ENC_NATIVE;
+  char* e8_base = nullptr;
+  std::vector<Enc8Layer> enc8;
+  uint8_t* e8x = nullptr;
+  float* e8s = nullptr;
+  bool e8_quantised = false;
   const void* kv8_layer(int l) const { return ckv8 ? ckv8 + (size_t)l * Wcap * ckv8_slot_bytes(nh) : nullptr; }
   float* x_e;
   int64_t* d_seeks;
@@ -196,6 +215,7 @@ struct Ctx : public wh_ctx {
     if (wbase) rel(hipFree(wbase), "hipFree(weights)");
     if (abase) rel(hipFree(abase), "hipFree(activations)");
     if (ckv8) rel(hipFree(ckv8), "hipFree(cross-KV 8-bit copy)");
+    if (e8_base) rel(hipFree(e8_base), "hipFree(encoder 8-bit copy)");
     audio.release(rel);
     scratch.release(rel, "hipFree(scratch)");
     if (h_done) rel(hipHostFree(h_done), "hipHostFree(done flags)");
@@ -494,6 +514,117 @@ struct Ctx : public wh_ctx {
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     finalized = true;
+    if (enc_fmt == WH_ENC_FP8_E4M3) TRY(quantise_enc8());
+    return 0;
+  }
+
+  // ------------------------------------------------------------ encoder format
+  int quantise_enc8() {
+    const int n = ns;
+    for (int l = 0; l < La; ++l) {
+      const auto& e = enc[l];
+      const auto& q = enc8[l];
+      launch_quant_weights(e.wqkv, q.wqkv, q.sqkv, 3 * n, n, st);
+      launch_quant_weights(e.wo, q.wo, q.so, n, n, st);
+      launch_quant_weights(e.w1, q.w1, q.s1, 4 * n, n, st);
+      launch_quant_weights(e.w2, q.w2, q.s2, n, 4 * n, st);
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(launch_status(__func__));
+    e8_quantised = true;
+    return 0;
+  }
+  int set_enc_format(int fmt) override {
+    if (fmt != WH_ENC_NATIVE && fmt != WH_ENC_FP8_E4M3)
+      return fail(-12, "encoder_format: unknown format " + std::to_string(fmt));
+    if (fmt == WH_ENC_FP8_E4M3 && sizeof(T) != 2)
+      return fail(-12, "encoder_format: WH_ENC_FP8_E4M3 needs an fp16 context (this one is fp32)");
+    if (fmt == WH_ENC_FP8_E4M3 && !e8_base) {
+      const size_t n = ns, WE = std::min(Wcap, enc_chunk());
+      auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+      const size_t per_layer = al(3 * n * n) + al(n * n) + 2 * al(4 * n * n) + al(3 * n * 4) + 2 * al(n * 4) + al(4 * n * 4);
+      const size_t bytes = La * per_layer + al(WE * 1500 * 4 * n) + al(WE * 1500 * 4);
+      void* p = nullptr;
+      HIPCHK(hipMalloc(&p, bytes));
+      e8_base = (char*)p;
+      Arena ar;
+      ar.base = e8_base;
+      ar.cap = bytes;
+      enc8.resize(La);
+      for (auto& q : enc8) {
+        q.wqkv = (uint8_t*)ar.take(3 * n * n); q.wo = (uint8_t*)ar.take(n * n);
+        q.w1 = (uint8_t*)ar.take(4 * n * n); q.w2 = (uint8_t*)ar.take(4 * n * n);
+        q.sqkv = (float*)ar.take(3 * n * 4); q.so = (float*)ar.take(n * 4);
+        q.s1 = (float*)ar.take(4 * n * 4); q.s2 = (float*)ar.take(n * 4);
+      }
+      e8x = (uint8_t*)ar.take(WE * 1500 * 4 * n);
+      e8s = (float*)ar.take(WE * 1500 * 4);
+      if (!e8s) return fail(-3, "encoder_format: 8-bit arena overflow");
+    }
+    if (fmt == WH_ENC_FP8_E4M3 && finalized && !e8_quantised) TRY(quantise_enc8());
+    enc_fmt = fmt;
+    return 0;
+  }
+  // the tile kernel of each of the block's four GEMMs for an encode of n_win windows (native:
+  // launch_gemm_tiles' rule for M > 128 rows)
+  std::string encoder_kernels(int n_win) const override {
+    const int n = ns, M = std::min(std::max(n_win, 1), std::min(Wcap, enc_chunk())) * 1500;
+    const bool e8 = enc_fmt == WH_ENC_FP8_E4M3;
+    auto name = [&](int N, int K) -> std::string {
+      if (e8) return gemm8_tile(M, N, K) == 256 ? "k_gemm8<256x128>" : "k_gemm8<128x64>";
+      const bool t256 = sizeof(T) == 2 && N % 256 == 0 && K % 128 == 0 && ((M + 255) / 256) * (N / 256) >= 256;
+      return t256 ? "k_gemm_256" : "k_gemm_tile";
+    };
+    return std::string("encoder=") + (e8 ? "fp8" : "native") + ",qkv=" + name(3 * n, n) + ",out=" + name(n, n) +
+           ",fc1=" + name(4 * n, n) + ",fc2=" + name(n, 4 * n);
+  }
+  int fp8_linear(int M, int N, int K, const float* x, const float* w, const float* bias, int gelu, int tile, float* y,
+                 uint8_t* xc, float* xs, uint8_t* wc, float* ws) override {
+    if (sizeof(T) != 2) return fail(-12, "fp8_linear: needs an fp16 context (this one is fp32)");
+    if (M < 1 || N < 1 || K < 1 || !x || !w || !y || !xc || !xs || !wc || !ws) return fail(-12, "fp8_linear: bad arguments");
+    if (K % G8_BK || K > 8192)
+      return fail(-12, "fp8_linear: K=" + std::to_string(K) + " is not a multiple of the K-tile (128) up to 8192");
+    if (tile != 0 && tile != 256 && tile != 128) return fail(-12, "fp8_linear: tile " + std::to_string(tile) + ": 0, 256 or 128");
+    const int tl = tile ? tile : (N % 64 ? 256 : gemm8_tile(M, N, K)), cols = tl == 256 ? 128 : 64;
+    if (N % cols)
+      return fail(-12, "fp8_linear: N=" + std::to_string(N) + " is not a multiple of the tile's " + std::to_string(cols) + " columns");
+    struct Dev {
+      void* p = nullptr;
+      ~Dev() { if (p) (void)hipFree(p); }
+    } dev;
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t mk = (size_t)M * K, nk = (size_t)N * K, mn = (size_t)M * N;
+    const size_t bytes = al(mk * 2) + al(nk * 2) + al(mk) + al(nk) + al((size_t)M * 4) + 2 * al((size_t)N * 4) + al(mn * 2);
+    HIPCHK(hipMalloc(&dev.p, bytes));
+    Arena ar;
+    ar.base = (char*)dev.p;
+    ar.cap = bytes;
+    half_t* dx = (half_t*)ar.take(mk * 2); half_t* dw = (half_t*)ar.take(nk * 2);
+    uint8_t* dxc = (uint8_t*)ar.take(mk); uint8_t* dwc = (uint8_t*)ar.take(nk);
+    float* dxs = (float*)ar.take((size_t)M * 4); float* dws = (float*)ar.take((size_t)N * 4);
+    float* db = (float*)ar.take((size_t)N * 4); half_t* dy = (half_t*)ar.take(mn * 2);
+    if (!dy) return fail(-3, "fp8_linear: arena overflow");
+    std::vector<half_t> h(std::max(mk, std::max(nk, mn)));
+    for (size_t i = 0; i < mk; ++i) h[i] = (half_t)x[i];
+    HIPCHK(hipMemcpy(dx, h.data(), mk * 2, hipMemcpyHostToDevice));
+    for (size_t i = 0; i < nk; ++i) h[i] = (half_t)w[i];
+    HIPCHK(hipMemcpy(dw, h.data(), nk * 2, hipMemcpyHostToDevice));
+    if (bias) HIPCHK(hipMemcpy(db, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+    launch_quant_rows(dx, dxc, dxs, M, K, st);
+    launch_quant_weights(dw, dwc, dws, N, K, st);
+    GemmArgs a;
+    a.X = dxc; a.ldx = K; a.W = dwc; a.bias = bias ? db : nullptr; a.M = M; a.N = N; a.K = K;
+    a.x_group_rows = M; a.out = dy; a.ldo = N;
+    const int rc = launch_gemm8(a, dxs, dws, gelu ? EPI_STORE_GELU : EPI_STORE, tl, st);
+    if (rc) return fail(-20, "fp8_linear: gemm8 launch failed code " + std::to_string(rc));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(launch_status(__func__));
+    HIPCHK(hipMemcpy(h.data(), dy, mn * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < mn; ++i) y[i] = (float)h[i];
+    HIPCHK(hipMemcpy(xc, dxc, mk, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(wc, dwc, nk, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(xs, dxs, (size_t)M * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ws, dws, (size_t)N * 4, hipMemcpyDeviceToHost));
     return 0;
   }
 
@@ -536,8 +667,38 @@ struct Ctx : public wh_ctx {
     kz_on(g);
     TRY(gemm(h1, 2 * n, conv2_w, conv2_b, we * 1500, n, 3 * n, EPI_GELU_POS, g));
     const int M = we * 1500;
+    // WH_ENC_FP8_E4M3: the four GEMMs read codes + row scales (e8x, e8s: one input at a time,
+    // the stream orders its writer behind the GEMM before it) and the layer's 8-bit weights
+    const bool e8 = enc_fmt == WH_ENC_FP8_E4M3;
+    auto gemm8 = [&](const uint8_t* Wc, const float* sw, const float* bias, int N, int K, int epi, GemmArgs a) -> int {
+      a.X = e8x; a.ldx = K; a.W = Wc; a.bias = bias; a.M = M; a.N = N; a.K = K;
+      if (a.x_group_rows == (1 << 30)) a.x_group_rows = M;
+      const int rc = launch_gemm8(a, e8s, sw, epi, 0, st);
+      if (rc) return fail(-20, "gemm8 launch failed code " + std::to_string(rc) + " M=" + std::to_string(M) +
+                                   " N=" + std::to_string(N) + " K=" + std::to_string(K));
+      return 0;
+    };
     for (int l = 0; l < La; ++l) {
       auto& e = enc[l];
+      if (e8) {
+        const auto& q = enc8[l];
+        launch_layernorm_quant(x_e, e8x, e8s, e.ln1_g, e.ln1_b, M, n, 1e-7f, st);
+        g = GemmArgs(); g.out = qkv_e; g.ldo = 3 * n;
+        g.x_group_rows = 1500; g.out_group_stride = (int64_t)1500 * 3 * n;
+        g.hs_state = n; g.hs_heads = nh; g.hs_T = TKP; g.vc = vt_e;
+        TRY(gemm8(q.wqkv, q.sqkv, e.bqkv, 3 * n, n, EPI_QKV_ENC, g));
+        launch_attn_enc<T>(qkv_e, 3 * n, n, nh, 1500, we, (int64_t)1500 * 3 * n, vt_e, TKP, att_e, (int64_t)1500 * n, st);
+        launch_quant_rows(att_e, e8x, e8s, M, n, st);
+        g = GemmArgs(); g.out_f32 = x_e; g.ldo = n;
+        TRY(gemm8(q.wo, q.so, e.bo, n, n, EPI_RESID, g));
+        launch_layernorm_quant(x_e, e8x, e8s, e.ln2_g, e.ln2_b, M, n, 1e-7f, st);
+        g = GemmArgs(); g.out = hm_e; g.ldo = 4 * n;
+        TRY(gemm8(q.w1, q.s1, e.b1, 4 * n, n, EPI_STORE_GELU, g));
+        launch_quant_rows(hm_e, e8x, e8s, M, 4 * n, st);
+        g = GemmArgs(); g.out_f32 = x_e; g.ldo = n;
+        TRY(gemm8(q.w2, q.s2, e.b2, n, 4 * n, EPI_RESID, g));
+        continue;
+      }
       launch_layernorm<T>(x_e, xn_e, e.ln1_g, e.ln1_b, M, n, 1e-7f, nullptr, st);
       // q, k -> qkv_e; v -> vt_e as per-(window, head) V^T with permuted keys
       g = GemmArgs(); g.out = qkv_e; g.ldo = 3 * n;
@@ -1606,6 +1767,19 @@ int wh_encode(wh_ctx* ctx, int n_win, const int64_t* seeks, const int* segs) { C
 int wh_read_audio_features(wh_ctx* ctx, int slot, float* out) { CTXCALL(ctx->read_xa(slot, out)); }
 int wh_read_cross_kv(wh_ctx* ctx, int slot, int layer, float* k, float* v) { CTXCALL(ctx->read_ckv(slot, layer, k, v)); }
 int wh_set_cross_kv_format(wh_ctx* ctx, int fmt) { CTXCALL(ctx->set_ckv_format(fmt)); }
+int wh_set_encoder_format(wh_ctx* ctx, int fmt) { CTXCALL(ctx->set_enc_format(fmt)); }
+int wh_encoder_kernels(wh_ctx* ctx, int n_win, char* buf, int cap) {
+  if (!ctx || !buf || cap < 1) return fail(-1, "bad arguments");
+  const std::string d = ctx->encoder_kernels(n_win);
+  const int n = std::min<int>((int)d.size(), cap - 1);
+  memcpy(buf, d.data(), n);
+  buf[n] = 0;
+  return n;
+}
+int wh_fp8_linear(wh_ctx* ctx, int M, int N, int K, const float* x, const float* w, const float* bias, int gelu,
+                  int tile, float* y, uint8_t* x_codes, float* x_scales, uint8_t* w_codes, float* w_scales) {
+  CTXCALL(ctx->fp8_linear(M, N, K, x, w, bias, gelu, tile, y, x_codes, x_scales, w_codes, w_scales));
+}
 int wh_read_cross_kv8(wh_ctx* ctx, int slot, int layer, uint8_t* k_codes, float* k_scales, uint8_t* v_codes,
                       float* v_scales) {
   if (!k_codes || !k_scales || !v_codes || !v_scales) return fail(-1, "null argument");

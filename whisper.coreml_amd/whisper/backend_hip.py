@@ -24,6 +24,8 @@ WH_F32 = 0
 WH_F16 = 1
 WH_CKV_NATIVE = 0
 WH_CKV_FP8_E4M3 = 1
+WH_ENC_NATIVE = 0
+WH_ENC_FP8_E4M3 = 1
 WH_PCM_S16, WH_PCM_S32, WH_PCM_F32 = 0, 1, 2
 
 
@@ -107,6 +109,10 @@ _EXPORTS = {
     "wh_read_cross_kv": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "wh_set_cross_kv_format": (c_int, [c_void_p, c_int]),
     "wh_read_cross_kv8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wh_set_encoder_format": (c_int, [c_void_p, c_int]),
+    "wh_encoder_kernels": (c_int, [c_void_p, c_int, ctypes.c_char_p, c_int]),
+    "wh_fp8_linear": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p]),
     "wh_decode_begin": (c_int, [c_void_p, c_int, POINTER(WhDecodeOpts), c_void_p, c_void_p, c_int, c_void_p]),
     "wh_decode_begin_slots": (c_int, [c_void_p, c_int, c_void_p, POINTER(WhDecodeOpts), c_void_p, c_void_p, c_int,
                                       c_void_p]),
@@ -310,10 +316,19 @@ class HipContext:
     """One libwhisper_hip context = one model on one GPU (per process)."""
 
     def __init__(self, dims: dict, device: int = 0, dtype: str = "fp16", max_windows: int = 8, max_group: int = 5,
-                 cross_kv: Optional[str] = None):
+                 cross_kv: Optional[str] = None, encoder: Optional[str] = None):
         """cross_kv: None (the compute type) or "fp8": the decoder step's cross-attention reads
         an 8-bit (E4M3) copy of the cross-KV (wh_set_cross_kv_format).  With None, the
-        environment variable WHISPER_HIP_CROSS_KV=fp8 selects it for fp16 contexts."""
+        environment variable WHISPER_HIP_CROSS_KV=fp8 selects it for fp16 contexts.
+        encoder: None / "native" or "fp8": the four GEMMs of every encoder block run on the 8-bit
+        (E4M3) matrix path (wh_set_encoder_format); with None, WHISPER_HIP_ENCODER=fp8 selects it
+        for fp16 contexts.  Off by default; accuracy on real speech is unmeasured."""
+        if encoder is None:
+            encoder = "fp8" if dtype == "fp16" and os.environ.get("WHISPER_HIP_ENCODER", "") == "fp8" else "native"
+        if encoder not in ("native", "fp8"):
+            raise ValueError(f"encoder={encoder!r}: 'native' or 'fp8'")
+        if encoder == "fp8" and dtype != "fp16":
+            raise ValueError(f"encoder='fp8' needs dtype='fp16', not dtype={dtype!r}: the 8-bit GEMMs replace fp16 ones")
         if cross_kv is None and dtype == "fp16" and os.environ.get("WHISPER_HIP_CROSS_KV", "") == "fp8":
             cross_kv = "fp8"
         if cross_kv not in (None, "fp8"):
@@ -339,6 +354,9 @@ class HipContext:
         self.cross_kv_format = cross_kv
         if cross_kv == "fp8":
             self.set_cross_kv_format(WH_CKV_FP8_E4M3)
+        self.encoder_format = "native"
+        if encoder == "fp8":
+            self.set_encoder_format(WH_ENC_FP8_E4M3)
         self.phrase_bias = None  # what set_phrase_bias installed: (phrases, boosts, start)
 
     # -- errors
@@ -790,6 +808,35 @@ class HipContext:
     def set_cross_kv_format(self, fmt: int):
         """wh_set_cross_kv_format: WH_CKV_NATIVE or WH_CKV_FP8_E4M3, before the first encode."""
         self._check(self.lib.wh_set_cross_kv_format(self.h, int(fmt)), "wh_set_cross_kv_format")
+
+    def set_encoder_format(self, fmt: int):
+        """wh_set_encoder_format: WH_ENC_NATIVE or WH_ENC_FP8_E4M3, at any time between encodes."""
+        self._check(self.lib.wh_set_encoder_format(self.h, int(fmt)), "wh_set_encoder_format")
+        self.encoder_format = "fp8" if int(fmt) == WH_ENC_FP8_E4M3 else "native"
+
+    def encoder_kernels(self, n_win: int) -> dict:
+        """The GEMM kernels an encode of n_win windows runs (wh_encoder_kernels):
+        {"encoder", "qkv", "out", "fc1", "fc2"}."""
+        buf = ctypes.create_string_buffer(256)
+        n = self.lib.wh_encoder_kernels(self.h, n_win, buf, 256)
+        self._check(0 if n >= 0 else n, "wh_encoder_kernels")
+        return dict(kv.split("=", 1) for kv in re.split(r",(?=\w+=)", buf.value.decode()))
+
+    def fp8_linear(self, x: np.ndarray, w: np.ndarray, bias: Optional[np.ndarray] = None, gelu: bool = False,
+                   tile: int = 0):
+        """wh_fp8_linear: x [M][K] w[N][K]^T (+ bias, GELU) through the encoder's 8-bit path.
+        Returns (y [M][N] fp32, x_codes, x_scales, w_codes, w_scales)."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(w, np.float32)
+        (M, K), N = x.shape, w.shape[0]
+        assert w.shape == (N, K)
+        b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+        y = np.empty((M, N), np.float32)
+        xc, xs = np.empty((M, K), np.uint8), np.empty(M, np.float32)
+        wc, ws = np.empty((N, K), np.uint8), np.empty(N, np.float32)
+        self._check(self.lib.wh_fp8_linear(self.h, M, N, K, _ptr(x), _ptr(w), None if b is None else _ptr(b), int(gelu),
+                                           int(tile), _ptr(y), _ptr(xc), _ptr(xs), _ptr(wc), _ptr(ws)), "wh_fp8_linear")
+        return y, xc, xs, wc, ws
 
     def cross_kv8(self, slot: int, layer: int):
         """The 8-bit copy of one slot and layer: (k_codes, k_scales, v_codes, v_scales), codes
