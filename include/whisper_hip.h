@@ -101,7 +101,13 @@ int wh_destroy(wh_ctx* ctx);
 
 /* checkpoint-format float32 tensor by reference state_dict name; the decoder query
    pre-scale (decoder.py:16-20) and the encoder key scale (encoder.py:38) are
-   folded here. */
+   folded here.  A successful load, also of a tensor loaded before, leaves the context
+   unfinalized: what wh_finalize derives from the weights (the fragment-ordered W_q, the
+   encoder's 8-bit weights) would be stale, so every call that needs finalized weights
+   returns -9 "weights not finalized" until the next wh_finalize, which builds them again
+   (the 8-bit weights when the encoder format asks for them, then or later).  Refused with
+   -9 on a context whose weights are shared with another (wh_tune_share_weights, tuning
+   builds), on either side of the sharing. */
 int wh_load_tensor(wh_ctx* ctx, const char* name, const float* data, const int64_t* shape, int ndim);
 int wh_finalize(wh_ctx* ctx);
 

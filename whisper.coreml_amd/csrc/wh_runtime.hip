@@ -22,6 +22,7 @@
 #include "wh_gemm8.h"
 #include "wh_host.h"
 #include "wh_kernels.h"
+#include "wh_layout.h"
 #include "wh_loop.h"
 
 using namespace wh;
@@ -30,7 +31,6 @@ static thread_local std::string g_release_error;  // a failed release in the las
 
 namespace {
 
-constexpr int NSPLIT = 8;         // cross-attention key splits (1500 / 8 = 188 keys)
 // encoder windows per pass (WHISPER_HIP_ENC_CHUNK overrides; activations scale with it)
 static int enc_chunk() {
   static const int v = [] {
@@ -40,44 +40,6 @@ static int enc_chunk() {
   }();
   return v;
 }
-constexpr int PRE_ROWS = 1024;    // min prefill rows per pass (the context sizes it to ~240 per window)
-constexpr int MROWS = 3008;       // melT rows per window (1 pad + 3000 + slack for padded conv1 K)
-constexpr int H1ROWS = 3002;      // conv1 output rows per window (zero rows 0 and 3001)
-constexpr int KC = 9;
-// 128 x 64 tiles of a single window's n-wide encoder GEMMs (1500 rows: 12 row tiles)
-constexpr int EKZ_TILES(int n) { return 12 * (n / 64); }
-constexpr int RSPLIT = 16;      // max split-K slabs of the residual projections (decode rows <= 128)
-
-struct Arena {
-  char* base = nullptr;
-  size_t cap = 0, off = 0;
-  void* take(size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    void* p = base + off;
-    off += bytes;
-    return off <= cap ? p : nullptr;
-  }
-};
-
-template <typename T>
-struct EncLayer {
-  float *ln1_g, *ln1_b, *bqkv, *bo, *ln2_g, *ln2_b, *b1, *b2;
-  T *wqkv, *wo, *w1, *w2;
-};
-// the 8-bit copy of an encoder layer's four weights: codes [out][in], one scale per out
-struct Enc8Layer {
-  uint8_t *wqkv, *wo, *w1, *w2;
-  float *sqkv, *so, *s1, *s2;
-};
-template <typename T>
-struct DecLayer {
-  float *ln1_g, *ln1_b, *bqkv, *bo, *lnx_g, *lnx_b, *bqx, *box, *ln2_g, *ln2_b, *b1, *b2;
-  T *wqkv, *wo, *wqx, *wox, *w1, *w2;
-  // W_q in the in-kernel query projection's fragment order (xq_project: each wave's
-  // 16 B-per-lane loads are 1 KB contiguous), fp16 contexts whose shape xattn_fused_q serves
-  T* wqx_f = nullptr;
-};
-
 }  // namespace
 
 struct wh_ctx : DecodeLoop {
@@ -118,14 +80,13 @@ namespace {
 
 template <typename T>
 struct Ctx : public wh_ctx {
+  using elem = T;
   wh_dims d;
   int ns, La, K1p;
-  Arena wa;  // weights
-  Arena aa;  // activations / state
-  void* wbase = nullptr;
-  void* abase = nullptr;
+  LayoutDims ld;            // what the two layouts and the tensor shapes are sized by
+  void* wbase = nullptr;    // weights (layout_weights)
+  void* abase = nullptr;    // activations / state (layout_buffers)
   std::set<std::string> loaded;
-  size_t expected = 0;
 
   // weights
   T *conv1_w, *conv2_w, *E, *Pdec, *ckv_w;
@@ -164,7 +125,6 @@ struct Ctx : public wh_ctx {
   int *row_tok, *row_pos, *row_win, *row_slot, *win_row0, *win_nrows, *win_slot, *rows_in;
   int *st_row_win, *st_row_slot, *st_win_row0, *st_win_nrows, *st_win_slot;
   int* fp_anc = nullptr;
-  static constexpr int P1_SLABS = 2048;  // k_proj1 split-K slabs: zs x 16-column tiles <= 16 x 80 at n = 1280
   float* p1_slab = nullptr;  // k_proj1 in-launch split-K slabs [zs][N/16][256]
   int* p1_cnt = nullptr;     // and arrival counters [4n/16] (zero between launches)
   // single-window encoder: the residual GEMMs' K halves (k_gemm_tile KZ = 2) meet through
@@ -226,6 +186,22 @@ struct Ctx : public wh_ctx {
     if (!rel.first.empty()) g_release_error = rel.first;
   }
 
+  // every weight, and every activation / state buffer, named once (csrc/wh_layout.h)
+  void layout_weights(Arena& ar) { wh::layout_weights(*this, ar, ld); }
+  void layout_buffers(Arena& ar) { wh::layout_buffers(*this, ar, ld); }
+  // One device allocation for what `layout` takes: a run on a measuring arena gives the
+  // size, the allocation is that plus ARENA_TAIL_PAD, a second run carves it
+  template <class F>
+  int carve(void** base, Arena& ar, F layout, const char* what) {
+    Arena m;
+    layout(m);
+    HIPCHK(hipMalloc(base, m.off + ARENA_TAIL_PAD));
+    ar = Arena(*base, m.off + ARENA_TAIL_PAD);
+    layout(ar);
+    if (!ar.ok() || ar.off != m.off) return fail(-3, std::string(what) + " arena overflow");
+    return 0;
+  }
+
   int init(int device_, const wh_dims& dims, int Wcap_, int Gcap_) {
     device = device_;
     d = dims;
@@ -250,261 +226,87 @@ struct Ctx : public wh_ctx {
     TRY(tm.create());
     HIPCHK(hipHostMalloc((void**)&h_done, sizeof(int) * 2 * Wcap));  // two poll buffers
     for (auto& e : poll_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    // ---------------- weights
-    const size_t n = ns;
-    size_t wb = 0;
-    auto add = [&](size_t elems, size_t esz) { wb += ((elems * esz + 255) & ~size_t(255)) + 256; };
-    add(n * K1p, sizeof(T)); add(n, 4); add(n * 3 * n, sizeof(T)); add(n, 4); add(1500 * n, 4);
-    for (int l = 0; l < La; ++l) {
-      add(n, 4); add(n, 4); add(3 * n * n, sizeof(T)); add(3 * n, 4); add(n * n, sizeof(T)); add(n, 4);
-      add(n, 4); add(n, 4); add(4 * n * n, sizeof(T)); add(4 * n, 4); add(4 * n * n, sizeof(T)); add(n, 4);
-    }
-    add(n, 4); add(n, 4);
-    add((size_t)V * n, sizeof(T)); add(CTX * n, sizeof(T));
-    for (int l = 0; l < Ld; ++l) {
-      add(n, 4); add(n, 4); add(3 * n * n, sizeof(T)); add(3 * n, 4); add(n * n, sizeof(T)); add(n, 4);
-      add(n, 4); add(n, 4); add(n * n, sizeof(T)); add(n, 4); add(n * n, sizeof(T)); add(n, 4);
-      add(n, 4); add(n, 4); add(4 * n * n, sizeof(T)); add(4 * n, 4); add(4 * n * n, sizeof(T)); add(n, 4);
-    }
-    add(n, 4); add(n, 4);
-    add(2 * Ld * n * n, sizeof(T)); add(2 * Ld * n, 4);
-    const bool wq_frag = xattn_fused_q(n, 1, (int)sizeof(T));
-    if (wq_frag)
-      for (int l = 0; l < Ld; ++l) add(n * n, sizeof(T));
-    HIPCHK(hipMalloc(&wbase, wb));
-    HIPCHK(hipMemset(wbase, 0, wb));
-    wa.base = (char*)wbase;
-    wa.cap = wb;
-    auto tk = [&](size_t elems) { return (T*)wa.take(elems * sizeof(T)); };
-    auto fk = [&](size_t elems) { return (float*)wa.take(elems * 4); };
-    conv1_w = tk(n * K1p); conv1_b = fk(n); conv2_w = tk(n * 3 * n); conv2_b = fk(n); pos_enc = fk(1500 * n);
-    enc.resize(La);
-    for (auto& e : enc) {
-      e.ln1_g = fk(n); e.ln1_b = fk(n); e.wqkv = tk(3 * n * n); e.bqkv = fk(3 * n); e.wo = tk(n * n); e.bo = fk(n);
-      e.ln2_g = fk(n); e.ln2_b = fk(n); e.w1 = tk(4 * n * n); e.b1 = fk(4 * n); e.w2 = tk(4 * n * n); e.b2 = fk(n);
-    }
-    lnp_g = fk(n); lnp_b = fk(n);
-    E = tk((size_t)V * n); Pdec = tk(CTX * n);
-    dec.resize(Ld);
-    for (auto& e : dec) {
-      e.ln1_g = fk(n); e.ln1_b = fk(n); e.wqkv = tk(3 * n * n); e.bqkv = fk(3 * n); e.wo = tk(n * n); e.bo = fk(n);
-      e.lnx_g = fk(n); e.lnx_b = fk(n); e.wqx = tk(n * n); e.bqx = fk(n); e.wox = tk(n * n); e.box = fk(n);
-      e.ln2_g = fk(n); e.ln2_b = fk(n); e.w1 = tk(4 * n * n); e.b1 = fk(4 * n); e.w2 = tk(4 * n * n); e.b2 = fk(n);
-    }
-    ln_g = fk(n); ln_b = fk(n);
-    ckv_w = tk(2 * Ld * n * n); ckv_b = fk(2 * Ld * n);
-    if (wq_frag)
-      for (auto& e : dec) e.wqx_f = tk(n * n);
-    if (!ckv_b || (wq_frag && !dec.back().wqx_f)) return fail(-3, "weight arena overflow");
-    expected = 5 + La * 15 + 2 + 2 + Ld * 24 + 2;
-    // ---------------- activations
-    const int WE = std::min(Wcap, enc_chunk());
+    // the self-attention kernels address one layer's self-K / V cache with 32-bit byte
+    // offsets (buffer loads, wh_kernels.hip k_self_attn / k_self_attn_qkv)
+    if ((int64_t)Wcap * Gcap * CTX * ns * (int64_t)sizeof(T) >= ((int64_t)1 << 31) - 4096)
+      return fail(-3, "self-KV cache of one layer exceeds 2 GiB: lower max_windows or max_group");
     // first-pass rows per pass: every window's word-timestamp alignment (<= ~230 tokens)
     // fits one pass, so its GEMMs run at M in the thousands
     PRE = std::max(PRE_ROWS, std::min(Wcap * 240, 8192));
     RD = std::max(Wcap * Gcap, PRE);
-    const int LR = std::max(Wcap * Gcap, 2 * Wcap);
-    size_t ab = 0;
-    auto addA = [&](size_t bytes) { ab += ((bytes + 255) & ~size_t(255)) + 256; };
-    addA((size_t)WE * MROWS * n_mels * sizeof(T)); addA((size_t)WE * H1ROWS * n * sizeof(T));
-    addA((size_t)WE * 1500 * n * 4); addA((size_t)WE * 1500 * n * sizeof(T)); addA((size_t)WE * 1500 * 3 * n * sizeof(T));
-    addA((size_t)WE * 1500 * n * sizeof(T)); addA((size_t)WE * 1500 * 4 * n * sizeof(T));
-    addA(((size_t)WE * nh * 64 * TKP + 64) * sizeof(T));  // encoder V^T (padding keys stay zero)
-    addA((size_t)Wcap * 1500 * n * sizeof(T));
-    addA((size_t)2 * Ld * Wcap * TKP * n * sizeof(T) + 65536);  // + slack: last key tile reads past TKP
-    // the self-attention kernels address one layer's self-K / V cache with 32-bit byte
-    // offsets (buffer loads, wh_kernels.hip k_self_attn / k_self_attn_qkv)
-    if ((int64_t)Wcap * Gcap * CTX * n * (int64_t)sizeof(T) >= ((int64_t)1 << 31) - 4096)
-      return fail(-3, "self-KV cache of one layer exceeds 2 GiB: lower max_windows or max_group");
-    for (int l = 0; l < Ld; ++l) { addA((size_t)Wcap * Gcap * CTX * n * sizeof(T)); addA((size_t)Wcap * Gcap * CTX * n * sizeof(T)); }
-    addA((size_t)RD * n * 4); addA((size_t)RD * n * sizeof(T)); addA((size_t)RD * n * sizeof(T)); addA((size_t)RD * n * sizeof(T));
-    addA((size_t)RD * 4 * n * sizeof(T));
-    addA((size_t)RD * nh * NSPLIT * 64 * 4); addA((size_t)RD * nh * NSPLIT * 4); addA((size_t)RD * nh * NSPLIT * 4);
-    addA((size_t)LR * V * 4); addA((size_t)2 * Wcap * V * 4); addA(Wcap * 4); addA((size_t)RSPLIT * RD * n * 4);
-    for (int i = 0; i < 9; ++i) addA(RD * 4);
-    for (int i = 0; i < 5; ++i) addA(RD * 4);
-    addA(Ld * nh * 4);
-    addA(((V + 31) / 32) * 4);
-    addA(Wcap * 8); addA(Wcap * 4);
-    // state
-    addA((size_t)Wcap * Gcap * HCTX * 4); addA((size_t)Wcap * Gcap * CTX * 4);
-    addA((size_t)Wcap * CTX * 4);  // fp_anc
-    for (int i = 0; i < 5; ++i) addA(Wcap * 4);
-    addA(Wcap * Gcap * 4);
-    addA(Wcap * 16 * 4); addA(Wcap * 16 * 4); addA((size_t)Wcap * 16 * HCTX * 4);
-    addA((size_t)Wcap * Gcap * KC * 4); addA((size_t)Wcap * Gcap * KC * 4);
-    addA((size_t)Wcap * Gcap * LP_SLICES * LP_REC * 4); addA((size_t)Wcap * Gcap * 4);
-    addA((size_t)Wcap * 4);  // window arrival counters of the merging selection
-    addA(64);
-    addA(64);
-    addA((size_t)P1_SLABS * 256 * 4); addA((size_t)(4 * n / 16) * 4);  // k_proj1 split-K slabs + counters
-    addA((size_t)Wcap * nh * XS_NSP * XREC * 4); addA((size_t)Wcap * nh * 4);  // cross-attention segment records
-    addA((size_t)8 * n * 4);  // k_proj1 path (<= 8 rows, wh_proj.h P1_RMAX): the second residual buffer
-    addA((size_t)EKZ_TILES(n) * 65536); addA((size_t)EKZ_TILES(n) * 4 * 4);  // single-window encoder K halves
-    addA((size_t)BIAS_MAX_ENTRIES * sizeof(BiasRec));  // the phrase table, at its capacity
-    HIPCHK(hipMalloc(&abase, ab));
-    HIPCHK(hipMemset(abase, 0, ab));
-    aa.base = (char*)abase;
-    aa.cap = ab;
-    auto ta = [&](size_t elems) { return (T*)aa.take(elems * sizeof(T)); };
-    auto fa = [&](size_t elems) { return (float*)aa.take(elems * 4); };
-    auto ia = [&](size_t elems) { return (int*)aa.take(elems * 4); };
-    melT = ta((size_t)WE * MROWS * n_mels); h1 = ta((size_t)WE * H1ROWS * n);
-    x_e = fa((size_t)WE * 1500 * n); xn_e = ta((size_t)WE * 1500 * n); qkv_e = ta((size_t)WE * 1500 * 3 * n);
-    att_e = ta((size_t)WE * 1500 * n); hm_e = ta((size_t)WE * 1500 * 4 * n);
-    vt_e = ta((size_t)WE * nh * 64 * TKP + 64);  // + the last key tile's read past TKP
-    xa = ta((size_t)Wcap * 1500 * n);
-    ckv = ta((size_t)2 * Ld * Wcap * TKP * n + 32768 / sizeof(T));
-    kc.resize(Ld); vc.resize(Ld);
-    for (int l = 0; l < Ld; ++l) { kc[l] = ta((size_t)Wcap * Gcap * CTX * n); vc[l] = ta((size_t)Wcap * Gcap * CTX * n); }
-    x_d = fa((size_t)RD * n); xn_d = ta((size_t)RD * n); q_d = ta((size_t)RD * n); att_d = ta((size_t)RD * n);
-    hm_d = ta((size_t)RD * 4 * n);
-    po = fa((size_t)RD * nh * NSPLIT * 64); pm = fa((size_t)RD * nh * NSPLIT); pl = fa((size_t)RD * nh * NSPLIT);
-    logits = fa((size_t)LR * V); logits2 = fa((size_t)2 * Wcap * V); nsp = fa(Wcap); part = fa((size_t)RSPLIT * RD * n);
-    row_tok = ia(RD); row_pos = ia(RD); row_win = ia(RD); row_slot = ia(RD); win_row0 = ia(RD); win_nrows = ia(RD);
-    win_slot = ia(RD); rows_in = ia(RD); src_rows = ia(RD);
-    st_row_win = ia(RD); st_row_slot = ia(RD); st_win_row0 = ia(RD); st_win_nrows = ia(RD); st_win_slot = ia(RD);
-    qk_map = ia(Ld * nh);
-    suppress = (unsigned*)ia((V + 31) / 32);
-    d_seeks = (int64_t*)aa.take(Wcap * 8); d_segs = ia(Wcap);
-    S.hist = ia((size_t)Wcap * Gcap * HCTX); S.anc = ia((size_t)Wcap * Gcap * CTX);
-    fp_anc = ia((size_t)Wcap * CTX);  // first passes' ancestry: all zero (beam slot 0), never written
-    S.len = ia(Wcap); S.sample_begin = ia(Wcap); S.step = ia(Wcap); S.done = ia(Wcap); S.fin_n = ia(Wcap);
-    S.sum_lp = fa(Wcap * Gcap);
-    S.fin_score = fa(Wcap * 16); S.fin_len = ia(Wcap * 16); S.fin_tok = ia((size_t)Wcap * 16 * HCTX);
-    S.cand_val = fa((size_t)Wcap * Gcap * KC); S.cand_idx = ia((size_t)Wcap * Gcap * KC);
-    S.lpart = fa((size_t)Wcap * Gcap * LP_SLICES * LP_REC); S.lp_cnt = ia((size_t)Wcap * Gcap);  // zeroed with the arena
-    S.lpw_cnt = ia((size_t)Wcap);
-    S.seed = (unsigned long long*)aa.take(64);
-    p1_slab = fa((size_t)P1_SLABS * 256); p1_cnt = ia(4 * n / 16);  // zeroed with the arena
-    xs_rec = fa((size_t)Wcap * nh * XS_NSP * XREC); xs_cnt = ia((size_t)Wcap * nh);
-    x2_d = fa((size_t)8 * n);
-    ekz_slab = fa((size_t)EKZ_TILES(n) * 16384); ekz_cnt = ia((size_t)EKZ_TILES(n) * 4);  // zeroed with the arena
-    bias_dev = (BiasRec*)aa.take((size_t)BIAS_MAX_ENTRIES * sizeof(BiasRec));
-    if (!bias_dev || !fp_anc || !S.seed || !S.cand_idx || !S.lp_cnt || !S.lpw_cnt || !p1_cnt || !xs_cnt || !x2_d || !ekz_cnt)
-      return fail(-3, "activation arena overflow");
+    ld = LayoutDims{(size_t)ns, (size_t)n_mels, (size_t)K1p, (size_t)La, (size_t)Ld, (size_t)V, (size_t)nh,
+                    (size_t)Wcap, (size_t)Gcap, (size_t)std::min(Wcap, enc_chunk()), (size_t)RD,
+                    (size_t)std::max(Wcap * Gcap, 2 * Wcap), xattn_fused_q(ns, 1, (int)sizeof(T)),
+                    TKP, CTX, HCTX, LP_SLICES * LP_REC, XS_NSP * XREC, BIAS_MAX_ENTRIES};
+    // both arenas start zeroed: the arrival counters and the padding keys depend on it
+    Arena wa, aa;
+    TRY(carve(&wbase, wa, [&](Arena& ar) { layout_weights(ar); }, "weight"));
+    HIPCHK(hipMemset(wbase, 0, wa.cap));
+    TRY(carve(&abase, aa, [&](Arena& ar) { layout_buffers(ar); }, "activation"));
+    HIPCHK(hipMemset(abase, 0, aa.cap));
     S.nw = Wcap; S.G = 1; S.ctx = CTX; S.hctx = HCTX; S.maxc = 16;
     return audio.init(st, stats);
   }
 
   // ------------------------------------------------------------ weights
-  int up(void* dst, const std::vector<T>& h) {
-    HIPCHK(hipMemcpy(dst, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+  // (U)(src * scale), the product in fp32 (times 1 is the value itself)
+  template <typename U>
+  int upload(U* dst, const float* src, size_t cnt, float scale = 1.f) {
+    std::vector<U> t(cnt);
+    for (size_t i = 0; i < cnt; ++i) t[i] = (U)(src[i] * scale);
+    HIPCHK(hipMemcpy(dst, t.data(), cnt * sizeof(U), hipMemcpyHostToDevice));
     return 0;
   }
-  int upf(float* dst, const float* src, size_t cnt, float scale = 1.f) {
-    if (scale == 1.f) {
-      HIPCHK(hipMemcpy(dst, src, cnt * 4, hipMemcpyHostToDevice));
-      return 0;
+  // a convolution weight [n][cin][3] -> tap-major rows [o][j * cin + c] of ld >= 3 * cin elements
+  int upload_conv(T* dst, const float* w, size_t cin, size_t ld) {
+    std::vector<float> t(ns * ld, 0.f);
+    for (size_t o = 0; o < (size_t)ns; ++o)
+      for (size_t c = 0; c < cin; ++c)
+        for (int j = 0; j < 3; ++j) t[o * ld + j * cin + c] = w[(o * cin + c) * 3 + j];
+    return upload(dst, t.data(), t.size());
+  }
+  // tab's row `key` into obj (-1: no such row): the one shape check, then the upload
+  template <class O, class L>
+  int load_row(O& obj, const std::vector<Tensor<L, T>>& tab, const char* key, bool dec_layer, const std::string& name,
+               const float* data, const int64_t* shape, int ndim) {
+    for (const auto& r : tab) {
+      if (strcmp(r.name, key)) continue;
+      if ((int)strlen(r.shape) != ndim) return fail(-4, name + ": bad rank");
+      size_t cnt = 1;
+      for (int i = 0; i < ndim; ++i) {
+        if (shape[i] != dim_size(r.shape[i], ld)) return fail(-4, name + ": bad shape");
+        cnt *= shape[i];
+      }
+      if (!r.wt) return upload(obj.*(r.wf) + r.slot * cnt, data, cnt, r.scale[dec_layer]);
+      T* dst = obj.*(r.wt) + r.slot * cnt;
+      if (dst == conv1_w) return upload_conv(dst, data, n_mels, K1p);
+      if (dst == conv2_w) return upload_conv(dst, data, ns, 3 * (size_t)ns);
+      return upload(dst, data, cnt, r.scale[dec_layer]);
     }
-    std::vector<float> t(src, src + cnt);
-    for (auto& v : t) v *= scale;
-    HIPCHK(hipMemcpy(dst, t.data(), cnt * 4, hipMemcpyHostToDevice));
-    return 0;
-  }
-  int upT(T* dst, const float* src, size_t cnt, float scale = 1.f) {
-    std::vector<T> t(cnt);
-    for (size_t i = 0; i < cnt; ++i) t[i] = (T)(src[i] * scale);
-    return up(dst, t);
+    return -1;
   }
 
   int load(const std::string& name, const float* data, const int64_t* shape, int ndim) override {
-    auto need = [&](std::initializer_list<int64_t> want) -> int {
-      if ((int)want.size() != ndim) return fail(-4, name + ": bad rank");
-      int i = 0;
-      for (auto w : want)
-        if (shape[i++] != w) return fail(-4, name + ": bad shape");
-      return 0;
-    };
-    const size_t n = ns;
-    const float kscale = 0.125f;  // (64)^-0.5: encoder key (encoder.py:38), decoder query (decoder.py:20)
-    int rc = 0;
-    if (name == "encoder.conv1.weight") {
-      TRY(need({(int64_t)n, n_mels, 3}));
-      std::vector<float> t(n * K1p, 0.f);  // [o][j*n_mels + c] = w[o][c][j]
-      for (size_t o = 0; o < n; ++o)
-        for (int c = 0; c < n_mels; ++c)
-          for (int j = 0; j < 3; ++j) t[o * K1p + j * n_mels + c] = data[(o * n_mels + c) * 3 + j];
-      rc = upT(conv1_w, t.data(), t.size());
-    } else if (name == "encoder.conv1.bias") { TRY(need({(int64_t)n})); rc = upf(conv1_b, data, n); }
-    else if (name == "encoder.conv2.weight") {
-      TRY(need({(int64_t)n, (int64_t)n, 3}));
-      std::vector<float> t(n * 3 * n);
-      for (size_t o = 0; o < n; ++o)
-        for (size_t c = 0; c < n; ++c)
-          for (int j = 0; j < 3; ++j) t[o * 3 * n + j * n + c] = data[(o * n + c) * 3 + j];
-      rc = upT(conv2_w, t.data(), t.size());
-    } else if (name == "encoder.conv2.bias") { TRY(need({(int64_t)n})); rc = upf(conv2_b, data, n); }
-    else if (name == "encoder.positional_embedding") { TRY(need({1500, (int64_t)n})); rc = upf(pos_enc, data, 1500 * n); }
-    else if (name == "encoder.ln_post.weight") { TRY(need({(int64_t)n})); rc = upf(lnp_g, data, n); }
-    else if (name == "encoder.ln_post.bias") { TRY(need({(int64_t)n})); rc = upf(lnp_b, data, n); }
-    else if (name == "decoder.token_embedding.weight") { TRY(need({V, (int64_t)n})); rc = upT(E, data, (size_t)V * n); }
-    else if (name == "decoder.positional_embedding") { TRY(need({CTX, (int64_t)n})); rc = upT(Pdec, data, CTX * n); }
-    else if (name == "decoder.ln.weight") { TRY(need({(int64_t)n})); rc = upf(ln_g, data, n); }
-    else if (name == "decoder.ln.bias") { TRY(need({(int64_t)n})); rc = upf(ln_b, data, n); }
-    else {
-      int l = -1;
-      char part[128];
-      const bool is_enc = sscanf(name.c_str(), "encoder.blocks.%d.%127s", &l, part) == 2;
-      const bool is_dec = !is_enc && sscanf(name.c_str(), "decoder.blocks.%d.%127s", &l, part) == 2;
-      if (!is_enc && !is_dec) return fail(-5, "unknown tensor " + name);
-      const std::string p(part);
-      if (is_enc) {
-        if (l < 0 || l >= La) return fail(-5, "layer out of range " + name);
-        auto& e = enc[l];
-        if (p == "attn.query.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(e.wqkv, data, n * n); }
-        else if (p == "attn.query.bias") { TRY(need({(int64_t)n})); rc = upf(e.bqkv, data, n); }
-        else if (p == "attn.key.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(e.wqkv + n * n, data, n * n, kscale); }
-        else if (p == "attn.value.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(e.wqkv + 2 * n * n, data, n * n); }
-        else if (p == "attn.value.bias") { TRY(need({(int64_t)n})); rc = upf(e.bqkv + 2 * n, data, n); }
-        else if (p == "attn.out.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(e.wo, data, n * n); }
-        else if (p == "attn.out.bias") { TRY(need({(int64_t)n})); rc = upf(e.bo, data, n); }
-        else if (p == "attn_ln.weight") { TRY(need({(int64_t)n})); rc = upf(e.ln1_g, data, n); }
-        else if (p == "attn_ln.bias") { TRY(need({(int64_t)n})); rc = upf(e.ln1_b, data, n); }
-        else if (p == "mlp_ln.weight") { TRY(need({(int64_t)n})); rc = upf(e.ln2_g, data, n); }
-        else if (p == "mlp_ln.bias") { TRY(need({(int64_t)n})); rc = upf(e.ln2_b, data, n); }
-        else if (p == "mlp.0.weight") { TRY(need({4 * (int64_t)n, (int64_t)n})); rc = upT(e.w1, data, 4 * n * n); }
-        else if (p == "mlp.0.bias") { TRY(need({4 * (int64_t)n})); rc = upf(e.b1, data, 4 * n); }
-        else if (p == "mlp.2.weight") { TRY(need({(int64_t)n, 4 * (int64_t)n})); rc = upT(e.w2, data, 4 * n * n); }
-        else if (p == "mlp.2.bias") { TRY(need({(int64_t)n})); rc = upf(e.b2, data, n); }
-        else return fail(-5, "unknown tensor " + name);
-      } else {
-        if (l < 0 || l >= Ld) return fail(-5, "layer out of range " + name);
-        auto& e = dec[l];
-        T* ck = ckv_w + (size_t)(2 * l) * n * n;
-        if (p == "attn.query.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(e.wqkv, data, n * n, kscale); }
-        else if (p == "attn.query.bias") { TRY(need({(int64_t)n})); rc = upf(e.bqkv, data, n, kscale); }
-        else if (p == "attn.key.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(e.wqkv + n * n, data, n * n); }
-        else if (p == "attn.value.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(e.wqkv + 2 * n * n, data, n * n); }
-        else if (p == "attn.value.bias") { TRY(need({(int64_t)n})); rc = upf(e.bqkv + 2 * n, data, n); }
-        else if (p == "attn.out.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(e.wo, data, n * n); }
-        else if (p == "attn.out.bias") { TRY(need({(int64_t)n})); rc = upf(e.bo, data, n); }
-        else if (p == "attn_ln.weight") { TRY(need({(int64_t)n})); rc = upf(e.ln1_g, data, n); }
-        else if (p == "attn_ln.bias") { TRY(need({(int64_t)n})); rc = upf(e.ln1_b, data, n); }
-        else if (p == "cross_attn.query.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(e.wqx, data, n * n, kscale); }
-        else if (p == "cross_attn.query.bias") { TRY(need({(int64_t)n})); rc = upf(e.bqx, data, n, kscale); }
-        else if (p == "cross_attn.key.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(ck, data, n * n); }
-        else if (p == "cross_attn.value.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(ck + n * n, data, n * n); }
-        else if (p == "cross_attn.value.bias") { TRY(need({(int64_t)n})); rc = upf(ckv_b + (2 * l + 1) * n, data, n); }
-        else if (p == "cross_attn.out.weight") { TRY(need({(int64_t)n, (int64_t)n})); rc = upT(e.wox, data, n * n); }
-        else if (p == "cross_attn.out.bias") { TRY(need({(int64_t)n})); rc = upf(e.box, data, n); }
-        else if (p == "cross_attn_ln.weight") { TRY(need({(int64_t)n})); rc = upf(e.lnx_g, data, n); }
-        else if (p == "cross_attn_ln.bias") { TRY(need({(int64_t)n})); rc = upf(e.lnx_b, data, n); }
-        else if (p == "mlp_ln.weight") { TRY(need({(int64_t)n})); rc = upf(e.ln2_g, data, n); }
-        else if (p == "mlp_ln.bias") { TRY(need({(int64_t)n})); rc = upf(e.ln2_b, data, n); }
-        else if (p == "mlp.0.weight") { TRY(need({4 * (int64_t)n, (int64_t)n})); rc = upT(e.w1, data, 4 * n * n); }
-        else if (p == "mlp.0.bias") { TRY(need({4 * (int64_t)n})); rc = upf(e.b1, data, 4 * n); }
-        else if (p == "mlp.2.weight") { TRY(need({(int64_t)n, 4 * (int64_t)n})); rc = upT(e.w2, data, 4 * n * n); }
-        else if (p == "mlp.2.bias") { TRY(need({(int64_t)n})); rc = upf(e.b2, data, n); }
-        else return fail(-5, "unknown tensor " + name);
-      }
-    }
-    if (rc) return rc;
+    if (sharers > 0 || shares_from) return fail(-9, "load " + name + ": this context's weights are shared with another");
+    int l = -1, rc;
+    char part[128];
+    const bool is_enc = sscanf(name.c_str(), "encoder.blocks.%d.%127s", &l, part) == 2;
+    const bool is_dec = !is_enc && sscanf(name.c_str(), "decoder.blocks.%d.%127s", &l, part) == 2;
+    if ((is_enc || is_dec) && (l < 0 || l >= (is_enc ? La : Ld))) return fail(-5, "layer out of range " + name);
+    if (is_enc) rc = load_row(enc[l], block_tensors<T>(), part, false, name, data, shape, ndim);
+    else if (!is_dec) rc = load_row(*this, top_tensors<Ctx<T>>(), name.c_str(), false, name, data, shape, ndim);
+    else if ((rc = load_row(dec[l], block_tensors<T>(), part, true, name, data, shape, ndim)) == -1)
+      rc = load_row(dec[l], cross_tensors<T>(), part, true, name, data, shape, ndim);
+    if (rc) return rc == -1 ? fail(-5, "unknown tensor " + name) : rc;
     loaded.insert(name);
+    // what finalize() derives from the weights (wqx_f, the 8-bit encoder weights) is stale now
+    finalized = false;
+    e8_quantised = false;
     return 0;
   }
 
   int finalize() override {
+    const size_t expected = n_loadable<Ctx<T>>(La, Ld);
     if (loaded.size() != expected)
       return fail(-6, "loaded " + std::to_string(loaded.size()) + " of " + std::to_string(expected) + " tensors");
     // the fragment-ordered W_q copies (after the 0.125 query scale was folded in at load)
@@ -534,32 +336,30 @@ struct Ctx : public wh_ctx {
     e8_quantised = true;
     return 0;
   }
+  // the 8-bit weights of every layer, then the codes + row scales of one GEMM input
+  void layout_enc8(Arena& ar) {
+    const size_t n = ns;
+    enc8.resize(La);
+    for (auto& q : enc8) {
+      q.wqkv = ar.take<uint8_t>(3 * n * n); q.wo = ar.take<uint8_t>(n * n);
+      q.w1 = ar.take<uint8_t>(4 * n * n); q.w2 = ar.take<uint8_t>(4 * n * n);
+      q.sqkv = ar.take<float>(3 * n); q.so = ar.take<float>(n);
+      q.s1 = ar.take<float>(4 * n); q.s2 = ar.take<float>(n);
+    }
+    e8x = ar.take<uint8_t>(ld.WE * 1500 * 4 * n);
+    e8s = ar.take<float>(ld.WE * 1500);
+  }
   int set_enc_format(int fmt) override {
     if (fmt != WH_ENC_NATIVE && fmt != WH_ENC_FP8_E4M3)
       return fail(-12, "encoder_format: unknown format " + std::to_string(fmt));
     if (fmt == WH_ENC_FP8_E4M3 && sizeof(T) != 2)
       return fail(-12, "encoder_format: WH_ENC_FP8_E4M3 needs an fp16 context (this one is fp32)");
     if (fmt == WH_ENC_FP8_E4M3 && !e8_base) {
-      const size_t n = ns, WE = std::min(Wcap, enc_chunk());
-      auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-      const size_t per_layer = al(3 * n * n) + al(n * n) + 2 * al(4 * n * n) + al(3 * n * 4) + 2 * al(n * 4) + al(4 * n * 4);
-      const size_t bytes = La * per_layer + al(WE * 1500 * 4 * n) + al(WE * 1500 * 4);
-      void* p = nullptr;
-      HIPCHK(hipMalloc(&p, bytes));
-      e8_base = (char*)p;
       Arena ar;
-      ar.base = e8_base;
-      ar.cap = bytes;
-      enc8.resize(La);
-      for (auto& q : enc8) {
-        q.wqkv = (uint8_t*)ar.take(3 * n * n); q.wo = (uint8_t*)ar.take(n * n);
-        q.w1 = (uint8_t*)ar.take(4 * n * n); q.w2 = (uint8_t*)ar.take(4 * n * n);
-        q.sqkv = (float*)ar.take(3 * n * 4); q.so = (float*)ar.take(n * 4);
-        q.s1 = (float*)ar.take(4 * n * 4); q.s2 = (float*)ar.take(n * 4);
-      }
-      e8x = (uint8_t*)ar.take(WE * 1500 * 4 * n);
-      e8s = (float*)ar.take(WE * 1500 * 4);
-      if (!e8s) return fail(-3, "encoder_format: 8-bit arena overflow");
+      void* p = nullptr;
+      const int rc = carve(&p, ar, [&](Arena& a) { layout_enc8(a); }, "encoder_format: 8-bit");
+      e8_base = (char*)p;
+      if (rc) return rc;
     }
     if (fmt == WH_ENC_FP8_E4M3 && finalized && !e8_quantised) TRY(quantise_enc8());
     enc_fmt = fmt;
@@ -592,18 +392,17 @@ struct Ctx : public wh_ctx {
       void* p = nullptr;
       ~Dev() { if (p) (void)hipFree(p); }
     } dev;
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t mk = (size_t)M * K, nk = (size_t)N * K, mn = (size_t)M * N;
-    const size_t bytes = al(mk * 2) + al(nk * 2) + al(mk) + al(nk) + al((size_t)M * 4) + 2 * al((size_t)N * 4) + al(mn * 2);
-    HIPCHK(hipMalloc(&dev.p, bytes));
+    half_t *dx, *dw, *dy;
+    uint8_t *dxc, *dwc;
+    float *dxs, *dws, *db;
     Arena ar;
-    ar.base = (char*)dev.p;
-    ar.cap = bytes;
-    half_t* dx = (half_t*)ar.take(mk * 2); half_t* dw = (half_t*)ar.take(nk * 2);
-    uint8_t* dxc = (uint8_t*)ar.take(mk); uint8_t* dwc = (uint8_t*)ar.take(nk);
-    float* dxs = (float*)ar.take((size_t)M * 4); float* dws = (float*)ar.take((size_t)N * 4);
-    float* db = (float*)ar.take((size_t)N * 4); half_t* dy = (half_t*)ar.take(mn * 2);
-    if (!dy) return fail(-3, "fp8_linear: arena overflow");
+    TRY(carve(&dev.p, ar, [&](Arena& a) {
+      dx = a.take<half_t>(mk); dw = a.take<half_t>(nk);
+      dxc = a.take<uint8_t>(mk); dwc = a.take<uint8_t>(nk);
+      dxs = a.take<float>(M); dws = a.take<float>(N);
+      db = a.take<float>(N); dy = a.take<half_t>(mn);
+    }, "fp8_linear:"));
     std::vector<half_t> h(std::max(mk, std::max(nk, mn)));
     for (size_t i = 0; i < mk; ++i) h[i] = (half_t)x[i];
     HIPCHK(hipMemcpy(dx, h.data(), mk * 2, hipMemcpyHostToDevice));
