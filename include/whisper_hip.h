@@ -103,9 +103,9 @@ int wh_destroy(wh_ctx* ctx);
    pre-scale (decoder.py:16-20) and the encoder key scale (encoder.py:38) are
    folded here.  A successful load, also of a tensor loaded before, leaves the context
    unfinalized: what wh_finalize derives from the weights (the fragment-ordered W_q, the
-   encoder's 8-bit weights) would be stale, so every call that needs finalized weights
-   returns -9 "weights not finalized" until the next wh_finalize, which builds them again
-   (the 8-bit weights when the encoder format asks for them, then or later).  Refused with
+   encoder's and the decoder's 8-bit weights) would be stale, so every call that needs finalized
+   weights returns -9 "weights not finalized" until the next wh_finalize, which builds them again
+   (the 8-bit weights when the encoder / decoder format asks for them, then or later).  Refused with
    -9 on a context whose weights are shared with another (wh_tune_share_weights, tuning
    builds), on either side of the sharing. */
 int wh_load_tensor(wh_ctx* ctx, const char* name, const float* data, const int64_t* shape, int ndim);
@@ -325,6 +325,41 @@ int wh_set_encoder_format(wh_ctx* ctx, int fmt);
 int wh_encoder_kernels(wh_ctx* ctx, int n_win, char* buf, int cap);
 int wh_fp8_linear(wh_ctx* ctx, int M, int N, int K, const float* x, const float* w, const float* bias, int gelu,
                   int tile, float* y, uint8_t* x_codes, float* x_scales, uint8_t* w_codes, float* w_scales);
+
+/* Decoder formats.  The single-window decoder step (one window's beams, up to 8 rows: the
+   per-token latency path of streaming, prompt carry-over and temperature retries) reads every
+   decoder weight once per token.  WH_DEC_FP8_E4M3 gives it 8-bit copies of the six linear
+   weights of every decoder layer to read instead (about half the bytes): weight-only, the
+   activations stay fp16, accumulation fp32, the matrix instruction the fp16 one.  The fp16
+   weights stay: the first pass, wh_prefill_logits, wh_align*, wh_score_batch, every step of two
+   or more windows (or of more than 8 rows) and the vocabulary projection read them and do not
+   change.  Memory grows by about half the decoder layers' weights, allocated when the format
+   is first chosen.  Off by default; the default path runs the same kernels, launches and
+   buffers as before.  Per output channel (row of the [out][in] matrix; w: the fp16 weight):
+     amax  = max |w| over the row
+     scale = amax / 448                              (fp32)
+     code  = e4m3(clamp(w / scale, -448, 448))       (OCP E4M3, round to nearest even)
+   amax == 0 gives scale 0 and codes 0; the NaN codes 0x7F / 0xFF are never written.  The step
+   computes y[m][n] = scale[n] * sum_k x[m][k] code[n][k] in fp32 (a code is an fp16 value
+   exactly), then the fp16 path's bias, residual, GELU or QKV epilogue.  The copies are made at
+   wh_finalize, or when the format is set on a finalized context, and again by the wh_finalize
+   after any wh_load_tensor.  Accuracy on real speech is unmeasured.
+   wh_set_decoder_format: at any time; a change serves the batches begun after it
+   (wh_decode_begin*, wh_prefill), a batch in flight keeps the format it began with, and
+   wh_step_kernels describes a batch begun now: proj=k_proj1<w8> for the steps the copies
+   serve.  Refused with wh_last_error set and the context unchanged:
+   WH_DEC_FP8_E4M3 on an fp32 context, an unknown format, an n_text_state the single-window
+   step kernel does not serve (it serves 1280, 1024, 768, 512, 384, 128).  Setting the format
+   the context already has always succeeds.  wh_version() does not change: a caller detects
+   the feature by the symbols.
+   wh_read_decoder_w8: the codes [N][K] in logical order (un-permuted on the host) and the
+   scales [N] of one layer's weight; which: 0 qkv [3n][n], 1 attention out [n][n], 2 cross
+   query [n][n], 3 cross out [n][n], 4 fc1 [4n][n], 5 fc2 [n][4n] (the decoder's query rows
+   carry the 64^-0.5 folded in at load).  Refused by name: a WH_DEC_NATIVE context, an
+   unfinalized one, a layer or which out of range. */
+enum { WH_DEC_NATIVE = 0, WH_DEC_FP8_E4M3 = 1 };
+int wh_set_decoder_format(wh_ctx* ctx, int fmt);
+int wh_read_decoder_w8(wh_ctx* ctx, int layer, int which, uint8_t* codes, float* scales);
 
 /* decode n_win windows (slots 0..n_win-1): prefill of the initial tokens
    (init_tokens[w*max_init + i], i < n_init[w]) and the first token update */

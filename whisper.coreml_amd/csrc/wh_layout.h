@@ -76,6 +76,15 @@ struct DecLayer : EncLayer<T> {
   T* wqx_f = nullptr;
 };
 
+// the 8-bit copy of a decoder layer's six linear weights (wh_set_decoder_format), indexed as
+// wh_read_decoder_w8's `which`: 0 qkv, 1 o, 2 xq, 3 xo, 4 fc1, 5 fc2.  Codes [out][in] in
+// k_proj1<w8>'s fragment order (wh_proj8.h), one scale per out
+struct Dec8Layer {
+  uint8_t* w[6];
+  float* s[6];
+};
+constexpr size_t DEC8_OUT[6] = {3, 1, 1, 1, 4, 1}, DEC8_IN[6] = {1, 1, 1, 1, 1, 4};  // rows, columns in units of n
+
 // the sizes the layouts and the tensor shapes depend on
 struct LayoutDims {
   size_t n, n_mels, K1p, La, Ld, V, nh;  // the model's (K1p: conv1's K, 3 * n_mels padded to 128 B)
@@ -115,6 +124,18 @@ void layout_weights(C& c, Arena& ar, const LayoutDims& d) {
   }
   if (d.wq_frag)
     for (auto& e : c.dec) e.wqx_f = tk(n * n);
+}
+
+// the decoder's 8-bit weight copies: an arena of their own, allocated when the format first
+// asks for them (the default context allocates what it did before)
+template <class C>
+void layout_dec8(C& c, Arena& ar, const LayoutDims& d) {
+  c.dec8.resize(d.Ld);
+  for (auto& q : c.dec8)
+    for (int i = 0; i < 6; ++i) {
+      q.w[i] = ar.take<uint8_t>(DEC8_OUT[i] * d.n * DEC8_IN[i] * d.n);
+      q.s[i] = ar.take<float>(DEC8_OUT[i] * d.n);
+    }
 }
 
 // activations and decode state

@@ -24,6 +24,7 @@
 #include "wh_kernels.h"
 #include "wh_layout.h"
 #include "wh_loop.h"
+#include "wh_proj8.h"
 
 using namespace wh;
 
@@ -53,6 +54,8 @@ struct wh_ctx : DecodeLoop {
   virtual int set_ckv_format(int fmt) = 0;
   virtual int read_ckv8(int slot, int layer, uint8_t* kc, float* ks, uint8_t* vc, float* vs) = 0;
   virtual int set_enc_format(int fmt) = 0;
+  virtual int set_dec_format(int fmt) = 0;
+  virtual int read_dec_w8(int layer, int which, uint8_t* codes, float* scales) = 0;
   virtual std::string encoder_kernels(int n_win) const = 0;
   virtual int fp8_linear(int M, int N, int K, const float* x, const float* w, const float* bias, int gelu, int tile,
                          float* y, uint8_t* xc, float* xs, uint8_t* wc, float* ws) = 0;
@@ -112,6 +115,13 @@ struct Ctx : public wh_ctx {
   uint8_t* e8x = nullptr;
   float* e8s = nullptr;
   bool e8_quantised = false;
+  // decoder format (wh_set_decoder_format).  The 8-bit copies of the six linear weights of
+  // every layer (wh_layout.h layout_dec8) are allocated when WH_DEC_FP8_E4M3 is first chosen
+  // and kept until the context is destroyed; w8_step: the format the current batch began with
+  int dec_fmt = WH_DEC_NATIVE;
+  char* d8_base = nullptr;
+  std::vector<Dec8Layer> dec8;
+  bool d8_quantised = false, w8_step = false;
   const void* kv8_layer(int l) const { return ckv8 ? ckv8 + (size_t)l * Wcap * ckv8_slot_bytes(nh) : nullptr; }
   float* x_e;
   int64_t* d_seeks;
@@ -161,6 +171,9 @@ struct Ctx : public wh_ctx {
     if (shares_from) --shares_from->sharers;
     shares_from = src;
     ++src->sharers;  // src's weight arena must outlive this context (wh_destroy checks)
+    // this context's 8-bit decoder copies are of the weights it reads now
+    d8_quantised = false;
+    if (dec_fmt == WH_DEC_FP8_E4M3 || w8_step) TRY(quantise_dec8());
     return 0;
   }
 
@@ -176,6 +189,7 @@ struct Ctx : public wh_ctx {
     if (abase) rel(hipFree(abase), "hipFree(activations)");
     if (ckv8) rel(hipFree(ckv8), "hipFree(cross-KV 8-bit copy)");
     if (e8_base) rel(hipFree(e8_base), "hipFree(encoder 8-bit copy)");
+    if (d8_base) rel(hipFree(d8_base), "hipFree(decoder 8-bit copy)");
     audio.release(rel);
     scratch.release(rel, "hipFree(scratch)");
     if (h_done) rel(hipHostFree(h_done), "hipHostFree(done flags)");
@@ -299,9 +313,10 @@ struct Ctx : public wh_ctx {
       rc = load_row(dec[l], cross_tensors<T>(), part, true, name, data, shape, ndim);
     if (rc) return rc == -1 ? fail(-5, "unknown tensor " + name) : rc;
     loaded.insert(name);
-    // what finalize() derives from the weights (wqx_f, the 8-bit encoder weights) is stale now
+    // what finalize() derives from the weights (wqx_f, the 8-bit encoder and decoder weights) is stale now
     finalized = false;
     e8_quantised = false;
+    d8_quantised = false;
     return 0;
   }
 
@@ -317,8 +332,70 @@ struct Ctx : public wh_ctx {
     HIPCHK(hipDeviceSynchronize());
     finalized = true;
     if (enc_fmt == WH_ENC_FP8_E4M3) TRY(quantise_enc8());
+    // (w8_step: a batch begun in fp8 still reads the copies after the format was set back)
+    if (dec_fmt == WH_DEC_FP8_E4M3 || w8_step) TRY(quantise_dec8());
     return 0;
   }
+
+  // ------------------------------------------------------------ decoder format
+  const T* dec_weight(int l, int which) const {
+    const auto& e = dec[l];
+    const T* w[6] = {e.wqkv, e.wo, e.wqx, e.wox, e.w1, e.w2};
+    return w[which];
+  }
+  int quantise_dec8() {
+    for (int l = 0; l < Ld; ++l)
+      for (int i = 0; i < 6; ++i)
+        if (launch_quant_dec_w8(dec_weight(l, i), dec8[l].w[i], dec8[l].s[i], (int)DEC8_OUT[i] * ns, (int)DEC8_IN[i] * ns,
+                                p1_nstep(ns), st))
+          return fail(-20, "decoder_format: k_quant_dec_w8 does not serve n_text_state " + std::to_string(ns));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(launch_status(__func__));
+    d8_quantised = true;
+    return 0;
+  }
+  int set_dec_format(int fmt) override {
+    if (fmt != WH_DEC_NATIVE && fmt != WH_DEC_FP8_E4M3)
+      return fail(-12, "decoder_format: unknown format " + std::to_string(fmt));
+    if (fmt == dec_fmt) return 0;
+    if (fmt == WH_DEC_FP8_E4M3) {
+      if (sizeof(T) != 2) return fail(-12, "decoder_format: WH_DEC_FP8_E4M3 needs an fp16 context (this one is fp32)");
+      if (!proj1_supported(1, ns))
+        return fail(-12, "decoder_format: WH_DEC_FP8_E4M3 serves n_text_state 1280, 1024, 768, 512, 384 and 128 (the "
+                         "single-window step kernel's widths), not " + std::to_string(ns));
+      if (!d8_base) {
+        Arena ar;
+        void* p = nullptr;
+        const int rc = carve(&p, ar, [&](Arena& a) { layout_dec8(*this, a, ld); }, "decoder_format: 8-bit");
+        d8_base = (char*)p;
+        if (rc) return rc;
+      }
+      if (finalized && !d8_quantised) TRY(quantise_dec8());
+    }
+    // (the captured step graph holds the kernels of w8_step, the format of the batch in flight:
+    // begin_batch drops it where the next batch begins in the other format)
+    dec_fmt = fmt;
+    return 0;
+  }
+  int read_dec_w8(int layer, int which, uint8_t* codes, float* scales) override {
+    if (dec_fmt != WH_DEC_FP8_E4M3) return fail(-12, "read_decoder_w8: the context's decoder format is WH_DEC_NATIVE");
+    if (!finalized) return fail(-9, "read_decoder_w8: weights not finalized");
+    if (layer < 0 || layer >= Ld || which < 0 || which > 5) return fail(-12, "read_decoder_w8: bad layer or which");
+    const int N = (int)DEC8_OUT[which] * ns, K = (int)DEC8_IN[which] * ns, nst = p1_nstep(ns);
+    std::vector<uint8_t> h((size_t)N * K);
+    HIPCHK(hipMemcpy(h.data(), dec8[layer].w[which], h.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(scales, dec8[layer].s[which], (size_t)N * 4, hipMemcpyDeviceToHost));
+    for (int r = 0; r < N; ++r)
+      for (int k = 0; k < K; ++k) codes[(size_t)r * K + k] = h[(size_t)r * K + w8_offset(k, nst)];
+    return 0;
+  }
+  // the 8-bit operands of layer l's projection `which` where this batch's single-window step
+  // reads them; nulls: the fp16 weight
+  struct W8 {
+    const uint8_t* c = nullptr;
+    const float* s = nullptr;
+  };
+  W8 w8(int l, int which) const { return w8_step ? W8{dec8[l].w[which], dec8[l].s[which]} : W8{}; }
 
   // ------------------------------------------------------------ encoder format
   int quantise_enc8() {
@@ -793,14 +870,16 @@ struct Ctx : public wh_ctx {
     return on;
   }
 
-  int p1(GemmArgs& g, int epi, bool ln) {
+  // q: the weight's 8-bit copy (w8()), which then stands in for g.W
+  int p1(GemmArgs& g, int epi, bool ln, W8 q) {
     g.p1_slab = p1_slab;
     g.p1_cnt = p1_cnt;
     g.p1_slabs = P1_SLABS;
     // time_stage(7): each projection of an eager step timed by its own dispatch events
     const bool tev = proj_ev_n < (int)proj_ev.size() / 2;
-    const int rc = tev ? launch_proj1<T>(g, epi, ln, st, proj_ev[2 * proj_ev_n], proj_ev[2 * proj_ev_n + 1])
-                       : launch_proj1<T>(g, epi, ln, st);
+    hipEvent_t e0 = tev ? proj_ev[2 * proj_ev_n] : nullptr, e1 = tev ? proj_ev[2 * proj_ev_n + 1] : nullptr;
+    if (q.c) g.W = q.c;
+    const int rc = q.c ? launch_proj1_w8(g, q.s, epi, ln, st, e0, e1) : launch_proj1<T>(g, epi, ln, st, e0, e1);
     if (tev && rc == 0) ++proj_ev_n;
     return rc == 0 ? 0 : fail(-20, "k_proj1 launch failed code " + std::to_string(rc));
   }
@@ -817,7 +896,7 @@ struct Ctx : public wh_ctx {
       g.out = q_d; g.ldo = n; g.hs_state = n; g.hs_heads = nh;
       g.row_win = st_row_win; g.row_slot = st_row_slot; g.row_pos = row_pos; g.kc = kc[l]; g.vc = vc[l];
       g.kv_beams = Gcap; g.kv_ctx = CTX;
-      TRY(p1(g, EPI_QKV_DEC, true));
+      TRY(p1(g, EPI_QKV_DEC, true, w8(l, 0)));
       struct Q { const T* X; int K; const T* W; const float* b; int N; int epi; const float* lg; const float* lb; T* out; };
       const Q qs[5] = {{att_d, n, e.wo, e.bo, n, EPI_RESID, nullptr, nullptr, nullptr},
                        {nullptr, n, e.wqx, e.bqx, n, EPI_STORE, e.lnx_g, e.lnx_b, q_d},
@@ -832,7 +911,7 @@ struct Ctx : public wh_ctx {
         } else {
           g.X = q.X; g.ldx = q.K; g.out_f32 = x_d; g.ldo = n;
         }
-        TRY(p1(g, q.epi, q.lg != nullptr));
+        TRY(p1(g, q.epi, q.lg != nullptr, w8(l, 1 + (int)(&q - qs))));
       }
       return 0;
     }
@@ -858,7 +937,7 @@ struct Ctx : public wh_ctx {
     // the 8-bit copy serves the steps k_xattn_seg serves: up to 128 rows (dec_layers: skinny);
     // a larger step runs the first-pass kernel over the fp16 cross-KV, in either format
     const bool kv8 = ckv8 && n_win * group <= 128;
-    return std::string("proj=") + (p1 ? "k_proj1" : "k_proj") + ",xattn=k_xattn_seg" +
+    return std::string("proj=") + (p1 ? (dec_fmt == WH_DEC_FP8_E4M3 ? "k_proj1<w8>" : "k_proj1") : "k_proj") + ",xattn=k_xattn_seg" +
            (kv8 ? (qp ? "<kv8,qproj>" : "<kv8>") : qp ? "<qproj>" : "") + ",self_attn=" +
            (p1 ? (h ? "k_self_attn<kco>" : "k_self_attn") : h ? "k_self_attn_qkv<pipe+kco>" : "k_self_attn_qkv") +
            ",tail=vocab+k_logit_part";
@@ -881,11 +960,11 @@ struct Ctx : public wh_ctx {
     auto ln_done = [&]() {
       if (pend) { std::swap(xc, xo); pend = nullptr; }
     };
-    auto resid = [&](const T* X, int K, const T* W, const float* b, bool defer) -> int {
+    auto resid = [&](const T* X, int K, const T* W, W8 q, const float* b, bool defer) -> int {
       GemmArgs g;
       g.X = X; g.ldx = K; g.W = W; g.bias = b; g.M = R; g.N = n; g.K = K; g.out_f32 = xc; g.ldo = n;
       g.p1_defer = defer;
-      TRY(p1(g, EPI_RESID, false));
+      TRY(p1(g, EPI_RESID, false, q));
       if (defer) pend = b;
       return 0;
     };
@@ -897,32 +976,32 @@ struct Ctx : public wh_ctx {
       ln_in(g, e.ln1_g, e.ln1_b);
       g.out = q_d; g.ldo = n; g.hs_state = n; g.hs_heads = nh;
       g.row_win = rw; g.row_slot = rs; g.row_pos = rp; g.kc = kc[l]; g.vc = vc[l]; g.kv_beams = Gcap; g.kv_ctx = CTX;
-      TRY(p1(g, EPI_QKV_DEC, true));
+      TRY(p1(g, EPI_QKV_DEC, true, w8(l, 0)));
       ln_done();
       launch_self_attn<T>(q_d, n, kc[l], vc[l], rw, rs, rp, A, ancG, Gcap, nh, CTX, att_d, n, R, st);
-      TRY(resid(att_d, n, e.wo, e.bo, false));  // deferring it measured +1.0 us on cross-q, -0.2 here
+      TRY(resid(att_d, n, e.wo, w8(l, 1), e.bo, false));  // deferring it measured +1.0 us on cross-q, -0.2 here
       // cross-attention block
       XQPart xq = step_xq(ancG);
       g = GemmArgs();
       g.W = e.wqx; g.bias = e.bqx; g.M = R; g.N = n; g.K = n;
       ln_in(g, e.lnx_g, e.lnx_b);
       g.out = q_d; g.ldo = n;
-      TRY(p1(g, EPI_STORE, true));
+      TRY(p1(g, EPI_STORE, true, w8(l, 2)));
       ln_done();
       const T* ck = ckv + (size_t)(2 * l) * Wcap * TKP * n;
       const T* cv = ckv + (size_t)(2 * l + 1) * Wcap * TKP * n;
       launch_cross_attn<T>(q_d, n, ck, cv, 1500, nh, NSPLIT, nwin, wr0, wnr, wsl, (int64_t)TKP * n, po, pm, pl, att_d,
                            n, R, nullptr, nullptr, 0, st, xq, kv8_layer(l));
       // (not deferred: fc1's 16-wave LayerNorm prologue has no registers for two more row copies)
-      TRY(resid(att_d, n, e.wox, e.box, false));
+      TRY(resid(att_d, n, e.wox, w8(l, 3), e.box, false));
       // MLP; the last layer's fc2 reduces in-launch (the final LayerNorm reads x)
       g = GemmArgs();
       g.W = e.w1; g.bias = e.b1; g.M = R; g.N = 4 * n; g.K = n;
       ln_in(g, e.ln2_g, e.ln2_b);
       g.out = hm_d; g.ldo = 4 * n;
-      TRY(p1(g, EPI_STORE_GELU, true));
+      TRY(p1(g, EPI_STORE_GELU, true, w8(l, 4)));
       ln_done();
-      TRY(resid(hm_d, 4 * n, e.w2, e.b2, l + 1 < Ld));
+      TRY(resid(hm_d, 4 * n, e.w2, w8(l, 5), e.b2, l + 1 < Ld));
     }
     // the final LayerNorm runs in the vocabulary kernel's prologue (vocab(), final_x)
     final_x = xc;
@@ -1045,6 +1124,15 @@ struct Ctx : public wh_ctx {
     // the self-KV cache uses [w][Gcap][..] slots; the anc table uses [w][G][..]
     cur_nwin = n_win;
     cur_G = G;
+    // a format set during the last batch serves from this one on; the captured step graph
+    // holds the last batch's kernels and its key (wh_loop.hip ensure_graph) does not know
+    // the format, so it goes where the format flips
+    if (w8_step != (dec_fmt == WH_DEC_FP8_E4M3)) {
+      HIPCHK(hipStreamSynchronize(st));
+      if (gexec) { HIPCHK(hipGraphExecDestroy(gexec)); gexec = nullptr; }
+      if (graph) { HIPCHK(hipGraphDestroy(graph)); graph = nullptr; }
+      w8_step = !w8_step;
+    }
     h_len = nin;
     // the host vectors above must outlive the async copies
     HIPCHK(hipStreamSynchronize(st));
@@ -1567,6 +1655,11 @@ int wh_read_audio_features(wh_ctx* ctx, int slot, float* out) { CTXCALL(ctx->rea
 int wh_read_cross_kv(wh_ctx* ctx, int slot, int layer, float* k, float* v) { CTXCALL(ctx->read_ckv(slot, layer, k, v)); }
 int wh_set_cross_kv_format(wh_ctx* ctx, int fmt) { CTXCALL(ctx->set_ckv_format(fmt)); }
 int wh_set_encoder_format(wh_ctx* ctx, int fmt) { CTXCALL(ctx->set_enc_format(fmt)); }
+int wh_set_decoder_format(wh_ctx* ctx, int fmt) { CTXCALL(ctx->set_dec_format(fmt)); }
+int wh_read_decoder_w8(wh_ctx* ctx, int layer, int which, uint8_t* codes, float* scales) {
+  if (!codes || !scales) return fail(-1, "null argument");
+  CTXCALL(ctx->read_dec_w8(layer, which, codes, scales));
+}
 int wh_encoder_kernels(wh_ctx* ctx, int n_win, char* buf, int cap) {
   if (!ctx || !buf || cap < 1) return fail(-1, "bad arguments");
   const std::string d = ctx->encoder_kernels(n_win);

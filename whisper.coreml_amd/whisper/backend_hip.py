@@ -26,6 +26,8 @@ WH_CKV_NATIVE = 0
 WH_CKV_FP8_E4M3 = 1
 WH_ENC_NATIVE = 0
 WH_ENC_FP8_E4M3 = 1
+WH_DEC_NATIVE = 0
+WH_DEC_FP8_E4M3 = 1
 WH_PCM_S16, WH_PCM_S32, WH_PCM_F32 = 0, 1, 2
 
 
@@ -111,6 +113,8 @@ _EXPORTS = {
     "wh_read_cross_kv8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wh_set_encoder_format": (c_int, [c_void_p, c_int]),
     "wh_encoder_kernels": (c_int, [c_void_p, c_int, ctypes.c_char_p, c_int]),
+    "wh_set_decoder_format": (c_int, [c_void_p, c_int]),
+    "wh_read_decoder_w8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "wh_fp8_linear": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "wh_decode_begin": (c_int, [c_void_p, c_int, POINTER(WhDecodeOpts), c_void_p, c_void_p, c_int, c_void_p]),
@@ -316,13 +320,26 @@ class HipContext:
     """One libwhisper_hip context = one model on one GPU (per process)."""
 
     def __init__(self, dims: dict, device: int = 0, dtype: str = "fp16", max_windows: int = 8, max_group: int = 5,
-                 cross_kv: Optional[str] = None, encoder: Optional[str] = None):
+                 cross_kv: Optional[str] = None, encoder: Optional[str] = None, decoder: Optional[str] = None):
         """cross_kv: None (the compute type) or "fp8": the decoder step's cross-attention reads
         an 8-bit (E4M3) copy of the cross-KV (wh_set_cross_kv_format).  With None, the
         environment variable WHISPER_HIP_CROSS_KV=fp8 selects it for fp16 contexts.
         encoder: None / "native" or "fp8": the four GEMMs of every encoder block run on the 8-bit
         (E4M3) matrix path (wh_set_encoder_format); with None, WHISPER_HIP_ENCODER=fp8 selects it
-        for fp16 contexts.  Off by default; accuracy on real speech is unmeasured."""
+        for fp16 contexts.  Off by default; accuracy on real speech is unmeasured.
+        decoder: None / "native" or "fp8": the single-window decoder step (one window's beams)
+        reads 8-bit (E4M3) copies of the decoder layers' linear weights, one scale per output
+        channel (wh_set_decoder_format); with None, WHISPER_HIP_DECODER=fp8 selects it for the
+        contexts it can serve (fp16, a model width the single-window step kernel has) and leaves
+        the others native, where decoder="fp8" raises.  Off by default; accuracy on real speech is
+        unmeasured."""
+        decoder_from_env = decoder is None
+        if decoder is None:
+            decoder = "fp8" if dtype == "fp16" and os.environ.get("WHISPER_HIP_DECODER", "") == "fp8" else "native"
+        if decoder not in ("native", "fp8"):
+            raise ValueError(f"decoder={decoder!r}: 'native' or 'fp8'")
+        if decoder == "fp8" and dtype != "fp16":
+            raise ValueError(f"decoder='fp8' needs dtype='fp16', not dtype={dtype!r}: the 8-bit weights feed fp16 MFMAs")
         if encoder is None:
             encoder = "fp8" if dtype == "fp16" and os.environ.get("WHISPER_HIP_ENCODER", "") == "fp8" else "native"
         if encoder not in ("native", "fp8"):
@@ -357,6 +374,14 @@ class HipContext:
         self.encoder_format = "native"
         if encoder == "fp8":
             self.set_encoder_format(WH_ENC_FP8_E4M3)
+        self.decoder_format = "native"
+        if decoder == "fp8":
+            try:
+                self.set_decoder_format(WH_DEC_FP8_E4M3)
+            except HipBackendError:
+                if not decoder_from_env:  # (refused by name, context unchanged: the environment's default stays native)
+                    self.close()
+                    raise
         self.phrase_bias = None  # what set_phrase_bias installed: (phrases, boosts, start)
 
     # -- errors
@@ -813,6 +838,24 @@ class HipContext:
         """wh_set_encoder_format: WH_ENC_NATIVE or WH_ENC_FP8_E4M3, at any time between encodes."""
         self._check(self.lib.wh_set_encoder_format(self.h, int(fmt)), "wh_set_encoder_format")
         self.encoder_format = "fp8" if int(fmt) == WH_ENC_FP8_E4M3 else "native"
+
+    def set_decoder_format(self, fmt):
+        """wh_set_decoder_format: WH_DEC_NATIVE / "native" or WH_DEC_FP8_E4M3 / "fp8"; serves the
+        batches begun after it (decode_begin, prefill)."""
+        fmt = {"native": WH_DEC_NATIVE, "fp8": WH_DEC_FP8_E4M3}.get(fmt, fmt)
+        self._check(self.lib.wh_set_decoder_format(self.h, int(fmt)), "wh_set_decoder_format")
+        self.decoder_format = "fp8" if int(fmt) == WH_DEC_FP8_E4M3 else "native"
+
+    def decoder_w8(self, layer: int, which: int):
+        """The 8-bit copy of one decoder weight (wh_read_decoder_w8; which: 0 qkv, 1 out, 2 cross
+        query, 3 cross out, 4 fc1, 5 fc2): (codes uint8 E4M3 [N][K], scales fp32 [N]); value =
+        code * scale."""
+        n = self.dims["n_text_state"]
+        N, K = (3, 1, 1, 1, 4, 1)[which % 6] * n, (1, 1, 1, 1, 1, 4)[which % 6] * n
+        codes, scales = np.empty((N, K), dtype=np.uint8), np.empty(N, dtype=np.float32)
+        self._check(self.lib.wh_read_decoder_w8(self.h, int(layer), int(which), _ptr(codes), _ptr(scales)),
+                    "wh_read_decoder_w8")
+        return codes, scales
 
     def encoder_kernels(self, n_win: int) -> dict:
         """The GEMM kernels an encode of n_win windows runs (wh_encoder_kernels):
