@@ -103,9 +103,10 @@ int wh_destroy(wh_ctx* ctx);
    pre-scale (decoder.py:16-20) and the encoder key scale (encoder.py:38) are
    folded here.  A successful load, also of a tensor loaded before, leaves the context
    unfinalized: what wh_finalize derives from the weights (the fragment-ordered W_q, the
-   encoder's and the decoder's 8-bit weights) would be stale, so every call that needs finalized
-   weights returns -9 "weights not finalized" until the next wh_finalize, which builds them again
-   (the 8-bit weights when the encoder / decoder format asks for them, then or later).  Refused with
+   encoder's, the decoder's and the vocabulary's 8-bit weights) would be stale, so every call that
+   needs finalized weights returns -9 "weights not finalized" until the next wh_finalize, which builds
+   them again (the 8-bit weights when the encoder / decoder / vocabulary format asks for them, then
+   or later).  Refused with
    -9 on a context whose weights are shared with another (wh_tune_share_weights, tuning
    builds), on either side of the sharing. */
 int wh_load_tensor(wh_ctx* ctx, const char* name, const float* data, const int64_t* shape, int ndim);
@@ -361,6 +362,40 @@ enum { WH_DEC_NATIVE = 0, WH_DEC_FP8_E4M3 = 1 };
 int wh_set_decoder_format(wh_ctx* ctx, int fmt);
 int wh_read_decoder_w8(wh_ctx* ctx, int layer, int which, uint8_t* codes, float* scales);
 
+/* Vocabulary formats.  The vocabulary projection of the single-window decoder step (one
+   window's beams, up to 8 rows) streams the whole token embedding once per token: the one
+   launch of that step that is bound by memory bandwidth.  WH_VOCAB_FP8_E4M3 gives it an 8-bit
+   copy of the embedding to read instead (half the bytes): weight-only, the final LayerNorm's
+   output stays fp16, accumulation fp32, the matrix instruction the fp16 one.  The fp16
+   embedding stays: the token lookup, the first pass, wh_prefill_logits, wh_align*,
+   wh_score_batch and every step of two or more windows (or of more than 8 rows) read it and
+   do not change.  Memory grows by n_text_state + 4 bytes per vocabulary row (66.6 MB at n_vocab
+   51866, n_text_state 1280), allocated when the format is first chosen.  Off by default; the
+   default path runs the same kernels, launches and buffers as before.  The format is the
+   decoder weight rule above, per vocabulary row (w: the fp16 embedding row):
+     amax  = max |w| over the row
+     scale = amax / 448                              (fp32)
+     code  = e4m3(clamp(w / scale, -448, 448))       (OCP E4M3, round to nearest even)
+   amax == 0 gives scale 0 and codes 0; the NaN codes 0x7F / 0xFF are never written.  The step
+   computes logit[m][v] = scale[v] * sum_k LN(x[m])[k] code[v][k] in fp32 (a code is an fp16
+   value exactly; the k order per row is fixed).  The copy is made at wh_finalize, or when the
+   format is set on a finalized context, and again by the wh_finalize after any wh_load_tensor.
+   Accuracy on real speech is unmeasured.
+   wh_set_vocab_format: at any time; a change serves the batches begun after it
+   (wh_decode_begin*, wh_prefill), a batch in flight keeps the format it began with, and
+   wh_step_kernels describes a batch begun now: tail=vocab<w8>+k_logit_part for the steps the
+   copy serves.  It composes with the decoder and cross-KV formats in any combination.
+   Refused with wh_last_error set and the context unchanged: WH_VOCAB_FP8_E4M3 on an fp32
+   context, an unknown format, an n_text_state the single-window step does not serve (it serves
+   1280, 1024, 768, 512, 384, 128).  Setting the format the context already has always succeeds.
+   wh_version() does not change: a caller detects the feature by the symbols.
+   wh_read_vocab_w8: the codes [n_vocab][n_text_state] in logical order (the device keeps them
+   in the kernel's tile order; un-permuted on the host) and the scales [n_vocab].  Refused by
+   name: a WH_VOCAB_NATIVE context, an unfinalized one. */
+enum { WH_VOCAB_NATIVE = 0, WH_VOCAB_FP8_E4M3 = 1 };
+int wh_set_vocab_format(wh_ctx* ctx, int fmt);
+int wh_read_vocab_w8(wh_ctx* ctx, uint8_t* codes, float* scales);
+
 /* decode n_win windows (slots 0..n_win-1): prefill of the initial tokens
    (init_tokens[w*max_init + i], i < n_init[w]) and the first token update */
 int wh_decode_begin(wh_ctx* ctx, int n_win, const wh_decode_opts* opts, const int* init_tokens, const int* n_init,
@@ -545,8 +580,10 @@ int wh_token_ms(wh_ctx* ctx, float* out, int cap, int* n, int reset);
              its own dispatch events (advances the decode state like a step),
          8 / 9 = the batched step's self-attention (k_self_attn_qkv) of every layer at the
              current context, with the decode's ancestry (8) or every row reading beam slot
-             0's history (9: all beams share one history); the ancestry is restored.
-   For 2, 3, 5, 6, 7, 8 and 9 *ms_per_iter is the average duration of a single kernel launch. */
+             0's history (9: all beams share one history); the ancestry is restored,
+         10 = the step's vocabulary projection of the current batch, back to back (the
+             kernel the batch's vocabulary format selects).
+   For 2, 3, 5, 6, 7, 8, 9 and 10 *ms_per_iter is the average duration of a single kernel launch. */
 int wh_time_stage(wh_ctx* ctx, int what, int iters, double* ms_per_iter);
 
 /* ---- audio file decoding (host only, no context / GPU needed) ----

@@ -25,6 +25,7 @@
 #include "wh_layout.h"
 #include "wh_loop.h"
 #include "wh_proj8.h"
+#include "wh_vocab8.h"
 
 using namespace wh;
 
@@ -56,6 +57,8 @@ struct wh_ctx : DecodeLoop {
   virtual int set_enc_format(int fmt) = 0;
   virtual int set_dec_format(int fmt) = 0;
   virtual int read_dec_w8(int layer, int which, uint8_t* codes, float* scales) = 0;
+  virtual int set_vocab_format(int fmt) = 0;
+  virtual int read_vocab_w8(uint8_t* codes, float* scales) = 0;
   virtual std::string encoder_kernels(int n_win) const = 0;
   virtual int fp8_linear(int M, int N, int K, const float* x, const float* w, const float* bias, int gelu, int tile,
                          float* y, uint8_t* xc, float* xs, uint8_t* wc, float* ws) = 0;
@@ -122,6 +125,14 @@ struct Ctx : public wh_ctx {
   char* d8_base = nullptr;
   std::vector<Dec8Layer> dec8;
   bool d8_quantised = false, w8_step = false;
+  // vocabulary format (wh_set_vocab_format).  The 8-bit copy of the token embedding
+  // (wh_vocab8.h: v8_cols(V) x ns codes, then v8_cols(V) scales) is allocated when
+  // WH_VOCAB_FP8_E4M3 is first chosen and kept until the context is destroyed; v8_step: the
+  // format the current batch began with
+  int vocab_fmt = WH_VOCAB_NATIVE;
+  uint8_t* v8_codes = nullptr;
+  float* v8_scales = nullptr;
+  bool v8_quantised = false, v8_step = false;
   const void* kv8_layer(int l) const { return ckv8 ? ckv8 + (size_t)l * Wcap * ckv8_slot_bytes(nh) : nullptr; }
   float* x_e;
   int64_t* d_seeks;
@@ -174,6 +185,8 @@ struct Ctx : public wh_ctx {
     // this context's 8-bit decoder copies are of the weights it reads now
     d8_quantised = false;
     if (dec_fmt == WH_DEC_FP8_E4M3 || w8_step) TRY(quantise_dec8());
+    v8_quantised = false;
+    if (vocab_fmt == WH_VOCAB_FP8_E4M3 || v8_step) TRY(quantise_vocab8());
     return 0;
   }
 
@@ -190,6 +203,7 @@ struct Ctx : public wh_ctx {
     if (ckv8) rel(hipFree(ckv8), "hipFree(cross-KV 8-bit copy)");
     if (e8_base) rel(hipFree(e8_base), "hipFree(encoder 8-bit copy)");
     if (d8_base) rel(hipFree(d8_base), "hipFree(decoder 8-bit copy)");
+    if (v8_codes) rel(hipFree(v8_codes), "hipFree(vocabulary 8-bit copy)");
     audio.release(rel);
     scratch.release(rel, "hipFree(scratch)");
     if (h_done) rel(hipHostFree(h_done), "hipHostFree(done flags)");
@@ -313,10 +327,12 @@ struct Ctx : public wh_ctx {
       rc = load_row(dec[l], cross_tensors<T>(), part, true, name, data, shape, ndim);
     if (rc) return rc == -1 ? fail(-5, "unknown tensor " + name) : rc;
     loaded.insert(name);
-    // what finalize() derives from the weights (wqx_f, the 8-bit encoder and decoder weights) is stale now
+    // what finalize() derives from the weights (wqx_f, the 8-bit encoder, decoder and vocabulary weights) is
+    // stale now
     finalized = false;
     e8_quantised = false;
     d8_quantised = false;
+    v8_quantised = false;
     return 0;
   }
 
@@ -334,6 +350,51 @@ struct Ctx : public wh_ctx {
     if (enc_fmt == WH_ENC_FP8_E4M3) TRY(quantise_enc8());
     // (w8_step: a batch begun in fp8 still reads the copies after the format was set back)
     if (dec_fmt == WH_DEC_FP8_E4M3 || w8_step) TRY(quantise_dec8());
+    if (vocab_fmt == WH_VOCAB_FP8_E4M3 || v8_step) TRY(quantise_vocab8());
+    return 0;
+  }
+
+  // ------------------------------------------------------------ vocabulary format
+  int quantise_vocab8() {
+    if (launch_quant_vocab_w8(E, v8_codes, v8_scales, V, ns, st))
+      return fail(-20, "vocab_format: k_quant_vocab_w8 does not serve n_text_state " + std::to_string(ns));
+    HIPCHK(hipStreamSynchronize(st));
+    TRY(launch_status(__func__));
+    v8_quantised = true;
+    return 0;
+  }
+  int set_vocab_format(int fmt) override {
+    if (fmt != WH_VOCAB_NATIVE && fmt != WH_VOCAB_FP8_E4M3)
+      return fail(-12, "vocab_format: unknown format " + std::to_string(fmt));
+    if (fmt == vocab_fmt) return 0;
+    if (fmt == WH_VOCAB_FP8_E4M3) {
+      if (sizeof(T) != 2) return fail(-12, "vocab_format: WH_VOCAB_FP8_E4M3 needs an fp16 context (this one is fp32)");
+      if (!proj1_supported(1, ns) || !v8_kw(ns))
+        return fail(-12, "vocab_format: WH_VOCAB_FP8_E4M3 serves n_text_state 1280, 1024, 768, 512, 384 and 128 (the "
+                         "single-window step kernel's widths), not " + std::to_string(ns));
+      if (!v8_codes) {
+        const size_t cb = (size_t)v8_cols(V) * ns;  // (a multiple of 16 bytes: the scales behind it are aligned)
+        void* p = nullptr;
+        HIPCHK(hipMalloc(&p, cb + (size_t)v8_cols(V) * 4));
+        v8_codes = (uint8_t*)p;
+        v8_scales = (float*)(v8_codes + cb);
+      }
+      if (finalized && !v8_quantised) TRY(quantise_vocab8());
+    }
+    // (the captured step graph holds the kernels of v8_step, the format of the batch in flight:
+    // begin_batch drops it where the next batch begins in the other format)
+    vocab_fmt = fmt;
+    return 0;
+  }
+  int read_vocab_w8(uint8_t* codes, float* scales) override {
+    if (vocab_fmt != WH_VOCAB_FP8_E4M3) return fail(-12, "read_vocab_w8: the context's vocabulary format is WH_VOCAB_NATIVE");
+    if (!finalized) return fail(-9, "read_vocab_w8: weights not finalized");
+    std::vector<uint8_t> h((size_t)v8_cols(V) * ns);
+    HIPCHK(hipMemcpy(h.data(), v8_codes, h.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(scales, v8_scales, (size_t)V * 4, hipMemcpyDeviceToHost));
+    const int sw = v8_sw(ns);
+    for (int r = 0; r < V; ++r)
+      for (int k = 0; k < ns; ++k) codes[(size_t)r * ns + k] = h[v8_offset(r, k, ns, sw)];
     return 0;
   }
 
@@ -940,7 +1001,7 @@ struct Ctx : public wh_ctx {
     return std::string("proj=") + (p1 ? (dec_fmt == WH_DEC_FP8_E4M3 ? "k_proj1<w8>" : "k_proj1") : "k_proj") + ",xattn=k_xattn_seg" +
            (kv8 ? (qp ? "<kv8,qproj>" : "<kv8>") : qp ? "<qproj>" : "") + ",self_attn=" +
            (p1 ? (h ? "k_self_attn<kco>" : "k_self_attn") : h ? "k_self_attn_qkv<pipe+kco>" : "k_self_attn_qkv") +
-           ",tail=vocab+k_logit_part";
+           (p1 && vocab_fmt == WH_VOCAB_FP8_E4M3 ? ",tail=vocab<w8>+k_logit_part" : ",tail=vocab+k_logit_part");
   }
 
   int dec_layers_p1(int R, const int* rw, const int* rs, const int* rp, int ancG, int nwin, const int* wr0,
@@ -1021,6 +1082,11 @@ struct Ctx : public wh_ctx {
     if (final_x && rows_sel) return fail(-20, "vocab: a row gather after the k_proj1 layers (xn_d not written)");
     if (final_x) {
       g.xf32 = final_x; g.ln_g = ln_g; g.ln_b = ln_b; g.ln_eps = 1e-5f;
+    }
+    if (final_x && v8_step) {  // this batch's single-window step reads the 8-bit copy of E
+      g.W = v8_codes; g.M = R; g.N = V; g.K = ns;
+      const int rc = launch_vocab1_w8(g, v8_scales, st);
+      return rc == 0 ? 0 : fail(-20, "k_vocab1_w8 launch failed code " + std::to_string(rc));
     }
     return gemm(xn_d, ns, E, nullptr, R, V, ns, EPI_F32_COLS, g);
   }
@@ -1127,11 +1193,12 @@ struct Ctx : public wh_ctx {
     // a format set during the last batch serves from this one on; the captured step graph
     // holds the last batch's kernels and its key (wh_loop.hip ensure_graph) does not know
     // the format, so it goes where the format flips
-    if (w8_step != (dec_fmt == WH_DEC_FP8_E4M3)) {
+    if (w8_step != (dec_fmt == WH_DEC_FP8_E4M3) || v8_step != (vocab_fmt == WH_VOCAB_FP8_E4M3)) {
       HIPCHK(hipStreamSynchronize(st));
       if (gexec) { HIPCHK(hipGraphExecDestroy(gexec)); gexec = nullptr; }
       if (graph) { HIPCHK(hipGraphDestroy(graph)); graph = nullptr; }
-      w8_step = !w8_step;
+      w8_step = dec_fmt == WH_DEC_FP8_E4M3;
+      v8_step = vocab_fmt == WH_VOCAB_FP8_E4M3;
     }
     h_len = nin;
     // the host vectors above must outlive the async copies
@@ -1420,6 +1487,19 @@ struct Ctx : public wh_ctx {
       HIPCHK(hipEventElapsedTime(&t, tm.ev[0], tm.ev[1]));
       *ms = t / (iters * Ld);
       return 0;
+    } else if (what == 10) {
+      // the step's vocabulary projection alone, back to back, on the current batch's rows
+      // (the single-window step: the final LayerNorm in its prologue, as after dec_layers_p1)
+      if (cur_nwin < 1) return fail(-16, "no decode batch");
+      const int R = cur_nwin * cur_G;
+      HIPCHK(hipEventRecord(tm.ev[0], st));
+      for (int i = 0; i < iters; ++i) {
+        final_x = p1_active(R, cur_nwin) ? x_d : nullptr;
+        const int rc = vocab(nullptr, R, logits);
+        final_x = nullptr;
+        if (rc) return rc;
+      }
+      HIPCHK(hipEventRecord(tm.ev[1], st));
     } else if (what == 4) {
       // the token-selection kernel alone on the current logits (state unchanged)
       if (cur_nwin < 1) return fail(-16, "no decode batch");
@@ -1659,6 +1739,11 @@ int wh_set_decoder_format(wh_ctx* ctx, int fmt) { CTXCALL(ctx->set_dec_format(fm
 int wh_read_decoder_w8(wh_ctx* ctx, int layer, int which, uint8_t* codes, float* scales) {
   if (!codes || !scales) return fail(-1, "null argument");
   CTXCALL(ctx->read_dec_w8(layer, which, codes, scales));
+}
+int wh_set_vocab_format(wh_ctx* ctx, int fmt) { CTXCALL(ctx->set_vocab_format(fmt)); }
+int wh_read_vocab_w8(wh_ctx* ctx, uint8_t* codes, float* scales) {
+  if (!codes || !scales) return fail(-1, "null argument");
+  CTXCALL(ctx->read_vocab_w8(codes, scales));
 }
 int wh_encoder_kernels(wh_ctx* ctx, int n_win, char* buf, int cap) {
   if (!ctx || !buf || cap < 1) return fail(-1, "bad arguments");

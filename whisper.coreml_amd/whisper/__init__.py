@@ -72,11 +72,12 @@ def load_model(name: str, device: Optional[Union[str, int]] = None, download_roo
                in_memory: bool = False, use_coreml: bool = False, *, dtype: str = "fp16", max_windows: int = 8,
                max_group: int = 5, synthetic: Optional[bool] = None, seed: int = 0,
                cross_kv: Optional[str] = None, encoder: Optional[str] = None,
-               decoder: Optional[str] = None) -> Whisper:
+               decoder: Optional[str] = None, vocab: Optional[str] = None) -> Whisper:
     """Load a model onto one MI355X (reference __init__.py:107-179).  cross_kv="fp8": the decoder
     step reads an 8-bit copy of the cross-KV; encoder="fp8": the encoder blocks' GEMMs run on the
     8-bit matrix path; decoder="fp8": the single-window decoder step reads 8-bit copies of the
-    decoder layers' weights (HipContext; all three off by default)."""
+    decoder layers' weights; vocab="fp8": that step's vocabulary projection reads an 8-bit copy of the
+    token embedding (HipContext; all four off by default)."""
     dev = _device_index(device)
     if download_root is None:
         default = os.path.join(os.path.expanduser("~"), ".cache")
@@ -115,7 +116,7 @@ def load_model(name: str, device: Optional[Union[str, int]] = None, download_roo
         dims = ModelDimensions(**MODEL_DIMS[name])
         state = synthetic_state_dict(MODEL_DIMS[name], seed)
     model = Whisper(dims, name, device=dev, dtype=dtype, max_windows=max_windows, max_group=max_group,
-                    cross_kv=cross_kv, encoder=encoder, decoder=decoder)
+                    cross_kv=cross_kv, encoder=encoder, decoder=decoder, vocab=vocab)
     model.load_state_dict(state)
     del state
     if align is not None:

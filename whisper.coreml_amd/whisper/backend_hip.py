@@ -28,6 +28,8 @@ WH_ENC_NATIVE = 0
 WH_ENC_FP8_E4M3 = 1
 WH_DEC_NATIVE = 0
 WH_DEC_FP8_E4M3 = 1
+WH_VOCAB_NATIVE = 0
+WH_VOCAB_FP8_E4M3 = 1
 WH_PCM_S16, WH_PCM_S32, WH_PCM_F32 = 0, 1, 2
 
 
@@ -115,6 +117,8 @@ _EXPORTS = {
     "wh_encoder_kernels": (c_int, [c_void_p, c_int, ctypes.c_char_p, c_int]),
     "wh_set_decoder_format": (c_int, [c_void_p, c_int]),
     "wh_read_decoder_w8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "wh_set_vocab_format": (c_int, [c_void_p, c_int]),
+    "wh_read_vocab_w8": (c_int, [c_void_p, c_void_p, c_void_p]),
     "wh_fp8_linear": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "wh_decode_begin": (c_int, [c_void_p, c_int, POINTER(WhDecodeOpts), c_void_p, c_void_p, c_int, c_void_p]),
@@ -320,7 +324,8 @@ class HipContext:
     """One libwhisper_hip context = one model on one GPU (per process)."""
 
     def __init__(self, dims: dict, device: int = 0, dtype: str = "fp16", max_windows: int = 8, max_group: int = 5,
-                 cross_kv: Optional[str] = None, encoder: Optional[str] = None, decoder: Optional[str] = None):
+                 cross_kv: Optional[str] = None, encoder: Optional[str] = None, decoder: Optional[str] = None,
+                 vocab: Optional[str] = None):
         """cross_kv: None (the compute type) or "fp8": the decoder step's cross-attention reads
         an 8-bit (E4M3) copy of the cross-KV (wh_set_cross_kv_format).  With None, the
         environment variable WHISPER_HIP_CROSS_KV=fp8 selects it for fp16 contexts.
@@ -332,7 +337,19 @@ class HipContext:
         channel (wh_set_decoder_format); with None, WHISPER_HIP_DECODER=fp8 selects it for the
         contexts it can serve (fp16, a model width the single-window step kernel has) and leaves
         the others native, where decoder="fp8" raises.  Off by default; accuracy on real speech is
-        unmeasured."""
+        unmeasured.
+        vocab: None / "native" or "fp8": the vocabulary projection of the single-window decoder step
+        reads an 8-bit (E4M3) copy of the token embedding, one scale per vocabulary row
+        (wh_set_vocab_format); with None, WHISPER_HIP_VOCAB=fp8 selects it for the contexts it can
+        serve (those decoder="fp8" can) and leaves the others native, where vocab="fp8" raises.
+        Off by default; accuracy on real speech is unmeasured."""
+        vocab_from_env = vocab is None
+        if vocab is None:
+            vocab = "fp8" if dtype == "fp16" and os.environ.get("WHISPER_HIP_VOCAB", "") == "fp8" else "native"
+        if vocab not in ("native", "fp8"):
+            raise ValueError(f"vocab={vocab!r}: 'native' or 'fp8'")
+        if vocab == "fp8" and dtype != "fp16":
+            raise ValueError(f"vocab='fp8' needs dtype='fp16', not dtype={dtype!r}: the 8-bit embedding feeds fp16 MFMAs")
         decoder_from_env = decoder is None
         if decoder is None:
             decoder = "fp8" if dtype == "fp16" and os.environ.get("WHISPER_HIP_DECODER", "") == "fp8" else "native"
@@ -380,6 +397,14 @@ class HipContext:
                 self.set_decoder_format(WH_DEC_FP8_E4M3)
             except HipBackendError:
                 if not decoder_from_env:  # (refused by name, context unchanged: the environment's default stays native)
+                    self.close()
+                    raise
+        self.vocab_format = "native"
+        if vocab == "fp8":
+            try:
+                self.set_vocab_format(WH_VOCAB_FP8_E4M3)
+            except HipBackendError:
+                if not vocab_from_env:  # (as above: the environment's default stays native)
                     self.close()
                     raise
         self.phrase_bias = None  # what set_phrase_bias installed: (phrases, boosts, start)
@@ -855,6 +880,21 @@ class HipContext:
         codes, scales = np.empty((N, K), dtype=np.uint8), np.empty(N, dtype=np.float32)
         self._check(self.lib.wh_read_decoder_w8(self.h, int(layer), int(which), _ptr(codes), _ptr(scales)),
                     "wh_read_decoder_w8")
+        return codes, scales
+
+    def set_vocab_format(self, fmt):
+        """wh_set_vocab_format: WH_VOCAB_NATIVE / "native" or WH_VOCAB_FP8_E4M3 / "fp8"; serves the
+        batches begun after it (decode_begin, prefill)."""
+        fmt = {"native": WH_VOCAB_NATIVE, "fp8": WH_VOCAB_FP8_E4M3}.get(fmt, fmt)
+        self._check(self.lib.wh_set_vocab_format(self.h, int(fmt)), "wh_set_vocab_format")
+        self.vocab_format = "fp8" if int(fmt) == WH_VOCAB_FP8_E4M3 else "native"
+
+    def vocab_w8(self):
+        """The 8-bit copy of the token embedding (wh_read_vocab_w8): (codes uint8 E4M3
+        [n_vocab][n_text_state] in logical order, scales fp32 [n_vocab]); value = code * scale."""
+        V, n = self.dims["n_vocab"], self.dims["n_text_state"]
+        codes, scales = np.empty((V, n), dtype=np.uint8), np.empty(V, dtype=np.float32)
+        self._check(self.lib.wh_read_vocab_w8(self.h, _ptr(codes), _ptr(scales)), "wh_read_vocab_w8")
         return codes, scales
 
     def encoder_kernels(self, n_win: int) -> dict:

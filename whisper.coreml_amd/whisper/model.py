@@ -33,14 +33,15 @@ class ModelDimensions:
 class Whisper:
     def __init__(self, dims: ModelDimensions, name: str = "", device: int = 0, dtype: str = "fp16",
                  max_windows: int = 8, max_group: int = 5, cross_kv: Optional[str] = None,
-                 encoder: Optional[str] = None, decoder: Optional[str] = None):
+                 encoder: Optional[str] = None, decoder: Optional[str] = None, vocab: Optional[str] = None):
         self.dims = dims
         self.name = name
         self.modelName = name
         self.device_index = device
         self.dtype = dtype
         self.ctx = HipContext(dims.__dict__, device=device, dtype=dtype, max_windows=max_windows,
-                              max_group=max_group, cross_kv=cross_kv, encoder=encoder, decoder=decoder)
+                              max_group=max_group, cross_kv=cross_kv, encoder=encoder, decoder=decoder,
+                              vocab=vocab)
         # default alignment heads: last half of the decoder layers (model.py:51-56)
         heads = np.zeros((dims.n_text_layer, dims.n_text_head), dtype=bool)
         heads[dims.n_text_layer // 2:] = True
