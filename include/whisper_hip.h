@@ -543,7 +543,9 @@ int wh_score_batch(wh_ctx* ctx, int n_seq, const int* slots, const int* tokens, 
 
 /* the kernels the decoder step runs for a batch of n_win windows x group rows, as
    "proj=<name>,xattn=<name>" (the dominant projection family and the cross-attention;
-   what bench.py labels its roofline lines with).  Returns the length written. */
+   what bench.py labels its roofline lines with), then self_attn=, tail= and vocab=<the kernel
+   of the vocabulary projection: k_vocab1, k_vocab_small, k_vocab_2p, k_gemv_x, k_gemv_rows or
+   k_vocab1_w8, named by the function that picks it for the launch>.  Returns the length written. */
 int wh_step_kernels(wh_ctx* ctx, int n_win, int group, char* buf, int cap);
 
 /* cumulative stage wall times in ms: [0] mel [1] encode [2] prefill [3] steps

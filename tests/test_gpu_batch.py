@@ -16,6 +16,9 @@ Bars (DESIGN.md §2 states them):
     (measured worst cases, round 6 with fp16 split-K slabs and the in-kernel cross-attention
     query: 9.3e-6 = 0.46 TAU and 3.9e-3 = 0.39 TAU, profiles/r06/fp16_margins.json; every
     case's worst error, its step / row and top-1 agreement go to gpurun_out/margins.jsonl);
+    where a trajectory carries the reference's whole rows (recorded ones do, for a few passes;
+    the golden ones do not), the same bound on every one of the V columns, every value
+    finite (score_whole_row, check_whole_rows; test_gpu_logit_rows.py);
   * the reference's host loop (decoding.py:707-737, restated by the oracle) driving
     the per-step ABI through whisper.inference.HipInference: fp32 tokens exact.
 """
@@ -127,11 +130,45 @@ def _trajectory(gs, prefix):
                 src=gs[f"{prefix}_src"] if f"{prefix}_src" in gs.files else None)
 
 
-def _teacher_force(m, trajs, sot):
+def score_top32(row, topv, topi, tau):
+    """One row of logits against the reference's top-32 (values topv, descending, at columns
+    topi): max |row - ref| over those 32 columns as a share of their range, and whether the
+    row's argmax is the reference's (True where the reference's top-2 margin is not decisive)."""
+    rng = topv[0] - topv[-1]
+    rel = np.abs(row[topi] - topv).max() / rng
+    top1 = True
+    if topv[0] - topv[1] > 2 * tau * rng:
+        top1 = int(np.argmax(row)) == int(topi[0])
+    return rel, top1
+
+
+def score_whole_row(row, ref, topv):
+    """One row of logits against the reference's whole row: max over ALL columns of
+    |row - ref| as a share of the same top-32 range, and the column where it sits.  A value
+    that is not finite scores inf at its column."""
+    bad = ~np.isfinite(row)
+    if bad.any():
+        return np.inf, int(np.argmax(bad))
+    err = np.abs(row - ref)
+    col = int(np.argmax(err))
+    return err[col] / (topv[0] - topv[-1]), col
+
+
+def whole_row_passes(n_passes):
+    """The passes whose whole rows a recorded trajectory keeps: the first pass, passes 1 and 2
+    (two consecutive steps: a column left unwritten shows as the previous step's value; on a
+    beam trajectory pass 1 is also the first after a reorder) and the last."""
+    return frozenset(p for p in (0, 1, 2, n_passes - 1) if 0 <= p < n_passes)
+
+
+def _teacher_force(m, trajs, sot, whole=False):
     """Replays one reference trajectory per window (trajs[w]) through the per-step ABI:
     wh_prefill of the sot sequence, then per step the reorder (beam) and wh_step with the
     reference's tokens.  Returns per-(step, row) relative errors and the per-step top-1
-    agreement where the reference's top-2 margin is decisive."""
+    agreement where the reference's top-2 margin is decisive.
+    whole=True: two more arrays, for the passes s whose whole reference rows the trajectories
+    carry (trajs[w]["full"][s], fp32 [rows][V]): score_whole_row's share per (step, row), NaN at
+    the other passes, and its column, -1 there."""
     n_win = len(trajs)
     S, G = trajs[0]["tok"].shape
     for t in trajs:
@@ -139,15 +176,18 @@ def _teacher_force(m, trajs, sot):
     two = m.ctx.prefill([sot] * n_win, G, [0] * n_win)         # [n_win][2][V]
     rel = np.zeros((S, n_win * G))
     top1 = np.ones((S, n_win * G), dtype=bool)
+    rel_all = np.full((S, n_win * G), np.nan)
+    col_all = np.full((S, n_win * G), -1)
 
     def score(s, rows):
         for r in range(n_win * G):
             w, b = divmod(r, G)
             topv, topi = trajs[w]["topv"][s, b], trajs[w]["topi"][s, b]
-            rng = topv[0] - topv[-1]
-            rel[s, r] = np.abs(rows[r][topi] - topv).max() / rng
-            if topv[0] - topv[1] > 2 * TAU[m.dtype] * rng:
-                top1[s, r] = int(np.argmax(rows[r])) == int(topi[0])
+            rel[s, r], top1[s, r] = score_top32(rows[r], topv, topi, TAU[m.dtype])
+            full = (trajs[w].get("full") or {}).get(s) if whole else None
+            if full is not None:
+                assert rows[r].shape == full[b].shape, (rows[r].shape, full[b].shape)
+                rel_all[s, r], col_all[s, r] = score_whole_row(rows[r], full[b], topv)
 
     score(0, np.repeat(two[:, 1], G, axis=0))
     for s in range(1, S):
@@ -156,7 +196,26 @@ def _teacher_force(m, trajs, sot):
         lg = m.ctx.step([int(x) for w in range(n_win) for x in trajs[w]["tok"][s]],
                         text_offsets=[len(sot) + s - 1] * n_win)
         score(s, lg)
-    return rel, top1
+    return (rel, top1, rel_all, col_all) if whole else (rel, top1)
+
+
+def check_whole_rows(test, rel, rel_all, col_all, dtype, kernel, **shape):
+    """The whole-row bar: TAU[dtype] x the row's top-32 range on every column of every kept
+    (pass, row), every value finite.  Records the worst whole-row share beside the top-32 one
+    (the margin log, conftest.record_margin) before it asserts."""
+    kept = ~np.isnan(rel_all)
+    assert kept[..., 0, :].all() and kept[..., 1:, :].any(), "the trajectory kept no whole reference rows"
+    at = np.unravel_index(int(np.nanargmax(rel_all)), rel_all.shape)
+    worst, col = float(rel_all[at]), int(col_all[at])
+    over = np.argwhere(kept & ~(np.nan_to_num(rel_all, nan=0.0) <= TAU[dtype]))
+    print(f"{test} {shape} {kernel}: whole rows over {int(kept.any(axis=-1).sum())} passes: max rel err {worst:.3e} "
+          f"({worst / TAU[dtype]:.3f} TAU) at pass {at[-2]} row {at[-1]} column {col}; top-32 {rel.max() / TAU[dtype]:.3f} TAU")
+    record_margin("logit_rows", case=test, kernel=kernel, dtype=dtype, worst_rel_all=worst, worst_col=col,
+                  worst_pass=int(at[-2]), worst_row=int(at[-1]), frac_of_tau=worst / TAU[dtype], tau=TAU[dtype],
+                  worst_rel_top32=float(rel.max()), frac_of_tau_top32=float(rel.max() / TAU[dtype]), **shape)
+    assert len(over) == 0, (f"whole-row max rel err {worst:.3e} > {TAU[dtype]} at (pass, row) {tuple(map(int, at[-2:]))} "
+                            f"column {col}; (.., pass, row, column) over the bar: "
+                            f"{[list(map(int, i)) + [int(col_all[tuple(i)])] for i in over[:16]]}")
 
 
 @pytest.mark.parametrize("n_win", [1, NWIN])

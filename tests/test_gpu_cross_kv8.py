@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import record_margin
-from test_gpu_batch import TAU, _teacher_force
+from test_gpu_batch import TAU, _teacher_force, check_whole_rows, whole_row_passes
 from test_gpu_widths import NONDECISIVE_CAP, TOPK, nondecisive
 
 gpu = pytest.mark.gpu
@@ -114,16 +114,18 @@ def _reference(model, seed, group, single):
     rng = np.random.default_rng([30, seed, group])
     om.cross_k, om.cross_v = own[seed]
     lg, cache, _ = om.decoder_forward(torch.tensor([sot] * group), 0, None)
-    tok, topv, topi = [np.full(group, sot[-1])], [], []
+    tok, topv, topi, full = [np.full(group, sot[-1])], [], [], {}
     om.cross_k, om.cross_v = [as_rows(k) for k, _ in deq], [as_rows(v) for _, v in deq]
     for s in range(N_STEPS + 1):
         v, i = torch.topk(lg[:, -1], TOPK)
         topv.append(v.numpy()), topi.append(i.numpy())
+        if s in whole_row_passes(N_STEPS + 1):
+            full[s] = lg[:, -1].numpy().copy()
         if s == N_STEPS:
             break
         tok.append(rng.integers(0, eot, group))
         lg, cache, _ = om.decoder_forward(torch.from_numpy(tok[-1])[:, None], len(sot) + s, cache)
-    return dict(tok=np.stack(tok), topv=np.stack(topv), topi=np.stack(topi), src=None)
+    return dict(tok=np.stack(tok), topv=np.stack(topv), topi=np.stack(topi), src=None, full=full)
 
 
 # ------------------------------------------------------------------ 1. the quantiser
@@ -166,7 +168,7 @@ def test_teacher_forced_step_logits(model, n_win, group):
     _encode(m, n_win)
     trajs = [_reference(model, SEEDS[w % 2], group, n_win == 1) for w in range(n_win)]
     skipped = nondecisive(trajs, TAU["fp16"])
-    rel, top1 = _teacher_force(m, trajs, _oracle(model)[3])
+    rel, top1, rel_all, col_all = _teacher_force(m, trajs, _oracle(model)[3], whole=True)
     worst = np.unravel_index(int(np.argmax(rel)), rel.shape)
     print(f"{model} fp8 {n_win} x {group}: max rel err {rel.max():.3e} ({rel.max() / TAU['fp16']:.3f} TAU) at step "
           f"{worst[0]} row {worst[1]}, top-1 agreement {top1.mean():.4f}, non-decisive {skipped:.4f}; {kern}")
@@ -176,6 +178,9 @@ def test_teacher_forced_step_logits(model, n_win, group):
     assert skipped <= NONDECISIVE_CAP, f"the top-1 check would skip {skipped:.3f} of the (step, row) pairs"
     assert rel.max() <= TAU["fp16"], f"max rel err {rel.max():.3e} > {TAU['fp16']} at step {worst[0]} row {worst[1]}"
     assert top1.all(), f"top-1 differs at {np.argwhere(~top1)[:5].tolist()} despite a decisive margin"
+    # every column of the first pass, steps 1, 2 and the last, the same bar
+    check_whole_rows("cross_kv8_teacher_forced", rel, rel_all, col_all, "fp16", kern["vocab"], model=model, windows=n_win,
+                     rows=int(rel.shape[1]))
 
 
 # ------------------------------------------------------------------ 3. batch invariance

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import record_margin
-from test_gpu_batch import TAU, _teacher_force
+from test_gpu_batch import TAU, _teacher_force, check_whole_rows, whole_row_passes
 from test_gpu_widths import NONDECISIVE_CAP, TOPK, nondecisive
 
 gpu = pytest.mark.gpu
@@ -73,6 +73,7 @@ def _close_contexts():
     yield
     for k in list(_CTX):
         _CTX.pop(k).close()
+    _reference.cache_clear()      # the kept whole rows
 
 
 def _encode(m, seeds):
@@ -146,15 +147,17 @@ def _reference(width, seed, group):
     om.cross_k, om.cross_v = om8.cross_k, om8.cross_v = _cross_kv(width, seed)
     rng = np.random.default_rng([32, seed, group])
     lg, cache, _ = om.decoder_forward(torch.tensor([sot] * group), 0, None)
-    tok, topv, topi = [np.full(group, sot[-1])], [], []
+    tok, topv, topi, full = [np.full(group, sot[-1])], [], [], {}
     for s in range(N_STEPS + 1):
         v, i = torch.topk(lg[:, -1], TOPK)
         topv.append(v.numpy()), topi.append(i.numpy())
+        if s in whole_row_passes(N_STEPS + 1):
+            full[s] = lg[:, -1].numpy().copy()
         if s == N_STEPS:
             break
         tok.append(rng.integers(0, eot, group))
         lg, cache, _ = om8.decoder_forward(torch.from_numpy(tok[-1])[:, None], len(sot) + s, cache)
-    return dict(tok=np.stack(tok), topv=np.stack(topv), topi=np.stack(topi), src=None)
+    return dict(tok=np.stack(tok), topv=np.stack(topv), topi=np.stack(topi), src=None, full=full)
 
 
 @gpu
@@ -168,12 +171,11 @@ def test_teacher_forced_step_logits(width, group):
     assert kern["proj"] == "k_proj1<w8>", kern
     trajs = [_reference(width, seed, group) for seed in SEEDS]
     skipped = nondecisive(trajs, TAU["fp16"])
-    rels, top1s = [], []
+    res = []
     for seed, t in zip(SEEDS, trajs):
         _encode(m, [seed])
-        rel, top1 = _teacher_force(m, [t], _oracle(width)[3])
-        rels.append(rel), top1s.append(top1)
-    rel, top1 = np.stack(rels), np.stack(top1s)
+        res.append(_teacher_force(m, [t], _oracle(width)[3], whole=True))
+    rel, top1, rel_all, col_all = (np.stack(x) for x in zip(*res))
     print(f"{width} w8 1 x {group}: max rel err {rel.max():.3e} ({rel.max() / TAU['fp16']:.3f} TAU), top-1 agreement "
           f"{top1.mean():.4f}, non-decisive {skipped:.4f}; {kern}")
     record_margin("decoder_w8_teacher_forced", width=width, rows=group, worst_rel=float(rel.max()),
@@ -182,6 +184,8 @@ def test_teacher_forced_step_logits(width, group):
     assert skipped <= NONDECISIVE_CAP, f"the top-1 check would skip {skipped:.3f} of the (step, row) pairs"
     assert rel.max() <= TAU["fp16"], f"max rel err {rel.max():.3e} > {TAU['fp16']}"
     assert top1.all(), f"top-1 differs at {np.argwhere(~top1)[:5].tolist()} despite a decisive margin"
+    # (seed, pass, row): every column of the first pass, steps 1, 2 and the last, the same bar
+    check_whole_rows("decoder_w8_teacher_forced", rel, rel_all, col_all, "fp16", kern["vocab"], width=width, rows=group)
 
 
 # ------------------------------------------------------------------ 3. nothing else moved

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import record_margin
-from test_gpu_batch import TAU, _teacher_force
+from test_gpu_batch import TAU, _teacher_force, check_whole_rows, whole_row_passes
 from test_gpu_decoder_w8 import MODEL_OF, N_STEPS, PARTS, SEEDS, _drive, _e4m3, _encode, _loop, _mel
 from test_gpu_widths import NONDECISIVE_CAP, TOPK, nondecisive
 
@@ -112,15 +112,17 @@ def _reference(width, V, decoder, seed, group):
     om.cross_k, om.cross_v = om8.cross_k, om8.cross_v = _cross_kv(width, V, seed)
     rng = np.random.default_rng([34, seed, group])
     lg, cache, _ = om.decoder_forward(torch.tensor([sot] * group), 0, None)
-    tok, topv, topi = [np.full(group, sot[-1])], [], []
+    tok, topv, topi, full = [np.full(group, sot[-1])], [], [], {}
     for s in range(N_STEPS + 1):
         v, i = torch.topk(lg[:, -1, -V:], TOPK)
         topv.append(v.numpy()), topi.append(i.numpy())
+        if s in whole_row_passes(N_STEPS + 1):
+            full[s] = lg[:, -1, -V:].numpy().copy()
         if s == N_STEPS:
             break
         tok.append(rng.integers(0, eot, group))
         lg, cache, _ = om8.decoder_forward(torch.from_numpy(tok[-1])[:, None], len(sot) + s, cache)
-    return dict(tok=np.stack(tok), topv=np.stack(topv), topi=np.stack(topi), src=None)
+    return dict(tok=np.stack(tok), topv=np.stack(topv), topi=np.stack(topi), src=None, full=full)
 
 
 # every width at 1, 5, 8 rows; at 384 a last tile of 8, 9, 10 columns (whole stores, scalar tails); one over decoder="fp8"
@@ -140,8 +142,8 @@ def test_teacher_forced_step_logits(width, V, group, decoder):
     res = []
     for seed, t in zip(SEEDS, trajs):
         _encode(m, [seed])
-        res.append(_teacher_force(m, [t], _oracle(width, V)[3]))
-    rel, top1 = (np.stack(x) for x in zip(*res))
+        res.append(_teacher_force(m, [t], _oracle(width, V)[3], whole=True))
+    rel, top1, rel_all, col_all = (np.stack(x) for x in zip(*res))
     print(f"{width} V {V} vocab w8 1 x {group} decoder {decoder}: max rel err {rel.max():.3e} "
           f"({rel.max() / TAU['fp16']:.3f} TAU), top-1 agreement {top1.mean():.4f}, non-decisive {skipped:.4f}; {kern}")
     record_margin("vocab_w8_teacher_forced", width=width, n_vocab=V, rows=group, decoder=decoder, worst_rel=float(rel.max()),
@@ -150,6 +152,10 @@ def test_teacher_forced_step_logits(width, V, group, decoder):
     assert skipped <= NONDECISIVE_CAP, f"the top-1 check would skip {skipped:.3f} of the (step, row) pairs"
     assert rel.max() <= TAU["fp16"], f"max rel err {rel.max():.3e} > {TAU['fp16']}"
     assert top1.all(), f"top-1 differs at {np.argwhere(~top1)[:5].tolist()} despite a decisive margin"
+    # (seed, pass, row): every column, the ragged last tile included, of the first pass, steps 1, 2 and the last
+    assert kern["vocab"] == "k_vocab1_w8", kern
+    check_whole_rows("vocab_w8_teacher_forced", rel, rel_all, col_all, "fp16", kern["vocab"], width=width, n_vocab=V,
+                     rows=group, decoder=decoder)
 
 
 @gpu

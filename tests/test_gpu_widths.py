@@ -20,7 +20,8 @@ Bars:
   * teacher-forced step logits along a seeded random trajectory (136 steps after the prefill,
     random source rows through wh_reorder_kv at 5 beams): test_gpu_batch.py's
         max |logit - oracle| over the oracle's top-32  <=  TAU[dtype] * (top-32 range)
-    per (step, row), top-1 equal wherever the oracle's top-2 margin exceeds 2 TAU range;
+    per (step, row), top-1 equal wherever the oracle's top-2 margin exceeds 2 TAU range; at the
+    first pass, steps 1, 2 and the last the same bar on every one of the V columns, all finite;
   * batch invariance: the same two windows' step logits in batches of 2 and 7 windows,
     bit-identical;
   * encoder output, every element: 2e-3 (fp32) / 6e-2 (fp16) max abs; cross K / V, every
@@ -35,7 +36,7 @@ import numpy as np
 import pytest
 
 from conftest import record_margin
-from test_gpu_batch import TAU, _teacher_force
+from test_gpu_batch import TAU, _teacher_force, check_whole_rows, whole_row_passes
 
 gpu = pytest.mark.gpu
 
@@ -58,12 +59,15 @@ class OracleRecorder:
     OracleWhisper whose audio is set, recording per pass the token fed to every row, the
     top-32 of the raw last-position logits and the reorder source rows: the
     dict(tok, topv, topi, src) that test_gpu_batch._teacher_force replays.  Pass 0 is the
-    first pass over the initial tokens; src[s - 1] is applied between passes s - 1 and s."""
+    first pass over the initial tokens; src[s - 1] is applied between passes s - 1 and s.
+    keep: the passes whose whole last-position logits (fp32 [rows][V]) are kept as well and come
+    back as full = {pass: array}, for _teacher_force's whole-row score; none by default."""
 
-    def __init__(self, om):
+    def __init__(self, om, keep=()):
         self.om = om
         self.cache, self.offset = None, 0
         self.tok, self.topv, self.topi, self.src = [], [], [], []
+        self.keep, self.full = frozenset(keep), {}
 
     def logits(self, tokens, audio_features=None):
         import torch
@@ -72,6 +76,8 @@ class OracleRecorder:
         lg, self.cache, _ = self.om.decoder_forward(inp, self.offset, self.cache)
         self.offset += inp.shape[1]
         v, i = torch.topk(lg[:, -1], TOPK)
+        if len(self.tok) in self.keep:
+            self.full[len(self.tok)] = lg[:, -1].numpy().copy()
         self.tok.append(inp[:, -1].numpy().copy())
         self.topv.append(v.numpy())
         self.topi.append(i.numpy())
@@ -85,15 +91,15 @@ class OracleRecorder:
     def trajectory(self):
         assert not self.src or len(self.src) >= len(self.tok) - 1
         return dict(tok=np.stack(self.tok), topv=np.stack(self.topv), topi=np.stack(self.topi),
-                    src=np.asarray(self.src[:len(self.tok) - 1]) if self.src else None)
+                    src=np.asarray(self.src[:len(self.tok) - 1]) if self.src else None, full=dict(self.full))
 
 
-def random_trajectory(om, sot, group, n_steps, rng):
+def random_trajectory(om, sot, group, n_steps, rng, keep=()):
     """A seeded random trajectory through the recorder: after the first pass over ``sot``,
     every step reorders the rows by a source vector drawn uniformly with repeats (group > 1)
     and feeds every row a token drawn uniformly from the vocabulary."""
     import torch
-    rec = OracleRecorder(om)
+    rec = OracleRecorder(om, keep)
     rec.logits(torch.tensor([list(sot)] * group))
     for _ in range(n_steps):
         if group > 1:
@@ -161,7 +167,8 @@ def _oracle(width):
 @functools.lru_cache(maxsize=None)
 def _random_reference(width, seed, group):
     o = _oracle(width)
-    return random_trajectory(o.audio(seed), o.sot, group, N_STEPS, np.random.default_rng([11, seed, group]))
+    return random_trajectory(o.audio(seed), o.sot, group, N_STEPS, np.random.default_rng([11, seed, group]),
+                             keep=whole_row_passes(N_STEPS + 1))
 
 
 @functools.lru_cache(maxsize=None)
@@ -199,6 +206,7 @@ def _close_contexts():
     yield
     for k in list(_CTX):
         _CTX.pop(k).close()
+    _random_reference.cache_clear()       # the kept whole rows
 
 
 def _encode(m, n_win):
@@ -227,7 +235,7 @@ def test_teacher_forced_step_logits(width, dtype, n_win, group):
     sot = _oracle(width).sot
     skipped = nondecisive(trajs, TAU[dtype])
     _encode(m, n_win)
-    rel, top1 = _teacher_force(m, trajs, sot)
+    rel, top1, rel_all, col_all = _teacher_force(m, trajs, sot, whole=True)
     assert rel.shape == (N_STEPS + 1, n_win * group)
     worst = np.unravel_index(int(np.argmax(rel)), rel.shape)
     print(f"width {width} {dtype} {n_win} x {group}: max rel err {rel.max():.3e} ({rel.max() / TAU[dtype]:.3f} TAU) at "
@@ -241,6 +249,9 @@ def test_teacher_forced_step_logits(width, dtype, n_win, group):
     assert skipped <= NONDECISIVE_CAP, f"the top-1 check would skip {skipped:.3f} of the (step, row) pairs"
     assert rel.max() <= TAU[dtype], f"max rel err {rel.max():.3e} > {TAU[dtype]} at step {worst[0]} row {worst[1]}"
     assert top1.all(), f"top-1 differs at {np.argwhere(~top1)[:5].tolist()} despite a decisive margin"
+    # every column of the kept passes' rows (first pass, steps 1, 2 and the last), the same bar
+    check_whole_rows("widths_teacher_forced", rel, rel_all, col_all, dtype, kern["vocab"], model=MODEL_OF[width],
+                     width=width, windows=n_win, rows=int(rel.shape[1]))
 
 
 INVARIANCE_STEPS = 40

@@ -1,6 +1,7 @@
 // GEMM argument block and fused epilogues (see wh_gemm.hip).
 #pragma once
 #include "wh_common.h"
+#include "wh_vocab_pick.h"
 
 namespace wh {
 
@@ -188,6 +189,11 @@ WH_DEV void tile_epilogue(const GemmArgs& a, const float4_t (&acc)[MI][NI], RowF
     }
   }
 }
+
+// the kernel a vocabulary projection (EPI_F32_COLS) of this shape runs: vocab_kernel
+// (wh_vocab_pick.h) with the tuning build's two switches read.  launch_gemm, launch_vocab1_w8,
+// the runtime's vocab() and wh_step_kernels all go by it.
+VocabKernel step_vocab_kernel(int elt, int M, int N, int K, bool ln, bool w8);
 
 template <typename T>
 int launch_gemm(const GemmArgs& a, int epi, hipStream_t st);

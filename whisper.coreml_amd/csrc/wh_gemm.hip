@@ -1078,6 +1078,18 @@ int gemv_ksplit(int M, int N, int K, int max_z, int mt_block) {
 }
 
 // ============================================================ launchers
+VocabKernel step_vocab_kernel(int elt, int M, int N, int K, bool ln, bool w8) {
+  static const bool vocab_small = [] {  // WHISPER_HIP_VOCAB_SMALL=0: the k_gemv path (A/B)
+    const char* e = tune_env("WHISPER_HIP_VOCAB_SMALL");
+    return !(e && e[0] == '0');
+  }();
+  static const bool vocab1 = [] {  // WHISPER_HIP_VOCAB1=0: k_vocab_small serves the single-window step (A/B)
+    const char* e = tune_env("WHISPER_HIP_VOCAB1");
+    return !(e && e[0] == '0');
+  }();
+  return vocab_kernel(elt, M, N, K, ln, w8, vocab1, vocab_small);
+}
+
 template <typename T>
 int launch_gemm_tiles(const GemmArgs& a, int epi, int tile_sel, hipStream_t st);
 
@@ -1141,21 +1153,12 @@ int launch_gemm_tiles(const GemmArgs& a, int epi, int tile_sel, hipStream_t st) 
     const int rows_per = rows_per_block(a.M, a.mt_block);
     const int ks = epi == EPI_PARTIAL ? a.ksplit : 1;
     if (ks < 1 || ks > a.K / 32) return -4;
-    static const bool vocab_small = [] {  // WHISPER_HIP_VOCAB_SMALL=0: the k_gemv path (A/B)
-      const char* e = tune_env("WHISPER_HIP_VOCAB_SMALL");
-      return !(e && e[0] == '0');
-    }();
-    if (a.xf32 && !(vocab_small && epi == EPI_F32_COLS && a.N >= 16384 && a.M <= 8 && a.K <= 1280 && a.K % 32 == 0 &&
-                    !a.x_rows))
-      return -6;  // the LayerNorm prologue exists only in k_vocab_small / k_vocab1
-    // the single-window step (LayerNorm prologue, fp16, K 1280): k_vocab1, balanced over the
-    // chip (WHISPER_HIP_VOCAB1=0 in the tuning build: k_vocab_small)
-    static const bool vocab1 = [] {
-      const char* e = tune_env("WHISPER_HIP_VOCAB1");
-      return !(e && e[0] == '0');
-    }();
-    if (sizeof(T) == 2 && vocab1 && a.xf32 && a.K == 1280 && !a.bias && a.M <= 8 && (a.N + 15) / 16 <= 256 * 13) {
-      constexpr int D = 6;  // (N + 15) / 16 <= 256 x 13: at most 13 tiles per workgroup (TMAX)
+    // the vocabulary projection: step_vocab_kernel names the kernel, the cases below launch it
+    if (epi == EPI_F32_COLS && a.bias) return -7;  // logits carry no bias
+    const VocabKernel vk = epi == EPI_F32_COLS ? step_vocab_kernel((int)sizeof(T), a.M, a.N, a.K, a.xf32 != nullptr, false) : VK_NONE;
+    if (a.xf32 && (vk == VK_NONE || a.x_rows)) return -6;  // the LayerNorm prologue exists only in k_vocab_small / k_vocab1
+    if (vk == VK_VOCAB1) {
+      constexpr int D = 6;  // at most 13 tiles per workgroup (TMAX)
       const int lds = 8 * (1280 * 2 + 16) + 13 * 8 * 64 * 16;
       static bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vocab1<D>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
@@ -1163,14 +1166,9 @@ int launch_gemm_tiles(const GemmArgs& a, int epi, int tile_sel, hipStream_t st) 
       k_vocab1<D><<<256, 512, lds, st>>>(a), wh_launched("k_vocab1");
       return 0;
     }
-    // k_vocab_small: the rows in groups of <= 64 that fit LDS with all of K (152 KB)
-    const int vxrow = a.K * (int)sizeof(T) + 16;
-    const int vrg_max = std::min(64, (152 * 1024) / vxrow);
-    const int vgrp = (a.M + vrg_max - 1) / vrg_max;
-    // (<= 32 rows: at 100 rows, 2 groups of 50, it measured 89.2 us against k_gemv_x's 84.6:
-    // each CU streams its column block twice, profiles/r03/vocab_groups_ab.txt)
-    if (vocab_small && epi == EPI_F32_COLS && !a.bias && a.N >= 16384 && a.M <= (sizeof(T) == 2 ? 32 : 16) && vgrp <= 4 &&
-        a.K <= 1280 && a.K % 32 == 0) {
+    if (vk == VK_VOCAB_SMALL) {
+      const int vxrow = a.K * (int)sizeof(T) + 16;
+      const int vgrp = vocab_small_groups((int)sizeof(T), a.M, a.K);
       const int rg = (a.M + vgrp - 1) / vgrp, mtv = (rg + 15) / 16;
       const int lds = rg * vxrow;
       const int grid = vgrp * std::max(1, std::min(256 / vgrp, (a.N + 127) / 128));
@@ -1191,10 +1189,7 @@ int launch_gemm_tiles(const GemmArgs& a, int epi, int tile_sel, hipStream_t st) 
         default: return go(std::integral_constant<int, 4>());
       }
     }
-    // k_vocab_2p: 33..112 fp16 rows resident in LDS, half of K per pass
-    if (sizeof(T) == 2 && vocab_small && epi == EPI_F32_COLS && !a.bias && a.N >= 16384 && a.M > 32 && a.M <= 112 &&
-        !a.xf32 &&
-        a.K == 1280 && a.M * (a.K + 16) <= 150 * 1024) {
+    if (vk == VK_VOCAB_2P) {
       const int nt = (a.N + 15) / 16;
       const int grid = std::max((nt + 15) / 16, std::min(256, nt));
       // rows x (K / 2 halves x 2 B + 16), or the epilogue's staged tiles (M x 1 KB + pad)
@@ -1215,7 +1210,7 @@ int launch_gemm_tiles(const GemmArgs& a, int epi, int tile_sel, hipStream_t st) 
         default: return go(std::integral_constant<int, 7>());
       }
     }
-    if (mt >= 3 && epi == EPI_F32_COLS && a.N >= 16384) {
+    if (vk == VK_GEMV_X) {
       // vocabulary projection: NW column tiles share each staged X subchunk, so X
       // (re-read from L2 by every workgroup) costs 112/(16 NW) of the weight bytes
       constexpr int nw = 8;  // (16 waves spill)

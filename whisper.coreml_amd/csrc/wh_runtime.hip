@@ -998,10 +998,14 @@ struct Ctx : public wh_ctx {
     // the 8-bit copy serves the steps k_xattn_seg serves: up to 128 rows (dec_layers: skinny);
     // a larger step runs the first-pass kernel over the fp16 cross-KV, in either format
     const bool kv8 = ckv8 && n_win * group <= 128;
+    // vocab(): after the k_proj1 layers the final LayerNorm runs in the kernel's prologue, and
+    // a batch begun now reads the 8-bit copy where the format is set
+    const bool v8 = p1 && vocab_fmt == WH_VOCAB_FP8_E4M3;
+    const VocabKernel vk = step_vocab_kernel((int)sizeof(T), n_win * group, V, ns, p1, v8);
     return std::string("proj=") + (p1 ? (dec_fmt == WH_DEC_FP8_E4M3 ? "k_proj1<w8>" : "k_proj1") : "k_proj") + ",xattn=k_xattn_seg" +
            (kv8 ? (qp ? "<kv8,qproj>" : "<kv8>") : qp ? "<qproj>" : "") + ",self_attn=" +
            (p1 ? (h ? "k_self_attn<kco>" : "k_self_attn") : h ? "k_self_attn_qkv<pipe+kco>" : "k_self_attn_qkv") +
-           (p1 && vocab_fmt == WH_VOCAB_FP8_E4M3 ? ",tail=vocab<w8>+k_logit_part" : ",tail=vocab+k_logit_part");
+           (v8 ? ",tail=vocab<w8>+k_logit_part" : ",tail=vocab+k_logit_part") + ",vocab=" + vocab_kernel_name(vk);
   }
 
   int dec_layers_p1(int R, const int* rw, const int* rs, const int* rp, int ancG, int nwin, const int* wr0,
@@ -1083,6 +1087,7 @@ struct Ctx : public wh_ctx {
     if (final_x) {
       g.xf32 = final_x; g.ln_g = ln_g; g.ln_b = ln_b; g.ln_eps = 1e-5f;
     }
+    // both launchers take their kernel from step_vocab_kernel (wh_vocab_pick.h), as step_kernels does
     if (final_x && v8_step) {  // this batch's single-window step reads the 8-bit copy of E
       g.W = v8_codes; g.M = R; g.N = V; g.K = ns;
       const int rc = launch_vocab1_w8(g, v8_scales, st);

@@ -245,9 +245,9 @@ int v8_go(const GemmArgs& a, const float* wscale, hipStream_t st) {
 }  // namespace
 
 int launch_vocab1_w8(const GemmArgs& a, const float* wscale, hipStream_t st) {
-  // (8 B x ldo x rows and 16 K x tiles stay under 2^31: V <= 57344, K <= 1280)
-  if (a.M < 1 || a.M > 8 || a.N < 1 || a.N > 57344 || a.ldo < a.N || !a.W || !wscale || !a.xf32 || !a.ln_g || !a.ln_b ||
-      !a.out_f32 || a.bias || a.x_rows)
+  // the shapes served: wh_vocab_pick.h (the switch below holds one case per width it admits)
+  if (vocab_kernel(2, a.M, a.N, a.K, a.xf32 != nullptr, true) != VK_VOCAB1_W8 || a.ldo < a.N || !a.W || !wscale || !a.ln_g ||
+      !a.ln_b || !a.out_f32 || a.bias || a.x_rows)
     return -1;
   switch (a.K) {  //                 KW SW  D
     case 1280: return v8_go<v8_kw(1280), v8_sw(1280), V8_TMAX>(a, wscale, st);
